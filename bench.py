@@ -6,23 +6,28 @@ M=10 templates, 255x255 fp32 masks, 20 outer x 5 inner solver iterations.  One "
 (IoU cost tables -> cosine + relaxed assignment -> assignment-weighted mask mix; forward, is_test=1) over a batch of
 ``--frames`` synthetic frames already resident in HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--config 2|3|4|5|loop]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--frames B] [--config 2|3|4|5|loop] [--full]
+                  [--dump-outputs DIR]
 
 ``--config 5`` = configs[4] (N=200, M=20, fp16 mask planes, fp32 accumulation), ``--config 3`` = configs[2]
 (ResNet-50 + heads in bf16 -> fused 4-level ROIAlign+mean -> the layer, 8 frames), ``--config 4`` = configs[3]'s per-GPU
 share (ResNet-101 training step through DMM_Model, gradient mean over RCCL with the bucketed overlapped all-reduce;
 ``--gpus 8`` is the BASELINE configuration), ``--config loop`` = the evaluator's frame loop (video.FrameLoop: encoder +
 two-phase proposal prep + ROI features + matching + label merge, 4 videos of 255x448, eval solver setting 40x5); same
-JSON schema, ``config.workload`` names the configuration.  The default N = 1 line also carries compact results of
-configs 3, 5 and the frame loop under ``other_configs`` (``--no-others`` skips them).
+JSON schema, ``config.workload`` names the configuration.  With ``--full`` the default N = 1 line also carries compact
+results of configs 3, 5 and the frame loop under ``other_configs`` (``--no-others`` skips them).
+
+A plain run (no ``--full``) only sets up, warms up, times the K steps and prints the line.  ``--dump-outputs DIR``
+(configs 2 and 5) writes what the last timed step computed to DIR/*.npy (``dump_outputs``); the inputs come from seeded
+generators, so two builds run with the same arguments can be compared output for output.
 
 N > 1 runs one rank per GPU over RCCL: launched by the driver through torch.distributed.run, or -- when ``--gpus N`` is
-given WITHOUT a launcher around it (WORLD_SIZE unset) -- by this script re-executing itself under torch.distributed.run;
+given WITHOUT a launcher around it (WORLD_SIZE unset) -- by this script running itself under torch.distributed.run;
 a world size other than N is an error, never a number.  Every rank owns its own B
 frames (weak scaling; the forward has no exchange step), timing is bracketed by barrier + synchronize on both sides and
 the MAX over ranks is used.  Rank 0 prints ONE JSON line.
 
-At N = 1 the line also carries (``--no-extras`` skips them): ``cpu_baseline`` (the C oracle on the host cores, bounded
+At N = 1 with ``--full`` the line also carries (``--no-extras`` skips them): ``cpu_baseline`` (the C oracle on the host cores, bounded
 sample), ``batch_sweep`` / ``latency`` (frames per launch sequence in {1, 4, 8, 64, 512, 1024}), and ``roofline.traffic``
 measured by two child ``rocprofv3 --pmc`` passes of this same command (``traffic_source`` says where the number is from).
 """
@@ -69,7 +74,7 @@ def parse():
     ap.add_argument("--f32-out", action="store_true", help="config 5: write full_outmask in fp32 instead of fp16")
     ap.add_argument("--f16-solver", action="store_true", help="config 5: the fp16-state solver (tolerance mode: R within 1e-2, "
                     "argmax identical where the fp32 top-2 gap exceeds 0.02) instead of the default bit-exact fp32-state one on the "
-                    "same fp16 planes; it buys ~1 % (round 5), so the bit-exact form is the default")
+                    "same fp16 planes; it buys ~1 %% (round 5), so the bit-exact form is the default")
     ap.add_argument("--f32-solver", action="store_true", help="(the default since round 6; accepted for old command lines)")
     ap.add_argument("--bf16", action="store_true", help="config 4: the encoder as train_encoder.TrainEncoder -- bf16 channels-last, "
                     "fp32 master weights, HIP-graph replays, own BatchNorm / weight-gradient kernels (the shipped bf16 training form)")
@@ -82,14 +87,23 @@ def parse():
                                                            "median with min / max beside it")
     ap.add_argument("--settle", type=int, default=8, help="config 4: untimed steps before the W warm-ups (MIOpen solver "
                                                           "picks, allocator working set, bucketer steady mode)")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline does not need: cpu_baseline, "
+                    "batch_sweep / latency, in-run PMC traffic and the compact other_configs entries (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="config 2 / 5: after the timed steps, write what "
+                    "the last timed step computed as DIR/<name>.npy (float32; full_outmask as a fixed sample of frames)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="no cpu_baseline / batch_sweep / in-run PMC traffic")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no cpu_baseline / batch_sweep / in-run PMC "
+                                                             "traffic / other_configs")
     ap.add_argument("--no-traffic", action="store_true", help="do not spawn the rocprofv3 --pmc child passes")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to "
                                                       "exercise the multi-rank control flow on a single-GPU box)")
     a = ap.parse_args()
     a.config = a.config if a.config in ("loop", "train", "dropin") else int(a.config)
+    if a.dump_outputs and a.config not in (2, 5):
+        ap.error("--dump-outputs: only the matching layer's configurations (--config 2 or 5)")
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     return a
 
 
@@ -227,10 +241,11 @@ def profile_traffic(tag_file, key):
 
 
 def self_launch(args):
-    """``python bench.py --gpus N`` (N > 1) without a launcher around it: become ``python -m torch.distributed.run
-    --nproc-per-node N ... bench.py <same arguments>`` (one rank per GPU, rendezvous on 127.0.0.1), so that a plain
-    invocation can never print a 1-GPU number for an N-GPU request.  Under a launcher (WORLD_SIZE set) nothing happens
-    here; ``Runner`` then insists on WORLD_SIZE == N."""
+    """``python bench.py --gpus N`` (N > 1) without a launcher around it: run ``python -m torch.distributed.run
+    --nproc-per-node N ... bench.py <same arguments>`` (one rank per GPU, rendezvous on 127.0.0.1) as a child process and
+    exit with its status, so that a plain invocation can never print a 1-GPU number for an N-GPU request.  (A child, not
+    an exec: the device count above has already initialised the HIP runtime in this process.)  Under a launcher
+    (WORLD_SIZE set) nothing happens here; ``Runner`` then insists on WORLD_SIZE == N."""
     if args.gpus <= 1 or "WORLD_SIZE" in os.environ:
         return
     ndev = torch.cuda.device_count()
@@ -247,7 +262,7 @@ def self_launch(args):
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execve(sys.executable, cmd, env)                        # does not return
+    raise SystemExit(subprocess.call(cmd, env=env))
 
 
 def bind_to_gpu_numa_node(index):
@@ -362,6 +377,40 @@ def quick_ms(fn, n, warm=3, dev=None):
     return a.elapsed_time(b) / n
 
 
+DUMP_BUDGET = 60 * 10 ** 6          # bytes of .npy data per --dump-outputs directory (64 MB at most)
+DUMP_SEED = 20251015
+
+
+def dump_outputs(d, plan):
+    """What the last timed ``plan.run`` handed its caller, as ``d/<name>.npy`` (float32): match_score, det_score [B,M],
+    iters [B], sim [B,M,N], assignment (= Rb) [B,M,Pp] for every frame, and full_outmask [F,M,H,W] for a fixed, seeded
+    sample of F frames (``full_outmask_frames`` lists them) that fills the rest of DUMP_BUDGET.  If the per-frame tables
+    alone would take more than half of it, they are written for a seeded sample of frames too (``frames``)."""
+    rng = np.random.default_rng(DUMP_SEED)
+    B = plan.B
+    tables = {"match_score": plan.match_score, "det_score": plan.det_score, "iters": plan.iters, "sim": plan.sim,
+              "assignment": plan.Rb}
+    per_frame = 4 * sum(t[0].numel() for t in tables.values())
+    out = {}
+    if B * per_frame > DUMP_BUDGET // 2:
+        keep = np.sort(rng.choice(B, max(1, DUMP_BUDGET // 2 // (per_frame + 8)), replace=False))
+        out["frames"] = keep.astype(np.float64)
+    else:
+        keep = np.arange(B)
+    sel = torch.as_tensor(keep, dtype=torch.long, device=plan.full_outmask.device)
+    for name, t in tables.items():
+        out[name] = t.index_select(0, sel).float().cpu().numpy()
+    left = DUMP_BUDGET - sum(a.nbytes for a in out.values())
+    per_mask = 4 * plan.full_outmask[0].numel() + 8                    # + its entry in full_outmask_frames
+    fm = np.sort(rng.choice(B, max(1, min(B, left // per_mask)), replace=False))
+    out["full_outmask_frames"] = fm.astype(np.float64)
+    sel = torch.as_tensor(fm, dtype=torch.long, device=plan.full_outmask.device)
+    out["full_outmask"] = plan.full_outmask.index_select(0, sel).float().cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # configs[1] (default) and configs[4]: the matching layer on resident mask batches
 # ---------------------------------------------------------------------------------------------------------------------
@@ -417,6 +466,8 @@ def bench_layer(R, ci):
         plan.run(*inputs, **kw)
 
     elapsed = R.timed(step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, plan)
     # every frame ran the solver; a frame may take the reference's data-dependent early exit (relax_match.py:96-98)
     it_mean = float(plan.iters.float().mean())
     assert int(plan.iters.max()) == 20 and it_mean > 19.5, f"work was skipped inside the timed region ({it_mean})"
@@ -469,7 +520,7 @@ def bench_layer(R, ci):
         out["roofline_mix"] = {"bound": "hbm", "kernel": "dmm::mask_mix_rows_kernel", "achieved": round(mix_gbs, 1),
                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(mix_gbs / HBM_PEAK_GBS, 4),
                                "algorithmic_bytes_per_launch": int(fpl * b_mix), "avg_launch_ms": round(mix_ms, 4)}
-    extras = rank == 0 and world == 1 and not args.no_extras
+    extras = rank == 0 and world == 1 and args.full and not args.no_extras
     if extras:
         # frames per launch sequence: 1 and 4 are the product's sizes (one call per video / per training batch)
         sweep = {}
@@ -1242,7 +1293,7 @@ def main():
         out = bench_layer(R, args.config)
     if "per_rank" not in out:
         R.rank_spread(out, out["value"] / R.world)
-    if args.config == 2 and R.rank == 0 and R.world == 1 and not args.no_extras and not args.no_others:
+    if args.config == 2 and R.rank == 0 and R.world == 1 and args.full and not args.no_extras and not args.no_others:
         # the other BASELINE configurations and the frame loop, compact, so that the driver's default run sees them
         import copy
         others = {}
@@ -1284,6 +1335,7 @@ def main():
                              ("dropin", bench_dropin, dict(steps=100, warmup=0, frames=0))):
             a2 = copy.copy(args)
             a2.no_extras = True
+            a2.dump_outputs = None                               # the dump is the headline workload's
             for k, v in kw.items():
                 setattr(a2, k, v)
             R.args = a2

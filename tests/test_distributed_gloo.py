@@ -388,10 +388,16 @@ def test_gloo_world2_a_bucket_layout_mismatch_fails_loudly_on_every_rank():
     assert sorted(res) == [(0, True), (1, True)]
 
 
-def test_host_thread_pinning_is_silent_without_a_gpu_topology():
-    """``bind_host_threads_to_gpu``: no visible GPU / sysfs topology -> (None, no-op restore), masks untouched."""
+def test_host_thread_pinning_is_silent_without_a_gpu_topology(monkeypatch):
+    """``bind_host_threads_to_gpu``: no visible GPU / sysfs topology -> (None, no-op restore), masks untouched.  The device
+    query fails here as it does on a host without a GPU, so the case holds on a host that has one too."""
     import os
+    import torch
     from dmm_net_amd.distributed import bind_host_threads_to_gpu
+
+    def no_device(index):
+        raise RuntimeError("No HIP GPUs are available")
+    monkeypatch.setattr(torch.cuda, "get_device_properties", no_device)
     before = os.sched_getaffinity(0)
     node, restore = bind_host_threads_to_gpu(0)
     assert node is None

@@ -106,6 +106,48 @@ def test_bench_compacts_the_other_workloads_lines():
     assert c["by_batch"]["64"]["kernels"] == {"mask_mix_bwd": {"ms": 0.175, "frac": 0.686}, "relax_match_bwd": {"ms": 0.157}}
 
 
+def test_bench_dump_outputs_stays_in_budget_and_samples_the_same_frames(tmp_path, monkeypatch):
+    """``bench.dump_outputs`` (``--dump-outputs DIR``): float32 .npy files within DUMP_BUDGET, every frame's tables, a
+    seeded sample of full_outmask frames (the same frames from run to run), and the tables sampled too when they alone
+    would take more than half of the budget."""
+    import sys
+    import types
+    import torch
+    from conftest import ROOT
+    sys.path.insert(0, ROOT)
+    import bench
+    B, N, M, H, W = 40, 7, 3, 9, 11
+    g = torch.Generator().manual_seed(3)
+    plan = types.SimpleNamespace(
+        B=B, match_score=torch.rand((B, M), generator=g), det_score=torch.rand((B, M), generator=g),
+        iters=torch.randint(1, 21, (B,), generator=g, dtype=torch.int32), sim=torch.rand((B, M, N), generator=g),
+        Rb=torch.rand((B, M, N), generator=g), full_outmask=torch.rand((B, M, H, W), generator=g).half())
+    per_table_frame = 4 * (M + M + 1 + M * N + M * N)
+    per_mask = 4 * M * H * W
+    monkeypatch.setattr(bench, "DUMP_BUDGET", B * per_table_frame + 12 * per_mask)
+
+    def dump(d):
+        bench.dump_outputs(str(d), plan)
+        return {p.stem: np.load(p) for p in d.iterdir()}
+    a, b = dump(tmp_path / "a"), dump(tmp_path / "b")
+    assert sorted(a) == ["assignment", "det_score", "full_outmask", "full_outmask_frames", "iters", "match_score", "sim"]
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_BUDGET
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    fm = a["full_outmask_frames"].astype(np.int64)
+    assert len(fm) == 11 and len(set(fm.tolist())) == 11
+    np.testing.assert_array_equal(a["full_outmask"], plan.full_outmask[torch.from_numpy(fm)].float().numpy())
+    np.testing.assert_array_equal(a["sim"], plan.sim.numpy())
+    np.testing.assert_array_equal(a["iters"], plan.iters.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", B * per_table_frame)           # tables alone > half: sampled
+    c = dump(tmp_path / "c")
+    keep = c["frames"].astype(np.int64)
+    assert len(keep) == B * per_table_frame // 2 // (per_table_frame + 8)
+    assert sum(v.nbytes for v in c.values()) <= bench.DUMP_BUDGET
+    np.testing.assert_array_equal(c["assignment"], plan.Rb[torch.from_numpy(keep)].numpy())
+    assert len(c["full_outmask_frames"]) >= 1
+
+
 def test_importing_the_matching_layer_leaves_the_environment_alone(tmp_path):
     """The one-line swap imports ``dmm_net_amd.match_model`` only: that must neither touch ``os.environ`` (MIOpen's
     MIOPEN_USER_DB_PATH is set when an ENCODER is constructed, not at import) nor write under the home directory."""

@@ -3,9 +3,9 @@
 
     python tools/collect_profiles.py r01 gpurun_out/profiles_new
 
-  <tag>_bench.json                  python bench.py                      (all extras: cpu baseline, sweep, in-run traffic)
+  <tag>_bench.json                  python bench.py --full               (all extras: cpu baseline, sweep, in-run traffic)
   <tag>_bench_single_stream.json    python bench.py --no-pipeline --no-extras
-  <tag>_bench_config5.json / _config3.json     python bench.py --config 5 / 3
+  <tag>_bench_config5.json / _config3.json     python bench.py --config 5 --full / --config 3
   <tag>_bench_frame_loop.json / _bench_config4_1gpu(_autocast|_bf16).json   python bench.py --config loop / --config 4 [--autocast|--bf16]
   <tag>_kernel_stats_config4(_autocast|_bf16).csv   rocprofv3 --kernel-trace --stats of the same three settings of config 4
   <tag>_bench_dropin.json           python bench.py --config dropin --steps 200   (wall vs device per call of the drop-in)
@@ -41,11 +41,11 @@ def last_json(stdout):
 
 
 if not only_pmc and os.environ.get("ONLY_STATS") is None:
-    open(os.path.join(out, f"{tag}_bench.json"), "w").write(last_json(run(bench).stdout) + "\n")
+    open(os.path.join(out, f"{tag}_bench.json"), "w").write(last_json(run(bench + ["--full"]).stdout) + "\n")
     open(os.path.join(out, f"{tag}_bench_single_stream.json"), "w").write(
         last_json(run(bench + ["--no-pipeline", "--no-extras"]).stdout) + "\n")
     open(os.path.join(out, f"{tag}_bench_config5.json"), "w").write(
-        last_json(run(bench + ["--config", "5", "--no-cpu-baseline"]).stdout) + "\n")
+        last_json(run(bench + ["--config", "5", "--full", "--no-cpu-baseline"]).stdout) + "\n")
     open(os.path.join(out, f"{tag}_bench_config3.json"), "w").write(
         last_json(run(bench + ["--config", "3"]).stdout) + "\n")
     open(os.path.join(out, f"{tag}_bench_frame_loop.json"), "w").write(
