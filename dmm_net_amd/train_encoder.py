@@ -530,7 +530,9 @@ class _DetConvFn(torch.autograd.Function):
                     dw = torch.ops.aten.convolution_backward(dy, x, w, None, list(stride), list(padding), list(dilation),
                                                              False, [0, 0], groups, [False, True, False])[1]
         if has_b and need[2]:
-            db = dy.float().sum((0, 2, 3)).to(dy.dtype)
+            # 16-bit gradients are summed in fp32; wider ones in their own precision (an fp32 sum of fp64 terms loses digits)
+            wide = dy.float() if dy.element_size() < 4 else dy
+            db = wide.sum((0, 2, 3)).to(dy.dtype)
         return dx, dw, db, None, None, None, None
 
 

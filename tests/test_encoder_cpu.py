@@ -217,3 +217,87 @@ def test_train_encoder_clip_call_keeps_the_per_frame_batchnorm_statistics_on_the
     import pytest
     with pytest.raises(AssertionError):
         te(torch.cat(frames, 0), bn_groups=4)                    # 6 images do not split into 4 groups
+
+
+def _conv_f64_case(seed, B, ci, co, H, W, k, stride, padding, dilation, groups, bias):
+    g = torch.Generator().manual_seed(seed)
+    kh, kw = (k, k) if isinstance(k, int) else k
+    x = torch.randn((B, ci, H, W), generator=g, dtype=torch.float64)
+    w = torch.randn((co, ci // groups, kh, kw), generator=g, dtype=torch.float64)
+    b = torch.randn((co,), generator=g, dtype=torch.float64) if bias else None
+    y = torch.nn.functional.conv2d(x, w, b, stride, padding, dilation, groups)
+    dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+    return x, w, b, dy
+
+
+@pytest.mark.parametrize("ci,co,H,W,k,stride,padding,dilation,groups", [
+    (8, 8, 9, 11, 3, 1, 0, 1, 1),            # stride 1: the data gradient as a forward convolution of the flipped weight
+    (8, 12, 9, 11, 3, 1, 1, 1, 1),
+    (6, 8, 7, 10, 3, 1, 2, 1, 1),
+    (8, 16, 6, 7, 1, 1, 0, 1, 1),
+    (4, 6, 9, 12, (3, 5), 1, (1, 2), 1, 1),   # non-square kernel and padding
+    (3, 16, 21, 27, 7, 2, 3, 1, 1),           # the 7x7 stem (stride 2): convolution_backward
+    (3, 8, 20, 26, 7, 1, 3, 1, 1),            # 7x7 at stride 1: the flipped path with padding 3
+    (8, 8, 9, 11, 3, 2, 1, 1, 1),             # stride 2 with odd sizes
+    (6, 8, 8, 9, 3, 1, 3, 1, 1),              # padding > k - 1: convolution_backward
+    (8, 12, 9, 11, 3, 1, 1, 1, 2),            # groups: the library weight gradient
+    (8, 8, 11, 13, 3, 1, 2, 2, 1),            # dilation: the library weight gradient
+])
+@pytest.mark.parametrize("bias", [True, False])
+def test_det_conv_fn_matches_autograd_of_conv2d_in_fp64(ci, co, H, W, k, stride, padding, dilation, groups, bias):
+    """``_DetConvFn`` (the deterministic mode's stock convolution) in float64 on the host against ``torch.autograd.grad`` of
+    ``F.conv2d``: y, dx, dw and db, every branch of its backward.  Both are exact fp64 arithmetic in different orders, so any
+    relative error above 1e-12 is a wrong index, flip, transpose or sum, not rounding."""
+    from dmm_net_amd.train_encoder import _DetConvFn
+    F = torch.nn.functional
+    x, w, b, dy = _conv_f64_case(H * W + co, 2, ci, co, H, W, k, stride, padding, dilation, groups, bias)
+    st, pd, dl = [(v, v) if isinstance(v, int) else tuple(v) for v in (stride, padding, dilation)]
+    ins = [t.clone().requires_grad_(True) for t in (x, w) + ((b,) if bias else ())]
+    y = _DetConvFn.apply(ins[0], ins[1], ins[2] if bias else None, st, pd, dl, groups)
+    got = (y,) + torch.autograd.grad(y, ins, dy)
+    ref_ins = [t.clone().requires_grad_(True) for t in (x, w) + ((b,) if bias else ())]
+    ry = F.conv2d(ref_ins[0], ref_ins[1], ref_ins[2] if bias else None, st, pd, dl, groups)
+    want = (ry,) + torch.autograd.grad(ry, ref_ins, dy)
+    for name, a, r in zip(("y", "dx", "dw", "db"), got, want):
+        assert a.dtype == torch.float64 and a.shape == r.shape, name
+        err = float((a - r).abs().max()) / float(r.abs().max())
+        assert err <= 1e-12, (name, err)
+
+
+def test_det_conv_fn_bias_gradient_sums_16_bit_inputs_in_fp32():
+    """The bias gradient of 16-bit operands is an fp32 sum rounded once (what the bf16 step has always computed); of fp64
+    ones an fp64 sum."""
+    from dmm_net_amd.train_encoder import _DetConvFn
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn((2, 8, 16, 16), generator=g).bfloat16().requires_grad_(True)
+    w = torch.randn((8, 8, 3, 3), generator=g).bfloat16().requires_grad_(True)
+    b = torch.randn((8,), generator=g).bfloat16().requires_grad_(True)
+    y = _DetConvFn.apply(x, w, b, (1, 1), (1, 1), (1, 1), 1)
+    dy = torch.randn(y.shape, generator=g).bfloat16()
+    (db,) = torch.autograd.grad(y, [b], dy)
+    assert db.dtype == torch.bfloat16 and torch.equal(db, dy.float().sum((0, 2, 3)).bfloat16())
+    dy64 = (torch.ones((1, 4, 300, 300), dtype=torch.float64) * (1.0 + 2.0 ** -40))
+    x64 = torch.zeros((1, 4, 300, 300), dtype=torch.float64, requires_grad=True)
+    w64 = torch.zeros((4, 4, 1, 1), dtype=torch.float64, requires_grad=True)
+    b64 = torch.zeros((4,), dtype=torch.float64, requires_grad=True)
+    y = _DetConvFn.apply(x64, w64, b64, (1, 1), (0, 0), (1, 1), 1)
+    (db,) = torch.autograd.grad(y, [b64], dy64)
+    assert torch.equal(db, dy64.sum((0, 2, 3)))                  # (an fp32 sum would drop the 2^-40)
+
+
+def test_tap_split_adds_the_body_and_head_gradients():
+    """``_TapSplit``: two aliases of x whose gradients autograd keeps apart; its backward is their sum, or the one that came."""
+    from dmm_net_amd.train_encoder import _TapSplit
+    g = torch.Generator().manual_seed(2)
+    x = torch.randn((2, 4, 5, 6), generator=g, dtype=torch.float64, requires_grad=True)
+    gb, gh = torch.randn((2,) + tuple(x.shape), generator=g, dtype=torch.float64)
+    body, head = _TapSplit.apply(x)
+    assert torch.equal(body, x) and torch.equal(head, x)
+    (dx,) = torch.autograd.grad((body * gb).sum() + (head * gh).sum() + (body * 3.0).sum(), [x])
+    assert torch.equal(dx, (gb + 3.0) + gh)                        # (autograd sums the body's own terms first)
+    for used, want in ((0, gb), (1, gh)):
+        out = _TapSplit.apply(x)
+        (dx,) = torch.autograd.grad((out[used] * want).sum(), [x])
+        assert torch.equal(dx, want)
+    assert _TapSplit.backward(None, None, gh) is gh and _TapSplit.backward(None, gb, None) is gb
+    assert _TapSplit.backward(None, None, None) is None
