@@ -3,53 +3,84 @@
 The library is built in-tree by ``__graft_entry__.build()`` (or ``make -C dmm_net_amd/csrc``) and
 loaded with ctypes.  There is NO fallback: if the library is missing or a call fails, the product
 raises -- nothing here ever routes to a CPU path.
+
+The ctypes signatures and the enum values are read from the header itself (``parse_header``): it is the
+one description of the ABI, and a binding cannot drift from it.
 """
 from __future__ import annotations
 
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdmm_match.so")        # no environment override: see use_library()
 CSRC = os.path.join(_HERE, "csrc")
+HEADER = os.path.join(_HERE, os.pardir, "include", "dmm_match.h")
 
-DMM_OK = 0
-DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_PACKED1 = 0, 1, 2, 3
 MAX_TEMPLATES = 32
 MAX_PROPOSALS = 256
 FRAME_TABLE = -(1 << 63)          # DMM_FRAME_TABLE: sp_b sentinel, masks_p = device table of per-frame base pointers
 
-# every symbol include/dmm_match.h declares
-SYMBOLS = (
-    "dmm_abi_version", "dmm_status_string", "dmm_last_hip_error", "dmm_build_info", "dmm_launch_count",
-    "dmm_set_option", "dmm_get_option", "dmm_reset_options",
-    "dmm_iou_counts", "dmm_iou_counts_dual", "dmm_feature_normalize_f32", "dmm_cosine_f32", "dmm_cosine_features_f32", "dmm_feature_sim_bwd_f32", "dmm_relax_match_f32", "dmm_relax_solve_f32",
-    "dmm_relax_bwd_workspace_bytes", "dmm_relax_match_bwd_f32",
-    "dmm_mask_mix", "dmm_mask_mix_to", "dmm_mask_mix_shared_to", "dmm_mask_mix_shared_frames", "dmm_mask_mix_bwd", "dmm_workspace_bytes", "dmm_match_forward", "dmm_match_forward_ws", "dmm_roialign4_mean_fwd", "dmm_roialign4_mean_bwd",
-    "dmm_iou_counts_frames", "dmm_iou_counts_dual_frames", "dmm_mask_mix_frames", "dmm_mask_mix_bwd_frames",
-    "dmm_bias_act_bf16", "dmm_paste_masks_f32", "dmm_nms_f32", "dmm_pack_words", "dmm_pack_masks", "dmm_mask_boxes_f32", "dmm_merge_labels_f32", "dmm_ragged_pad",
-    "dmm_workspace_bytes_packed", "dmm_match_forward_packed", "dmm_proposal_boxes_f32", "dmm_nms_slots_f32",
-    "dmm_paste_kept_f32", "dmm_step_select_i32", "dmm_step_advance", "dmm_commit_masks_f32", "dmm_roialign4_mean_nhwc_fwd",
-    "dmm_conv1x1_bf16", "dmm_im2col3x3_bf16", "dmm_bias_relu_maxpool_bf16", "dmm_relax_any_scratch_bytes", "dmm_relax_match_any_f32", "dmm_relax_match_f16s", "dmm_match_solve_packed", "dmm_step_finish_f32",
-    "dmm_matching_loss_f32", "dmm_match_train_tape_bytes", "dmm_match_train_forward_workspace_bytes", "dmm_match_train_forward",
-    "dmm_match_train_backward_workspace_bytes", "dmm_match_train_backward",
-    "dmm_bn_stats_bf16", "dmm_bn_apply_bf16", "dmm_bn_bwd_reduce_bf16", "dmm_bn_bwd_dx_bf16",
-    "dmm_bn_stats_grouped_bf16", "dmm_bn_apply_grouped_bf16", "dmm_bn_bwd_reduce_grouped_bf16", "dmm_bn_bwd_dx_grouped_bf16",
-    "dmm_graph_nodes_to_kernels", "dmm_wprep3x3_bf16", "dmm_cast_many_bf16", "dmm_subsample2_bf16", "dmm_upsample2_zero_bf16", "dmm_wgrad_workspace_bytes", "dmm_wgrad_bf16", "dmm_wgrad3x3_bf16",
-    # deterministic forms (dmm_net_amd.set_deterministic)
-    "dmm_bn_det_workspace_bytes", "dmm_bn_stats_det_grouped_bf16", "dmm_bn_apply_det_grouped_bf16",
-    "dmm_bn_bwd_reduce_det_grouped_bf16", "dmm_bn_bwd_dx_det_grouped_bf16", "dmm_bn_fold_det",
-    "dmm_mask_mix_bwd_det_workspace_bytes", "dmm_mask_mix_bwd_det", "dmm_mask_mix_bwd_frames_det",
-    "dmm_roialign4_mean_bwd_det_workspace_bytes", "dmm_roialign4_mean_bwd_det",
-    "dmm_match_train_backward_det_workspace_bytes", "dmm_match_train_backward_det",
-)
-
-_lib = None
-
 
 class DmmError(RuntimeError):
     pass
+
+
+# the closed map of the header's non-pointer types (every pointer, and dmm_stream_t, is passed as c_void_p)
+_CTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "long long": ctypes.c_longlong, "size_t": ctypes.c_size_t,
+           "float": ctypes.c_float, "dmm_stream_t": ctypes.c_void_p}
+
+
+def _ctype(decl: str, fn: str, is_return: bool):
+    """One C type (a parameter with its name, or a return type) -> its ctypes type."""
+    if "*" in decl or "[" in decl:                        # pointers and arrays; a returned string is read by ctypes
+        string = decl.replace("*", " ").split() == ["const", "char"]
+        return ctypes.c_char_p if is_return and string else ctypes.c_void_p
+    words = [w for w in decl.split() if w != "const"]
+    if is_return and words == ["void"]:
+        return None
+    t = " ".join(words if is_return else words[:-1])
+    if t not in _CTYPES:
+        raise DmmError(f"include/dmm_match.h: {fn} uses type '{t or decl.strip()}', which the ctypes binding does not map")
+    return _CTYPES[t]
+
+
+def parse_header(text: str):
+    """include/dmm_match.h -> ({function: (restype, argtypes)} in declaration order, {enum tag: {enumerator: value}})."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#[^\n]*", "", text, flags=re.M)
+    decls = {}
+    for ret, fn, params in re.findall(r"\bDMM_API\s+([^;(]*?)\s*\b(dmm_\w+)\s*\(([^)]*)\)\s*;", text):
+        params = params.strip()
+        args = [] if params in ("", "void") else [_ctype(p, fn, False) for p in params.split(",")]
+        decls[fn] = (_ctype(ret, fn, True), args)
+    enums = {}
+    for tag, body in re.findall(r"\benum\s+(\w+)\s*\{([^}]*)\}", text):
+        values, v = {}, -1
+        for item in filter(None, (s.strip() for s in body.split(","))):
+            name, _, val = (s.strip() for s in item.partition("="))
+            v = int(val, 0) if val else v + 1
+            values[name] = v
+        enums[tag] = values
+    return decls, enums
+
+
+try:
+    with open(HEADER) as _f:
+        _DECLS, _ENUMS = parse_header(_f.read())
+except OSError as _e:
+    raise DmmError(f"{os.path.normpath(HEADER)} is missing: the C ABI's bindings are read from it ({_e})") from None
+
+SYMBOLS = tuple(_DECLS)                                   # every function include/dmm_match.h declares
+DMM_OK, DMM_ERR_BAD_ARG, DMM_ERR_UNSUPPORTED, DMM_ERR_LAUNCH, DMM_ERR_WORKSPACE = (_ENUMS["dmm_status"][k] for k in (
+    "DMM_OK", "DMM_ERR_BAD_ARG", "DMM_ERR_UNSUPPORTED", "DMM_ERR_LAUNCH", "DMM_ERR_WORKSPACE"))
+DTYPE_F32, DTYPE_F16, DTYPE_BF16, DTYPE_PACKED1 = (_ENUMS["dmm_dtype"]["DMM_" + k] for k in ("F32", "F16", "BF16", "PACKED1"))
+# include/dmm_match.h (0): dispatch options, set through the ABI (the library reads no environment variable)
+OPTIONS = {k[len("DMM_OPT_"):]: v for k, v in _ENUMS["dmm_option"].items() if k != "DMM_OPT_COUNT"}
+
+_lib = None
 
 
 def build(verbose: bool = False) -> str:
@@ -82,185 +113,11 @@ def load():
                        "(the HIP extension is mandatory; there is no CPU fallback)")
     import torch  # noqa: F401  -- load torch's HIP runtime first so both share one libamdhip64
     L = ctypes.CDLL(LIB_PATH)
-    for s in SYMBOLS:
-        if not hasattr(L, s):
-            raise DmmError(f"{LIB_PATH} does not export {s}")
-    c_int, c_float, c_i64, vp, sz = ctypes.c_int, ctypes.c_float, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t
-    L.dmm_abi_version.restype = c_int
-    L.dmm_status_string.restype = ctypes.c_char_p
-    L.dmm_status_string.argtypes = [c_int]
-    L.dmm_last_hip_error.restype = c_int
-    L.dmm_build_info.restype = ctypes.c_char_p
-    L.dmm_launch_count.restype = ctypes.c_longlong
-    L.dmm_set_option.argtypes = [c_int, c_int]
-    L.dmm_set_option.restype = c_int
-    L.dmm_get_option.argtypes = [c_int]
-    L.dmm_get_option.restype = c_int
-    L.dmm_reset_options.restype = c_int
-    L.dmm_iou_counts.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, vp, vp,
-                                 vp, vp, vp, vp]
-    L.dmm_iou_counts_dual.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_i64,
-                                      c_i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dmm_iou_counts_frames.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, vp, vp, vp, vp, vp,
-                                        vp]
-    L.dmm_iou_counts_dual_frames.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_i64, c_i64,
-                                             c_i64, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dmm_mask_mix_frames.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, vp, vp, vp, c_i64, c_i64,
-                                      vp]
-    L.dmm_mask_mix_bwd_frames.argtypes = [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_i64, vp, vp, vp, vp]
-    L.dmm_feature_normalize_f32.argtypes = [vp, c_i64, c_int, vp, vp, vp]
-    L.dmm_cosine_f32.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp, vp, vp]
-    L.dmm_feature_sim_bwd_f32.argtypes = [vp, vp, vp, vp, c_float, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, vp, vp,
-                                          vp, vp, vp]
-    L.dmm_feature_sim_bwd_f32.restype = c_int
-    L.dmm_cosine_features_f32.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp]
-    L.dmm_cosine_features_f32.restype = c_int
-    L.dmm_relax_match_f32.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, c_float, c_int, c_int, c_float,
-                                      c_int, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dmm_relax_match_f16s.argtypes = L.dmm_relax_match_f32.argtypes
-    L.dmm_relax_match_any_f32.argtypes = L.dmm_relax_match_f32.argtypes[:-1] + [vp, sz, vp]
-    L.dmm_relax_match_any_f32.restype = c_int
-    L.dmm_relax_any_scratch_bytes.argtypes = [c_int, c_int, c_int]
-    L.dmm_relax_any_scratch_bytes.restype = sz
-    L.dmm_relax_match_f16s.restype = c_int
-    L.dmm_relax_solve_f32.argtypes = [vp, c_int, c_int, c_int, vp, vp, c_int, c_int, c_float, vp, vp, vp, vp, vp]
-    L.dmm_relax_bwd_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    L.dmm_relax_bwd_workspace_bytes.restype = sz
-    L.dmm_relax_match_bwd_f32.argtypes = [vp, vp, c_int, c_int, c_int, vp, vp, c_int, c_int, c_float, c_int, vp, vp, vp,
-                                          vp, vp, sz, vp]
-    L.dmm_roialign4_mean_fwd.argtypes = [vp, c_int, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp]
-    L.dmm_conv1x1_bf16.argtypes = [vp, vp, vp, vp, c_i64, c_int, c_int, c_int, vp, vp, sz, vp]
-    L.dmm_conv1x1_bf16.restype = c_int
-    L.dmm_im2col3x3_bf16.argtypes = [vp, c_int, c_int, c_int, c_int, c_int, vp, vp]
-    L.dmm_im2col3x3_bf16.restype = c_int
-    L.dmm_bias_relu_maxpool_bf16.argtypes = [vp, vp, c_int, c_int, c_int, c_int, vp, vp]
-    L.dmm_bias_relu_maxpool_bf16.restype = c_int
-    L.dmm_roialign4_mean_nhwc_fwd.argtypes = [vp, c_int, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp]
-    L.dmm_roialign4_mean_nhwc_fwd.restype = c_int
-    L.dmm_roialign4_mean_bwd.argtypes = [vp, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp]
-    L.dmm_paste_masks_f32.argtypes = [vp, c_int, c_int, vp, c_int, c_int, c_float, c_int, vp, c_i64, vp, vp, vp]
-    L.dmm_pack_words.argtypes = [c_int]
-    L.dmm_pack_words.restype = c_i64
-    L.dmm_pack_masks.argtypes = [vp, c_int, c_i64, c_int, c_i64, vp, c_i64, vp]
-    L.dmm_nms_f32.argtypes = [vp, vp, vp, c_int, c_int, c_float, c_int, vp, vp, vp]
-    L.dmm_mask_boxes_f32.argtypes = [vp, c_int, c_int, c_int, c_i64, c_float, vp, vp, vp]
-    L.dmm_merge_labels_f32.argtypes = [vp, c_int, c_int, c_int, c_i64, c_i64, vp, vp, vp]
-    L.dmm_ragged_pad.argtypes = [vp, vp, c_int, c_int, c_i64, vp, vp]
-    L.dmm_mask_mix.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, vp, vp, vp, c_i64,
-                               c_i64, vp]
-    L.dmm_bias_act_bf16.argtypes = [vp, vp, vp, c_i64, c_int, c_int, vp]
-    L.dmm_bias_act_bf16.restype = c_int
-    L.dmm_bn_stats_bf16.argtypes = [vp, c_i64, c_int, vp, vp]
-    L.dmm_bn_apply_bf16.argtypes = [vp, vp, c_i64, c_int, vp, vp, vp, vp, vp, c_float, c_float, c_int, vp, vp, vp]
-    L.dmm_bn_bwd_reduce_bf16.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, c_int, vp, vp]
-    L.dmm_bn_bwd_dx_bf16.argtypes = [vp, vp, vp, c_i64, c_int, vp, vp, vp, vp, c_int, vp, vp, vp, vp, vp]
-    L.dmm_bn_stats_grouped_bf16.argtypes = [vp, c_i64, c_int, c_int, vp, vp]
-    L.dmm_bn_apply_grouped_bf16.argtypes = [vp, vp, c_i64, c_int, c_int, vp, vp, vp, vp, vp, c_float, c_float, c_int, vp, vp, vp]
-    L.dmm_bn_bwd_reduce_grouped_bf16.argtypes = [vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp, vp, c_int, vp, vp]
-    L.dmm_bn_bwd_dx_grouped_bf16.argtypes = [vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, vp, vp, vp]
-    L.dmm_graph_nodes_to_kernels.argtypes = [vp, c_int, vp, vp, vp]
-    L.dmm_wgrad_bf16.argtypes = [vp, vp, c_i64, c_int, c_int, c_i64, c_i64, vp, vp, sz, vp]
-    L.dmm_wgrad3x3_bf16.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, sz, vp]
-    L.dmm_wprep3x3_bf16.argtypes = [vp, c_int, c_i64, vp]
-    L.dmm_wprep3x3_bf16.restype = c_int
-    L.dmm_cast_many_bf16.argtypes = [vp, c_int, c_i64, vp]
-    L.dmm_cast_many_bf16.restype = c_int
-    L.dmm_subsample2_bf16.argtypes = [vp, c_int, c_int, c_int, c_int, vp, vp]
-    L.dmm_subsample2_bf16.restype = c_int
-    L.dmm_upsample2_zero_bf16.argtypes = [vp, c_int, c_int, c_int, c_int, vp, vp]
-    L.dmm_upsample2_zero_bf16.restype = c_int
-    L.dmm_wgrad_workspace_bytes.argtypes = [c_i64, c_int, c_int]
-    L.dmm_wgrad_workspace_bytes.restype = sz
-    L.dmm_wgrad_bf16.restype = L.dmm_wgrad3x3_bf16.restype = c_int
-    for f in ("dmm_bn_stats_bf16", "dmm_bn_apply_bf16", "dmm_bn_bwd_reduce_bf16", "dmm_bn_bwd_dx_bf16",
-              "dmm_bn_stats_grouped_bf16", "dmm_bn_apply_grouped_bf16", "dmm_bn_bwd_reduce_grouped_bf16",
-              "dmm_bn_bwd_dx_grouped_bf16", "dmm_graph_nodes_to_kernels"):
-        getattr(L, f).restype = c_int
-    L.dmm_bn_det_workspace_bytes.argtypes = [c_i64, c_int, c_int]
-    L.dmm_bn_det_workspace_bytes.restype = sz
-    L.dmm_bn_stats_det_grouped_bf16.argtypes = [vp, c_i64, c_int, c_int, vp, sz, vp]
-    L.dmm_bn_apply_det_grouped_bf16.argtypes = [vp, vp, c_i64, c_int, c_int, vp, sz, vp, vp, vp, vp, c_float, c_float, c_int,
-                                                vp, vp, vp]
-    L.dmm_bn_bwd_reduce_det_grouped_bf16.argtypes = [vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp, vp, c_int, vp, sz, vp]
-    L.dmm_bn_bwd_dx_det_grouped_bf16.argtypes = [vp, vp, vp, vp, c_i64, c_int, c_int, vp, vp, vp, vp, sz, c_int, vp, vp, vp, vp,
-                                                 vp]
-    L.dmm_bn_fold_det.argtypes = [vp, sz, c_i64, c_int, c_int, vp, vp]
-    L.dmm_mask_mix_bwd_det_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    L.dmm_mask_mix_bwd_det_workspace_bytes.restype = sz
-    L.dmm_mask_mix_bwd_det.argtypes = [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, vp, vp, vp, vp, sz,
-                                       vp]
-    L.dmm_mask_mix_bwd_frames_det.argtypes = [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_i64, vp, vp, vp, vp, sz,
-                                              vp]
-    L.dmm_roialign4_mean_bwd_det_workspace_bytes.argtypes = [c_int, vp, vp]
-    L.dmm_roialign4_mean_bwd_det_workspace_bytes.restype = sz
-    L.dmm_roialign4_mean_bwd_det.argtypes = [vp, c_int, c_int, vp, vp, vp, vp, c_int, vp, vp, sz, vp]
-    for f in ("dmm_bn_stats_det_grouped_bf16", "dmm_bn_apply_det_grouped_bf16", "dmm_bn_bwd_reduce_det_grouped_bf16",
-              "dmm_bn_bwd_dx_det_grouped_bf16", "dmm_bn_fold_det", "dmm_mask_mix_bwd_det", "dmm_mask_mix_bwd_frames_det",
-              "dmm_roialign4_mean_bwd_det"):
-        getattr(L, f).restype = c_int
-    L.dmm_mask_mix_to.argtypes = [vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, vp, vp, vp, c_int, c_i64,
-                                  c_i64, vp]
-    L.dmm_mask_mix_to.restype = c_int
-    L.dmm_mask_mix_shared_to.argtypes = L.dmm_mask_mix_to.argtypes
-    L.dmm_mask_mix_shared_to.restype = c_int
-    L.dmm_mask_mix_shared_frames.argtypes = L.dmm_mask_mix_frames.argtypes
-    L.dmm_mask_mix_shared_frames.restype = c_int
-    L.dmm_mask_mix_bwd.argtypes = [vp, vp, c_int, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, vp, vp, vp, vp]
-    L.dmm_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    L.dmm_workspace_bytes.restype = sz
-    L.dmm_match_forward.argtypes = [vp, vp, c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
-                                    c_i64, c_i64, vp, vp, c_float, c_int, c_int, c_float, c_int, vp, vp, vp, vp,
-                                    vp, vp, vp, vp, sz, vp]
-    L.dmm_match_forward_ws.argtypes = [vp, vp, c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
-                                       c_i64, c_i64, vp, vp, c_float, c_int, c_int, c_float, c_int, vp, vp, vp, vp,
-                                       vp, vp, vp, vp, sz, ctypes.POINTER(c_int), vp]
-    L.dmm_workspace_bytes_packed.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    L.dmm_workspace_bytes_packed.restype = sz
-    L.dmm_match_forward_packed.argtypes = [vp, vp, vp, c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
-                                           c_i64, c_i64, c_i64, c_i64, vp, vp, c_float, c_int, c_int, c_float, c_int, vp,
-                                           vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.dmm_proposal_boxes_f32.argtypes = [vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_float, c_int, vp, vp, vp]
-    L.dmm_nms_slots_f32.argtypes = [vp, vp, vp, c_int, c_int, c_float, c_int, vp, vp, vp, vp]
-    L.dmm_paste_kept_f32.argtypes = [vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, vp, vp, vp,
-                                     c_i64, vp, vp, vp, vp, vp]
-    L.dmm_match_solve_packed.argtypes = [vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, vp, vp, c_float, c_int,
-                                         c_int, c_float, c_int, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    L.dmm_match_solve_packed.restype = c_int
-    L.dmm_step_finish_f32.argtypes = [vp, c_int, vp, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
-                                      vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.dmm_step_finish_f32.restype = c_int
-    L.dmm_step_select_i32.argtypes = [vp, vp, c_int, vp, vp]
-    L.dmm_step_advance.argtypes = [vp, vp]
-    L.dmm_commit_masks_f32.argtypes = [vp, vp, vp, c_int, c_i64, vp]
-    L.dmm_matching_loss_f32.argtypes = [vp, vp, vp, vp, c_int, c_int, c_int, vp, vp, vp, vp, vp]
-    L.dmm_matching_loss_f32.restype = c_int
-    L.dmm_match_train_forward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
-    L.dmm_match_train_forward_workspace_bytes.restype = sz
-    L.dmm_match_train_tape_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
-    L.dmm_match_train_tape_bytes.restype = sz
-    L.dmm_match_train_forward.argtypes = [vp, vp, vp, c_int, vp, vp, vp, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64,
-                                          c_i64, c_i64, c_i64, c_i64, vp, vp, c_float, c_int, c_int, c_float, c_int, vp, vp,
-                                          vp, vp, vp, vp, vp, vp, vp, vp, sz, vp, sz, ctypes.POINTER(c_int), vp]
-    L.dmm_match_train_forward.restype = c_int
-    L.dmm_match_train_backward_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int]
-    L.dmm_match_train_backward_workspace_bytes.restype = sz
-    L.dmm_match_train_backward.argtypes = [vp, c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, c_int, c_int, c_int, c_int,
-                                           c_int, c_i64, c_i64, vp, vp, c_float, c_int, c_int, c_float, c_int, vp, vp, vp,
-                                           sz, vp, vp, c_int, vp]
-    L.dmm_match_train_backward.restype = c_int
-    L.dmm_match_train_backward_det_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, c_int]
-    L.dmm_match_train_backward_det_workspace_bytes.restype = sz
-    L.dmm_match_train_backward_det.argtypes = L.dmm_match_train_backward.argtypes
-    L.dmm_match_train_backward_det.restype = c_int
-    for f in ("dmm_match_forward_packed", "dmm_proposal_boxes_f32", "dmm_nms_slots_f32", "dmm_paste_kept_f32",
-              "dmm_step_select_i32", "dmm_step_advance", "dmm_commit_masks_f32"):
-        getattr(L, f).restype = c_int
-    for f in ("dmm_iou_counts_frames", "dmm_iou_counts_dual_frames", "dmm_mask_mix_frames", "dmm_mask_mix_bwd_frames",
-              "dmm_iou_counts", "dmm_iou_counts_dual", "dmm_feature_normalize_f32", "dmm_cosine_f32", "dmm_relax_match_f32", "dmm_relax_solve_f32",
-              "dmm_mask_mix", "dmm_match_forward", "dmm_match_forward_ws", "dmm_relax_match_bwd_f32", "dmm_roialign4_mean_fwd",
-              "dmm_roialign4_mean_bwd", "dmm_mask_mix_bwd", "dmm_paste_masks_f32", "dmm_nms_f32", "dmm_pack_masks",
-              "dmm_mask_boxes_f32", "dmm_merge_labels_f32", "dmm_ragged_pad"):
-        getattr(L, f).restype = c_int
+    for name, sig in _DECLS.items():
+        if not hasattr(L, name):
+            raise DmmError(f"{LIB_PATH} does not export {name}")
+        fn = getattr(L, name)
+        (fn.restype, fn.argtypes) = sig
     if L.dmm_abi_version() != 2:
         raise DmmError("libdmm_match.so ABI version mismatch")
     # libdmm_match.so needs libhipblaslt.so.1 / libamdhip64.so.7 by SONAME; torch (imported above) has already mapped its
@@ -281,16 +138,21 @@ def check(rc: int, what: str):
     if rc != DMM_OK:
         L = load()
         msg = L.dmm_status_string(rc).decode()
-        extra = f" (hipError {L.dmm_last_hip_error()})" if rc == 3 else ""
+        extra = f" (hipError {L.dmm_last_hip_error()})" if rc == DMM_ERR_LAUNCH else ""
         raise DmmError(f"{what}: {msg}{extra}")
 
 
-# include/dmm_match.h (0): dispatch options, set through the ABI (the library reads no environment variable)
-OPTIONS = {name: k for k, name in enumerate((
-    "COST_KERNEL", "COST_TINY_FRAMES", "SOLVER_KERNEL", "FORCE_WIDE", "COSINE_KERNEL", "COST_WGS", "COST_SMALL_WGS",
-    "COST_TL_WGS", "COST_XCD", "MIX_XCD", "MIX_WGS", "MIX_STEPQ", "MIX_ALIGN", "MIX_NT", "SOLVER_HELPER_MAX", "NMS_WAVE",
-    "COS_ROWS_MIN_N", "GEMM_TUNE", "PACK_VARIANT", "SMALL_FUSED", "MIX_SHARED", "MIX_SHARED_STEPS", "FEAT_BWD_FRAME",
-    "MIX_SHARED_LOCKSTEP"))}
+def call(name: str, device, *args, allow=()):
+    """``load().<name>(*args)`` under ``device_guard(device)`` (no guard for ``device=None``), checked: a status other than
+    DMM_OK raises -- unless ``allow`` lists it (an "outside the envelope" answer the caller handles).  Returns the status."""
+    if device is None:
+        rc = getattr(load(), name)(*args)
+    else:
+        with device_guard(device):
+            rc = getattr(load(), name)(*args)
+    if rc != DMM_OK and rc not in allow:
+        check(rc, name)
+    return rc
 
 
 def set_option(name: str, value: int):

@@ -78,9 +78,8 @@ class SafeGraph:
     def _finish(self):
         n_set, n_cpy, left = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         raw = self.graph.raw_cuda_graph()
-        rc = _lib.load().dmm_graph_nodes_to_kernels(ctypes.c_void_p(int(raw)), 3, ctypes.byref(n_set), ctypes.byref(n_cpy),
-                                                     ctypes.byref(left))
-        _lib.check(rc, "dmm_graph_nodes_to_kernels")
+        _lib.call("dmm_graph_nodes_to_kernels", None, ctypes.c_void_p(int(raw)), 3, ctypes.byref(n_set), ctypes.byref(n_cpy),
+                  ctypes.byref(left))
         self.rewritten, self.left = (n_set.value, n_cpy.value), left.value
         self.graph.instantiate()
 

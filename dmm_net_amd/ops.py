@@ -125,11 +125,9 @@ def iou_counts(masks_p: torch.Tensor, masks_t: torch.Tensor, n_valid=None, m_val
         inter = torch.empty((B, M, N), dtype=torch.int32, device=dev)
         ap = torch.empty((B, N), dtype=torch.int32, device=dev)
         at = torch.empty((B, M), dtype=torch.int32, device=dev)
-        with _lib.device_guard(dev):
-            rc = _lib.load().dmm_iou_counts_frames(_ptr(fp.table), _ptr(masks_t), _DT[fp.dtype], B, N, M, H * W,
-                                                   fp.plane_stride, st_b, st_m, _ptr(n_valid), _ptr(m_valid),
-                                                   _ptr(inter), _ptr(ap), _ptr(at), _stream(masks_t))
-        _lib.check(rc, "dmm_iou_counts_frames")
+        _lib.call("dmm_iou_counts_frames", dev, _ptr(fp.table), _ptr(masks_t), _DT[fp.dtype], B, N, M, H * W,
+                  fp.plane_stride, st_b, st_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
+                  _stream(masks_t))
         return inter, ap, at
     _need_gpu(masks_p, masks_t)
     assert masks_p.dtype == masks_t.dtype and masks_p.dtype in _DT
@@ -142,11 +140,8 @@ def iou_counts(masks_p: torch.Tensor, masks_t: torch.Tensor, n_valid=None, m_val
     inter = torch.empty((B, M, N), dtype=torch.int32, device=dev)
     ap = torch.empty((B, N), dtype=torch.int32, device=dev)
     at = torch.empty((B, M), dtype=torch.int32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().dmm_iou_counts(_ptr(masks_p), _ptr(masks_t), _DT[masks_p.dtype], B, N, M, H * W, sp_b, sp_n,
-                                        st_b, st_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
-                                        _stream(masks_p))
-    _lib.check(rc, "dmm_iou_counts")
+    _lib.call("dmm_iou_counts", dev, _ptr(masks_p), _ptr(masks_t), _DT[masks_p.dtype], B, N, M, H * W, sp_b, sp_n, st_b,
+              st_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), _stream(masks_p))
     return inter, ap, at
 
 
@@ -181,10 +176,8 @@ def ragged_pad(blocks, P_max: int, counts: torch.Tensor, table: Optional[torch.T
         raise ValueError("ragged_pad: blocks must share dtype and trailing shape, rows of a multiple of 4 bytes")
     if table is None:
         table = _lib.small_to_device(addrs, torch.int64, first.device)
-    with _lib.device_guard(first.device):
-        rc = _lib.load().dmm_ragged_pad(_ptr(table), _ptr(counts), len(blocks), int(P_max), row_bytes, _ptr(out),
-                                        _stream(first))
-    _lib.check(rc, "dmm_ragged_pad")
+    _lib.call("dmm_ragged_pad", first.device, _ptr(table), _ptr(counts), len(blocks), int(P_max), row_bytes, _ptr(out),
+              _stream(first))
     return out                                        # (the blocks are read in stream order: no keep-alive needed)
 
 
@@ -198,9 +191,8 @@ def pack_masks(masks: torch.Tensor) -> torch.Tensor:
         s_k = H * W
     wd = pack_words(H * W)
     out = torch.empty((B, K, wd), dtype=torch.int64, device=masks.device)
-    with _lib.device_guard(masks.device):
-        rc = _lib.load().dmm_pack_masks(_ptr(masks), _DT[masks.dtype], B * K, H * W, s_k, _ptr(out), wd, _stream(masks))
-    _lib.check(rc, "dmm_pack_masks")
+    _lib.call("dmm_pack_masks", masks.device, _ptr(masks), _DT[masks.dtype], B * K, H * W, s_k, _ptr(out), wd,
+              _stream(masks))
     return out
 
 
@@ -216,11 +208,8 @@ def iou_counts_packed(packed_p: torch.Tensor, packed_t: torch.Tensor, HW: int, n
     inter = torch.empty((B, M, N), dtype=torch.int32, device=dev)
     ap = torch.empty((B, N), dtype=torch.int32, device=dev)
     at = torch.empty((B, M), dtype=torch.int32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().dmm_iou_counts(_ptr(packed_p), _ptr(packed_t), _lib.DTYPE_PACKED1, B, N, M, HW, N * wd, wd,
-                                        M * wd, wd, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
-                                        _stream(packed_p))
-    _lib.check(rc, "dmm_iou_counts (packed)")
+    _lib.call("dmm_iou_counts", dev, _ptr(packed_p), _ptr(packed_t), _lib.DTYPE_PACKED1, B, N, M, HW, N * wd, wd, M * wd,
+              wd, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), _stream(packed_p))
     return inter, ap, at
 
 
@@ -237,12 +226,9 @@ def iou_counts_dual(masks_p: torch.Tensor, masks_t: torch.Tensor, masks_t2: torc
         i32 = dict(dtype=torch.int32, device=fp.device)
         inter, inter2 = torch.empty((B, M, N), **i32), torch.empty((B, M, N), **i32)
         ap, at, at2 = torch.empty((B, N), **i32), torch.empty((B, M), **i32), torch.empty((B, M), **i32)
-        with _lib.device_guard(fp.device):
-            rc = _lib.load().dmm_iou_counts_dual_frames(_ptr(fp.table), _ptr(masks_t), _ptr(masks_t2), _DT[fp.dtype], B,
-                                                        N, M, H * W, fp.plane_stride, st_b, st_m, st2_b, st2_m,
-                                                        _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
-                                                        _ptr(inter2), _ptr(at2), _stream(masks_t))
-        _lib.check(rc, "dmm_iou_counts_dual_frames")
+        _lib.call("dmm_iou_counts_dual_frames", fp.device, _ptr(fp.table), _ptr(masks_t), _ptr(masks_t2), _DT[fp.dtype],
+                  B, N, M, H * W, fp.plane_stride, st_b, st_m, st2_b, st2_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter),
+                  _ptr(ap), _ptr(at), _ptr(inter2), _ptr(at2), _stream(masks_t))
         return (inter, ap, at), (inter2, at2)
     _need_gpu(masks_p, masks_t, masks_t2)
     assert masks_p.dtype == masks_t.dtype == masks_t2.dtype and masks_p.dtype in _DT
@@ -256,11 +242,9 @@ def iou_counts_dual(masks_p: torch.Tensor, masks_t: torch.Tensor, masks_t2: torc
     i32 = dict(dtype=torch.int32, device=dev)
     inter, inter2 = torch.empty((B, M, N), **i32), torch.empty((B, M, N), **i32)
     ap, at, at2 = torch.empty((B, N), **i32), torch.empty((B, M), **i32), torch.empty((B, M), **i32)
-    with _lib.device_guard(dev):
-        rc = _lib.load().dmm_iou_counts_dual(_ptr(masks_p), _ptr(masks_t), _ptr(masks_t2), _DT[masks_p.dtype], B, N, M,
-                                             H * W, sp_b, sp_n, st_b, st_m, st2_b, st2_m, _ptr(n_valid), _ptr(m_valid),
-                                             _ptr(inter), _ptr(ap), _ptr(at), _ptr(inter2), _ptr(at2), _stream(masks_p))
-    _lib.check(rc, "dmm_iou_counts_dual")
+    _lib.call("dmm_iou_counts_dual", dev, _ptr(masks_p), _ptr(masks_t), _ptr(masks_t2), _DT[masks_p.dtype], B, N, M, H * W,
+              sp_b, sp_n, st_b, st_m, st2_b, st2_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
+              _ptr(inter2), _ptr(at2), _stream(masks_p))
     return (inter, ap, at), (inter2, at2)
 
 
@@ -272,9 +256,7 @@ def feature_normalize(x: torch.Tensor, want_norms: bool = False):
     rows = x.numel() // max(D, 1)
     out = torch.empty_like(x)
     norms = torch.empty(x.shape[:-1], dtype=torch.float32, device=x.device) if want_norms else None
-    with _lib.device_guard(x.device):
-        rc = _lib.load().dmm_feature_normalize_f32(_ptr(x), rows, D, _ptr(out), _ptr(norms), _stream(x))
-    _lib.check(rc, "dmm_feature_normalize_f32")
+    _lib.call("dmm_feature_normalize_f32", x.device, _ptr(x), rows, D, _ptr(out), _ptr(norms), _stream(x))
     return (out, norms) if want_norms else out
 
 
@@ -285,10 +267,8 @@ def cosine(featn_t: torch.Tensor, featn_p: torch.Tensor, n_valid=None, m_valid=N
     B, M, D = featn_t.shape
     N = featn_p.shape[1]
     out = torch.empty((B, M, N), dtype=torch.float32, device=featn_t.device)
-    with _lib.device_guard(featn_t.device):
-        rc = _lib.load().dmm_cosine_f32(_ptr(featn_t), _ptr(featn_p), B, N, M, D, _ptr(n_valid), _ptr(m_valid),
-                                        _ptr(out), _stream(featn_t))
-    _lib.check(rc, "dmm_cosine_f32")
+    _lib.call("dmm_cosine_f32", featn_t.device, _ptr(featn_t), _ptr(featn_p), B, N, M, D, _ptr(n_valid), _ptr(m_valid),
+              _ptr(out), _stream(featn_t))
     return out
 
 
@@ -301,11 +281,10 @@ def cosine_features(feat_t: torch.Tensor, feat_p: torch.Tensor) -> torch.Tensor:
     B, M, D = feat_t.shape
     N = feat_p.shape[1]
     out = torch.empty((B, M, N), dtype=torch.float32, device=feat_t.device)
-    with _lib.device_guard(feat_t.device):
-        rc = _lib.load().dmm_cosine_features_f32(_ptr(feat_t), _ptr(feat_p), B, N, M, D, _ptr(out), _stream(feat_t))
-    if rc == 2:                                               # DMM_ERR_UNSUPPORTED: outside the fused kernel's envelope
+    rc = _lib.call("dmm_cosine_features_f32", feat_t.device, _ptr(feat_t), _ptr(feat_p), B, N, M, D, _ptr(out),
+                   _stream(feat_t), allow=(_lib.DMM_ERR_UNSUPPORTED,))
+    if rc == _lib.DMM_ERR_UNSUPPORTED:                        # outside the fused kernel's envelope
         return cosine(feature_normalize(feat_t), feature_normalize(feat_p))
-    _lib.check(rc, "dmm_cosine_features_f32")
     return out
 
 
@@ -327,20 +306,16 @@ def relax_match(cos, inter, area_p, area_t, score_p, *, score_weight, max_iter, 
                X=torch.empty((B, M, Pp), **f32) if want_x else None)
     cos, score_p = cos.contiguous().float(), score_p.contiguous().float()
     assert state in ("f32", "f16")
-    L = _lib.load()
-    fn = L.dmm_relax_match_f32 if state == "f32" else L.dmm_relax_match_f16s
     args = (_ptr(cos), _ptr(inter), _ptr(area_p), _ptr(area_t), _ptr(score_p), B, N, M, _ptr(n_valid), _ptr(m_valid),
             float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(out["sim"]),
             _ptr(out["R"]), _ptr(out["Rb"]), _ptr(out["match_score"]), _ptr(out["det_score"]), _ptr(out["iters"]),
             _ptr(out["X"]))
-    with _lib.device_guard(dev):
-        if state == "f32" and (M > _lib.MAX_TEMPLATES or Pp > _lib.MAX_PROPOSALS):
-            scratch = torch.empty((int(L.dmm_relax_any_scratch_bytes(B, N, M)),), dtype=torch.uint8, device=dev)
-            rc = L.dmm_relax_match_any_f32(*args, _ptr(scratch), scratch.numel(), _stream(cos))
-            scratch.record_stream(torch.cuda.current_stream(dev))
-        else:
-            rc = fn(*args, _stream(cos))
-    _lib.check(rc, "dmm_relax_match_" + ("f32" if state == "f32" else "f16s"))
+    if state == "f32" and (M > _lib.MAX_TEMPLATES or Pp > _lib.MAX_PROPOSALS):
+        scratch = torch.empty((int(_lib.load().dmm_relax_any_scratch_bytes(B, N, M)),), dtype=torch.uint8, device=dev)
+        _lib.call("dmm_relax_match_any_f32", dev, *args, _ptr(scratch), scratch.numel(), _stream(cos))
+        scratch.record_stream(torch.cuda.current_stream(dev))
+    else:
+        _lib.call("dmm_relax_match_f32" if state == "f32" else "dmm_relax_match_f16s", dev, *args, _stream(cos))
     return out
 
 
@@ -357,11 +332,9 @@ def relax_match_bwd(sim, score_p, dRb, d_match_score, d_det_score, *, max_iter, 
     nbytes = int(L.dmm_relax_bwd_workspace_bytes(B, N, M, int(max_iter), int(proj_iter)))
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
     out = torch.empty((B, M, N), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = L.dmm_relax_match_bwd_f32(_ptr(sim), _ptr(score_p), B, N, M, _ptr(n_valid), _ptr(m_valid), int(max_iter),
-                                       int(proj_iter), float(lr), int(is_test), _ptr(dRb), _ptr(d_match_score),
-                                       _ptr(d_det_score), _ptr(out), _ptr(ws), ws.numel(), _stream(sim))
-    _lib.check(rc, "dmm_relax_match_bwd_f32")
+    _lib.call("dmm_relax_match_bwd_f32", dev, _ptr(sim), _ptr(score_p), B, N, M, _ptr(n_valid), _ptr(m_valid),
+              int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(dRb), _ptr(d_match_score), _ptr(d_det_score),
+              _ptr(out), _ptr(ws), ws.numel(), _stream(sim))
     return out
 
 
@@ -381,12 +354,9 @@ def feature_sim_bwd(dsim, cos, gt, d_loss, score_weight, feat_t, feat_p, featn_t
         gt = d_loss = cos_arg = None
     else:
         cos_arg = cos
-    with _lib.device_guard(dsim.device):
-        rc = _lib.load().dmm_feature_sim_bwd_f32(_ptr(dsim), _ptr(cos_arg), _ptr(gt), _ptr(d_loss), float(score_weight),
-                                                 _ptr(feat_t), _ptr(feat_p), _ptr(featn_t), _ptr(featn_p), _ptr(norm_t),
-                                                 _ptr(norm_p), B, N, M, D, _ptr(n_valid), _ptr(m_valid), _ptr(g_t),
-                                                 _ptr(g_p), _stream(dsim))
-    _lib.check(rc, "dmm_feature_sim_bwd_f32")
+    _lib.call("dmm_feature_sim_bwd_f32", dsim.device, _ptr(dsim), _ptr(cos_arg), _ptr(gt), _ptr(d_loss),
+              float(score_weight), _ptr(feat_t), _ptr(feat_p), _ptr(featn_t), _ptr(featn_p), _ptr(norm_t), _ptr(norm_p), B,
+              N, M, D, _ptr(n_valid), _ptr(m_valid), _ptr(g_t), _ptr(g_p), _stream(dsim))
     return g_t, g_p
 
 
@@ -427,11 +397,8 @@ def relax_solve(C: torch.Tensor, max_iter: int, proj_iter: int, lr: float, rows_
     R = torch.empty_like(C)
     cost = torch.zeros((B, max_iter + 1), dtype=torch.float32, device=C.device)
     iters = torch.empty((B,), dtype=torch.int32, device=C.device)
-    with _lib.device_guard(C.device):
-        rc = _lib.load().dmm_relax_solve_f32(_ptr(C), B, n, m, _ptr(rows_valid), _ptr(cols_valid), int(max_iter),
-                                             int(proj_iter), float(lr), _ptr(X), _ptr(R), _ptr(cost), _ptr(iters),
-                                             _stream(C))
-    _lib.check(rc, "dmm_relax_solve_f32")
+    _lib.call("dmm_relax_solve_f32", C.device, _ptr(C), B, n, m, _ptr(rows_valid), _ptr(cols_valid), int(max_iter),
+              int(proj_iter), float(lr), _ptr(X), _ptr(R), _ptr(cost), _ptr(iters), _stream(C))
     return dict(X=X, R=R, cost=cost, iters=iters)
 
 
@@ -451,12 +418,9 @@ def mask_mix(Rb: torch.Tensor, masks_p: torch.Tensor, n_valid=None, m_valid=None
         if out_dtype not in (None, torch.float32):
             raise ValueError("mask_mix on per-frame plane tables writes fp32 (dmm_mask_mix_frames)")
         out = torch.empty((B, M, H, W), dtype=torch.float32, device=Rb.device)
-        with _lib.device_guard(Rb.device):
-            L = _lib.load()
-            rc = (L.dmm_mask_mix_shared_frames if shared else L.dmm_mask_mix_frames)(_ptr(Rb), _ptr(fp.table), _DT[fp.dtype], B, N, M, Pp, H * W,
-                                                 fp.plane_stride, _ptr(n_valid), _ptr(m_valid), _ptr(out), M * H * W,
-                                                 H * W, _stream(Rb))
-        _lib.check(rc, "dmm_mask_mix_frames")
+        _lib.call("dmm_mask_mix_shared_frames" if shared else "dmm_mask_mix_frames", Rb.device, _ptr(Rb), _ptr(fp.table),
+                  _DT[fp.dtype], B, N, M, Pp, H * W, fp.plane_stride, _ptr(n_valid), _ptr(m_valid), _ptr(out), M * H * W,
+                  H * W, _stream(Rb))
         return out
     _need_gpu(Rb, masks_p)
     masks_p, sp_b, sp_n = _planes(masks_p)
@@ -465,12 +429,9 @@ def mask_mix(Rb: torch.Tensor, masks_p: torch.Tensor, n_valid=None, m_valid=None
     Rb = Rb.contiguous().float()
     out_dtype = out_dtype or torch.float32
     out = torch.empty((B, M, H, W), dtype=out_dtype, device=Rb.device)
-    with _lib.device_guard(Rb.device):
-        L = _lib.load()
-        rc = (L.dmm_mask_mix_shared_to if shared else L.dmm_mask_mix_to)(_ptr(Rb), _ptr(masks_p), _DT[masks_p.dtype], B, N, M, Pp, H * W, sp_b, sp_n,
-                                         _ptr(n_valid), _ptr(m_valid), _ptr(out), _DT[out_dtype], M * H * W, H * W,
-                                         _stream(Rb))
-    _lib.check(rc, "dmm_mask_mix_to")
+    _lib.call("dmm_mask_mix_shared_to" if shared else "dmm_mask_mix_to", Rb.device, _ptr(Rb), _ptr(masks_p),
+              _DT[masks_p.dtype], B, N, M, Pp, H * W, sp_b, sp_n, _ptr(n_valid), _ptr(m_valid), _ptr(out), _DT[out_dtype],
+              M * H * W, H * W, _stream(Rb))
     return out
 
 
@@ -489,18 +450,13 @@ def mask_mix_bwd(Rb: torch.Tensor, masks_p: torch.Tensor, dout: torch.Tensor, n_
             n_valid = fp.n_valid()
         dout = dout.contiguous().float().view(B, M, H * W)
         dRb = torch.empty((B, M, Pp), dtype=torch.float32, device=Rb.device)
-        L = _lib.load()
-        with _lib.device_guard(Rb.device):
-            if det:
-                ws = _det_mix_ws(L, B, N, M, Pp, H * W, Rb.device)
-                rc = L.dmm_mask_mix_bwd_frames_det(_ptr(Rb), _ptr(fp.table), _DT[fp.dtype], _ptr(dout), B, N, M, Pp, H * W,
-                                                   fp.plane_stride, _ptr(n_valid), _ptr(m_valid), _ptr(dRb), _ptr(ws),
-                                                   ws.numel(), _stream(Rb))
-            else:
-                rc = L.dmm_mask_mix_bwd_frames(_ptr(Rb), _ptr(fp.table), _DT[fp.dtype], _ptr(dout), B, N, M, Pp,
-                                               H * W, fp.plane_stride, _ptr(n_valid), _ptr(m_valid), _ptr(dRb),
-                                               _stream(Rb))
-        _lib.check(rc, "dmm_mask_mix_bwd_frames")
+        args = (_ptr(Rb), _ptr(fp.table), _DT[fp.dtype], _ptr(dout), B, N, M, Pp, H * W, fp.plane_stride, _ptr(n_valid),
+                _ptr(m_valid), _ptr(dRb))
+        if det:
+            ws = _det_mix_ws(B, N, M, Pp, H * W, Rb.device)
+            _lib.call("dmm_mask_mix_bwd_frames_det", Rb.device, *args, _ptr(ws), ws.numel(), _stream(Rb))
+        else:
+            _lib.call("dmm_mask_mix_bwd_frames", Rb.device, *args, _stream(Rb))
         return dRb
     _need_gpu(Rb, masks_p, dout)
     masks_p, sp_b, sp_n = _planes(masks_p)
@@ -509,22 +465,19 @@ def mask_mix_bwd(Rb: torch.Tensor, masks_p: torch.Tensor, dout: torch.Tensor, n_
     Rb = Rb.contiguous().float()
     dout = dout.contiguous().float().view(B, M, H * W)
     dRb = torch.empty((B, M, Pp), dtype=torch.float32, device=Rb.device)
-    L = _lib.load()
-    with _lib.device_guard(Rb.device):
-        if det:
-            ws = _det_mix_ws(L, B, N, M, Pp, H * W, Rb.device)
-            rc = L.dmm_mask_mix_bwd_det(_ptr(Rb), _ptr(masks_p), _DT[masks_p.dtype], _ptr(dout), B, N, M, Pp, H * W, sp_b,
-                                        sp_n, _ptr(n_valid), _ptr(m_valid), _ptr(dRb), _ptr(ws), ws.numel(), _stream(Rb))
-        else:
-            rc = L.dmm_mask_mix_bwd(_ptr(Rb), _ptr(masks_p), _DT[masks_p.dtype], _ptr(dout), B, N, M, Pp, H * W,
-                                    sp_b, sp_n, _ptr(n_valid), _ptr(m_valid), _ptr(dRb), _stream(Rb))
-    _lib.check(rc, "dmm_mask_mix_bwd")
+    args = (_ptr(Rb), _ptr(masks_p), _DT[masks_p.dtype], _ptr(dout), B, N, M, Pp, H * W, sp_b, sp_n, _ptr(n_valid),
+            _ptr(m_valid), _ptr(dRb))
+    if det:
+        ws = _det_mix_ws(B, N, M, Pp, H * W, Rb.device)
+        _lib.call("dmm_mask_mix_bwd_det", Rb.device, *args, _ptr(ws), ws.numel(), _stream(Rb))
+    else:
+        _lib.call("dmm_mask_mix_bwd", Rb.device, *args, _stream(Rb))
     return dRb
 
 
-def _det_mix_ws(L, B, N, M, Pp, HW, device) -> torch.Tensor:
+def _det_mix_ws(B, N, M, Pp, HW, device) -> torch.Tensor:
     """The slab of the deterministic mix backward (zeroed by the entry itself)."""
-    n = int(L.dmm_mask_mix_bwd_det_workspace_bytes(B, N, M, Pp, HW))
+    n = int(_lib.load().dmm_mask_mix_bwd_det_workspace_bytes(B, N, M, Pp, HW))
     return torch.empty((max(n, 16),), dtype=torch.uint8, device=device)
 
 
@@ -580,13 +533,10 @@ def match_forward(masks_p, masks_t, feat_p, feat_t, score_p, *, score_weight, ma
         tables = {"sim": torch.empty((B, M, N), **f32), "R": torch.empty((B, M, Pp), **f32),
                   "Rb": torch.empty((B, M, Pp), **f32)}
     tp = (lambda k: _ptr(tables[k])) if tables else (lambda k: None)
-    with _lib.device_guard(dev):
-        rc = L.dmm_match_forward_ws(_ptr(masks_p), _ptr(masks_t), _DT[masks_p.dtype], _ptr(feat_p), _ptr(feat_t),
-                                    _ptr(score_p), B, N, M, H * W, D, sp_b, sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid),
-                                    float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(full),
-                                    _ptr(ms), _ptr(ds), tp("sim"), tp("R"), tp("Rb"), _ptr(iters), _ptr(ws), ws.numel(),
-                                    None if note is None else ctypes.byref(note), stream)
-    _lib.check(rc, "dmm_match_forward_ws")
+    _lib.call("dmm_match_forward_ws", dev, _ptr(masks_p), _ptr(masks_t), _DT[masks_p.dtype], _ptr(feat_p), _ptr(feat_t),
+              _ptr(score_p), B, N, M, H * W, D, sp_b, sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight),
+              int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(full), _ptr(ms), _ptr(ds), tp("sim"), tp("R"),
+              tp("Rb"), _ptr(iters), _ptr(ws), ws.numel(), None if note is None else ctypes.byref(note), stream)
     if return_tables:
         return full, ms, ds, iters, tables
     return full, ms, ds, iters
@@ -630,14 +580,11 @@ def match_forward_frame(proposed_mask, mask_last, feat_p, feat_t, score_p, *, sc
     full = torch.empty((M, H, W), dtype=torch.float32, device=dev)
     ms = torch.empty((M,), dtype=torch.float32, device=dev)
     ds = torch.empty((M,), dtype=torch.float32, device=dev)
-    with _lib.device_guard(dev):
-        rc = L.dmm_match_forward_ws(pm.data_ptr(), tm.data_ptr(), _DT[pm.dtype], feat_p.data_ptr(), feat_t.data_ptr(),
-                                    score_p.data_ptr(), 1, N, M, H * W, D, N * pm.stride(0) if N else 0, pm.stride(0),
-                                    M * tm.stride(0) if M else 0, tm.stride(0), None, None, score_weight, max_iter,
-                                    proj_iter, lr, is_test, full.data_ptr(), ms.data_ptr(), ds.data_ptr(), None, None, None,
-                                    None, ws.data_ptr(), ws.numel(), None if note is None else ctypes.byref(note), stream)
-    if rc:
-        _lib.check(rc, "dmm_match_forward_ws")
+    _lib.call("dmm_match_forward_ws", dev, pm.data_ptr(), tm.data_ptr(), _DT[pm.dtype], feat_p.data_ptr(),
+              feat_t.data_ptr(), score_p.data_ptr(), 1, N, M, H * W, D, N * pm.stride(0) if N else 0, pm.stride(0),
+              M * tm.stride(0) if M else 0, tm.stride(0), None, None, score_weight, max_iter, proj_iter, lr, is_test,
+              full.data_ptr(), ms.data_ptr(), ds.data_ptr(), None, None, None, None, ws.data_ptr(), ws.numel(),
+              None if note is None else ctypes.byref(note), stream)
     return full, ms, ds
 
 
@@ -725,18 +672,15 @@ def match_train_forward(masks_p, masks_t, targets, feat_p, feat_t, score_p, n_va
     saved = torch.empty((tape_off // 4 + tape_bytes // 4,), **f32)
     sp = saved.data_ptr()
     taped = ctypes.c_int(0)
-    with _lib.device_guard(dev):
-        rc = L.dmm_match_train_forward(p_ptr, masks_t.data_ptr(), g_ptr, _DT[dt], feat_p.data_ptr(), feat_t.data_ptr(),
-                                       score_p.data_ptr(), B, N, M, H * W, D, sp_b, sp_n, st_b, st_m, sg_b, sg_m,
-                                       _ptr(n_valid), _ptr(m_valid), score_weight, max_iter, proj_iter, lr, is_test,
-                                       full.data_ptr(), ms.data_ptr(), ds.data_ptr(), _ptr(loss), iters.data_ptr(), sp,
-                                       sp + 4 * n_cs, sp + 8 * n_cs, (sp + 8 * n_cs + 4 * n_rb) if targets is not None else None,
-                                       ws.data_ptr(), ws.numel(), (sp + tape_off) if tape_bytes else None, tape_bytes,
-                                       ctypes.byref(taped), stream)
-    if rc == 2:                                               # DMM_ERR_UNSUPPORTED: nothing was launched
+    rc = _lib.call("dmm_match_train_forward", dev, p_ptr, masks_t.data_ptr(), g_ptr, _DT[dt], feat_p.data_ptr(),
+                   feat_t.data_ptr(), score_p.data_ptr(), B, N, M, H * W, D, sp_b, sp_n, st_b, st_m, sg_b, sg_m,
+                   _ptr(n_valid), _ptr(m_valid), score_weight, max_iter, proj_iter, lr, is_test, full.data_ptr(),
+                   ms.data_ptr(), ds.data_ptr(), _ptr(loss), iters.data_ptr(), sp, sp + 4 * n_cs, sp + 8 * n_cs,
+                   (sp + 8 * n_cs + 4 * n_rb) if targets is not None else None, ws.data_ptr(), ws.numel(),
+                   (sp + tape_off) if tape_bytes else None, tape_bytes, ctypes.byref(taped), stream,
+                   allow=(_lib.DMM_ERR_UNSUPPORTED,))
+    if rc == _lib.DMM_ERR_UNSUPPORTED:                        # nothing was launched
         return None
-    if rc:
-        _lib.check(rc, "dmm_match_train_forward")
     return full, ms, ds, loss, iters, saved, int(taped.value)
 
 
@@ -799,16 +743,12 @@ def match_train_backward(masks_p, feat_p, feat_t, score_p, saved, has_loss, d_fu
     sp = saved.data_ptr()
     tape_off, tape_bytes = _train_tape_layout(L, B, N, M, max_iter, proj_iter)
     walk = bool(taped) and iters is not None and tape_bytes > 0 and saved.numel() * 4 >= tape_off + tape_bytes
-    with _lib.device_guard(dev):
-        rc = (L.dmm_match_train_backward_det if det else L.dmm_match_train_backward)(p_ptr, _DT[dt], feat_p.data_ptr(), feat_t.data_ptr(), score_p.data_ptr(),
-                                        sp if use_loss else None, sp + 4 * n_cs, sp + 8 * n_cs,
-                                        (sp + 8 * n_cs + 4 * n_rb) if use_loss else None, _ptr(d_full), _ptr(d_ms),
-                                        _ptr(d_ds), _ptr(d_loss) if use_loss else None, B, N, M, H * W, D, sp_b, sp_n,
-                                        _ptr(n_valid), _ptr(m_valid), score_weight, max_iter, proj_iter, lr, is_test,
-                                        g_t.data_ptr(), g_p.data_ptr(), ws.data_ptr(), ws.numel(),
-                                        (sp + tape_off) if walk else None, _ptr(iters) if walk else None, int(walk), stream)
-    if rc:
-        _lib.check(rc, "dmm_match_train_backward")
+    _lib.call("dmm_match_train_backward_det" if det else "dmm_match_train_backward", dev, p_ptr, _DT[dt], feat_p.data_ptr(),
+              feat_t.data_ptr(), score_p.data_ptr(), sp if use_loss else None, sp + 4 * n_cs, sp + 8 * n_cs,
+              (sp + 8 * n_cs + 4 * n_rb) if use_loss else None, _ptr(d_full), _ptr(d_ms), _ptr(d_ds),
+              _ptr(d_loss) if use_loss else None, B, N, M, H * W, D, sp_b, sp_n, _ptr(n_valid), _ptr(m_valid), score_weight,
+              max_iter, proj_iter, lr, is_test, g_t.data_ptr(), g_p.data_ptr(), ws.data_ptr(), ws.numel(),
+              (sp + tape_off) if walk else None, _ptr(iters) if walk else None, int(walk), stream)
     return g_t, g_p
 
 
@@ -843,13 +783,10 @@ def match_forward_packed(masks_p, packed_p, masks_t, feat_p, feat_t, score_p, n_
     full, ms, ds, iters = out
     assert full.is_contiguous() and full.shape == (B, M, H, W) and full.dtype == torch.float32
     wd = packed_p.shape[2]
-    with _lib.device_guard(dev):
-        rc = L.dmm_match_forward_packed(_ptr(masks_p), _ptr(packed_p), _ptr(masks_t), _DT[masks_p.dtype], _ptr(feat_p),
-                                        _ptr(feat_t), _ptr(score_p), B, N, M, H * W, D, sp_b, sp_n, N * wd, wd, st_b, st_m,
-                                        _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
-                                        float(lr), int(is_test), _ptr(full), _ptr(ms), _ptr(ds), None, None, None,
-                                        _ptr(iters), _ptr(workspace), workspace.numel(), _stream(masks_p))
-    _lib.check(rc, "dmm_match_forward_packed")
+    _lib.call("dmm_match_forward_packed", dev, _ptr(masks_p), _ptr(packed_p), _ptr(masks_t), _DT[masks_p.dtype],
+              _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, H * W, D, sp_b, sp_n, N * wd, wd, st_b, st_m, _ptr(n_valid),
+              _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(full),
+              _ptr(ms), _ptr(ds), None, None, None, _ptr(iters), _ptr(workspace), workspace.numel(), _stream(masks_p))
     return out
 
 
@@ -865,14 +802,11 @@ def match_solve_packed(packed_p, packed_t, feat_p, feat_t, score_p, n_valid, m_v
     assert feat_p.is_contiguous() and feat_t.is_contiguous() and score_p.is_contiguous()
     Rb, ms, ds, iters = out
     assert Rb.is_contiguous() and Rb.shape == (B, M, padded_width(N, M))
-    L = _lib.load()
-    assert workspace.numel() >= int(L.dmm_workspace_bytes(B, N, M, D))
-    with _lib.device_guard(packed_p.device):
-        rc = L.dmm_match_solve_packed(_ptr(packed_p), _ptr(packed_t), _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M,
-                                      int(HW), D, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter),
-                                      int(proj_iter), float(lr), int(is_test), _ptr(Rb), _ptr(ms), _ptr(ds), None, None,
-                                      _ptr(iters), _ptr(workspace), workspace.numel(), _stream(packed_p))
-    _lib.check(rc, "dmm_match_solve_packed")
+    assert workspace.numel() >= int(_lib.load().dmm_workspace_bytes(B, N, M, D))
+    _lib.call("dmm_match_solve_packed", packed_p.device, _ptr(packed_p), _ptr(packed_t), _ptr(feat_p), _ptr(feat_t),
+              _ptr(score_p), B, N, M, int(HW), D, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter),
+              int(proj_iter), float(lr), int(is_test), _ptr(Rb), _ptr(ms), _ptr(ds), None, None, _ptr(iters),
+              _ptr(workspace), workspace.numel(), _stream(packed_p))
     return out
 
 
@@ -906,6 +840,7 @@ class ForwardPlan:
         # Its <= 128 VGPRs let it share a SIMD with the streaming kernels, so wide tables can take the 2-lane schedule.
         assert solver_state in ("f32", "f16")
         self.solver_state = solver_state
+        self.solver_entry = "dmm_relax_match_f32" if solver_state == "f32" else "dmm_relax_match_f16s"
         # default: two lanes for large batches whose solver fits beside the streaming kernels (one wave per frame, exact
         # row count: M <= 16, Pp <= 64); the multi-wave solvers of wide tables hold up to 256 VGPRs per wave and only
         # serialise with them (config 5, fp32 state: 2.26 ms single stream vs 2.37 ms two lanes per 256 frames)
@@ -1002,7 +937,7 @@ class ForwardPlan:
                 else "HIP graph replay (feature similarity + IoU counts [one launch at <= 8 dense frames] -> solver -> mix, one chain)"
         return "single stream"
 
-    def _launch_forked(self, L, masks_p, masks_t, feat_p, feat_t, score_p, dt, strides, n_valid, m_valid, cfg):
+    def _launch_forked(self, masks_p, masks_t, feat_p, feat_t, score_p, dt, strides, n_valid, m_valid, cfg):
         """Granular launches, the form that is captured into the HIP graph (``graph_fork``: feature branch on the side
         stream, fork / join by stream waits)."""
         B, N, M, D, Pp, HW = self.B, self.N, self.M, self.D, self.Pp, self.H * self.W
@@ -1011,34 +946,29 @@ class ForwardPlan:
         main = torch.cuda.current_stream(self.device)
         if not self.graph_fork:
             # one chain: the fused C call (its feature-similarity launch also clears the count tables: no memset node)
-            _lib.check(L.dmm_match_forward_ws(
-                _ptr(masks_p), _ptr(masks_t), dt, _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, HW, D, sp_b, sp_n,
-                st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter), float(lr),
-                int(is_test), _ptr(self.full_outmask), _ptr(self.match_score), _ptr(self.det_score), _ptr(self.sim),
-                _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace), self.ws_bytes,
-                ctypes.byref(self._ws_state), main.cuda_stream),
-                "dmm_match_forward_ws (graph capture)")
+            _lib.call("dmm_match_forward_ws", None,
+                      _ptr(masks_p), _ptr(masks_t), dt, _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, HW, D, sp_b,
+                      sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
+                      float(lr), int(is_test), _ptr(self.full_outmask), _ptr(self.match_score), _ptr(self.det_score),
+                      _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace), self.ws_bytes,
+                      ctypes.byref(self._ws_state), main.cuda_stream)
             return
         side = self.side
         inter, ap, at = self._tables(0)
         if self.graph_fork:
             side.wait_stream(main)
         ss, ms = side.cuda_stream, main.cuda_stream
-        rc = self._feature_sim(L, feat_p, feat_t, n_valid, m_valid, ss)
-        rc |= L.dmm_iou_counts(_ptr(masks_p), _ptr(masks_t), dt, B, N, M, HW, sp_b, sp_n, st_b, st_m, _ptr(n_valid),
-                               _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), ms)
+        self._feature_sim(feat_p, feat_t, n_valid, m_valid, ss)
+        _lib.call("dmm_iou_counts", None, _ptr(masks_p), _ptr(masks_t), dt, B, N, M, HW, sp_b, sp_n, st_b, st_m,
+                  _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), ms)
         if self.graph_fork:
             main.wait_stream(side)
-        rc |= self._solver(L)(_ptr(self.cos), _ptr(inter), _ptr(ap), _ptr(at), _ptr(score_p), B, N, M,
-                               _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
-                               float(lr), int(is_test), _ptr(self.sim), _ptr(self.R), _ptr(self.Rb),
-                               _ptr(self.match_score), _ptr(self.det_score), _ptr(self.iters), None, ms)
-        rc |= L.dmm_mask_mix_to(_ptr(self.Rb), _ptr(masks_p), dt, B, N, M, Pp, HW, sp_b, sp_n, _ptr(n_valid),
-                                _ptr(m_valid), _ptr(self.full_outmask), _DT[self.out_dtype], self.so_b, self.so_m, ms)
-        _lib.check(rc, "ForwardPlan.run (forked)")
-
-    def _solver(self, L):
-        return L.dmm_relax_match_f32 if self.solver_state == "f32" else L.dmm_relax_match_f16s
+        _lib.call(self.solver_entry, None, _ptr(self.cos), _ptr(inter), _ptr(ap), _ptr(at), _ptr(score_p), B, N, M,
+                  _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test),
+                  _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.match_score), _ptr(self.det_score),
+                  _ptr(self.iters), None, ms)
+        _lib.call("dmm_mask_mix_to", None, _ptr(self.Rb), _ptr(masks_p), dt, B, N, M, Pp, HW, sp_b, sp_n, _ptr(n_valid),
+                  _ptr(m_valid), _ptr(self.full_outmask), _DT[self.out_dtype], self.so_b, self.so_m, ms)
 
     def _mark(self, name, stream, begin):
         """HIP event on ``stream`` before / after a kernel launch when bench.py asked for kernel timing."""
@@ -1051,19 +981,18 @@ class ForwardPlan:
         else:
             self.kernel_events[name][-1][1] = e
 
-    def _feature_sim(self, L, feat_p, feat_t, n_valid, m_valid, stream) -> int:
+    def _feature_sim(self, feat_p, feat_t, n_valid, m_valid, stream):
         """cos[B,M,N] into self.cos on ``stream``: the fused one-launch kernel for dense batches inside its envelope,
         normalise + normalise + cosine otherwise."""
         B, N, M, D = self.B, self.N, self.M, self.D
         if n_valid is None and m_valid is None:
-            rc = L.dmm_cosine_features_f32(_ptr(feat_t), _ptr(feat_p), B, N, M, D, _ptr(self.cos), stream)
-            if rc != 2:
-                return rc
-        rc = L.dmm_feature_normalize_f32(_ptr(feat_p), B * N, D, _ptr(self.pn), None, stream)
-        rc |= L.dmm_feature_normalize_f32(_ptr(feat_t), B * M, D, _ptr(self.tn), None, stream)
-        rc |= L.dmm_cosine_f32(_ptr(self.tn), _ptr(self.pn), B, N, M, D, _ptr(n_valid), _ptr(m_valid), _ptr(self.cos),
-                               stream)
-        return rc
+            if _lib.call("dmm_cosine_features_f32", None, _ptr(feat_t), _ptr(feat_p), B, N, M, D, _ptr(self.cos), stream,
+                         allow=(_lib.DMM_ERR_UNSUPPORTED,)) == _lib.DMM_OK:
+                return
+        _lib.call("dmm_feature_normalize_f32", None, _ptr(feat_p), B * N, D, _ptr(self.pn), None, stream)
+        _lib.call("dmm_feature_normalize_f32", None, _ptr(feat_t), B * M, D, _ptr(self.tn), None, stream)
+        _lib.call("dmm_cosine_f32", None, _ptr(self.tn), _ptr(self.pn), B, N, M, D, _ptr(n_valid), _ptr(m_valid),
+                  _ptr(self.cos), stream)
 
     def _tables(self, h):
         (b, e) = self.halves[h]
@@ -1082,7 +1011,6 @@ class ForwardPlan:
         assert masks_p.dtype == self.mask_dtype and masks_t.dtype == self.mask_dtype
         assert feat_p.is_contiguous() and feat_t.is_contiguous() and score_p.is_contiguous()
         assert feat_p.dtype == torch.float32 and feat_t.dtype == torch.float32 and score_p.dtype == torch.float32
-        L = _lib.load()
         dt = _DT[self.mask_dtype]
         if self.graph_mode and not torch.cuda.is_current_stream_capturing():
             cfg = (float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test))
@@ -1101,7 +1029,7 @@ class ForwardPlan:
                 with _CAPTURE_LOCK, torch.cuda.device(self.device):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        self._launch_forked(L, masks_p, masks_t, feat_p, feat_t, score_p, dt, (sp_b, sp_n, st_b, st_m),
+                        self._launch_forked(masks_p, masks_t, feat_p, feat_t, score_p, dt, (sp_b, sp_n, st_b, st_m),
                                             n_valid, m_valid, cfg)
                 ws_out = self._ws_state.value                       # what a replay leaves (nothing ran during the capture)
                 self._ws_state.value = ws_in
@@ -1117,32 +1045,29 @@ class ForwardPlan:
                 ms = main.cuda_stream
                 inter, ap, at = self._tables(0)
                 self._mark("cost", main, True)
-                rc = L.dmm_iou_counts(_ptr(masks_p), _ptr(masks_t), dt, B, N, M, HW, sp_b, sp_n, st_b, st_m,
-                                      _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), ms)
+                _lib.call("dmm_iou_counts", None, _ptr(masks_p), _ptr(masks_t), dt, B, N, M, HW, sp_b, sp_n, st_b, st_m,
+                          _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), ms)
                 self._mark("cost", main, False)
-                rc |= self._feature_sim(L, feat_p, feat_t, n_valid, m_valid, ms)
+                self._feature_sim(feat_p, feat_t, n_valid, m_valid, ms)
                 self._mark("solver", main, True)
-                rc |= self._solver(L)(_ptr(self.cos), _ptr(inter), _ptr(ap), _ptr(at), _ptr(score_p), B, N, M,
-                                       _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter),
-                                       int(proj_iter), float(lr), int(is_test), _ptr(self.sim), _ptr(self.R),
-                                       _ptr(self.Rb), _ptr(self.match_score), _ptr(self.det_score),
-                                       _ptr(self.iters), None, ms)
+                _lib.call(self.solver_entry, None, _ptr(self.cos), _ptr(inter), _ptr(ap), _ptr(at), _ptr(score_p), B, N,
+                          M, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter), float(lr),
+                          int(is_test), _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.match_score),
+                          _ptr(self.det_score), _ptr(self.iters), None, ms)
                 self._mark("solver", main, False)
                 self._mark("mix", main, True)
-                rc |= L.dmm_mask_mix_to(_ptr(self.Rb), _ptr(masks_p), dt, B, N, M, Pp, HW, sp_b, sp_n, _ptr(n_valid),
-                                        _ptr(m_valid), _ptr(self.full_outmask), _DT[self.out_dtype], self.so_b, self.so_m, ms)
+                _lib.call("dmm_mask_mix_to", None, _ptr(self.Rb), _ptr(masks_p), dt, B, N, M, Pp, HW, sp_b, sp_n,
+                          _ptr(n_valid), _ptr(m_valid), _ptr(self.full_outmask), _DT[self.out_dtype], self.so_b,
+                          self.so_m, ms)
                 self._mark("mix", main, False)
-            _lib.check(rc, "ForwardPlan.run (granular, timed)")
             return self.full_outmask, self.match_score, self.det_score
         if not self.pipeline:
-            with _lib.device_guard(self.device):
-                rc = L.dmm_match_forward_ws(
-                    _ptr(masks_p), _ptr(masks_t), dt, _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, HW, D, sp_b,
-                    sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
-                    float(lr), int(is_test), _ptr(self.full_outmask), _ptr(self.match_score), _ptr(self.det_score),
-                    _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace), self.ws_bytes,
-                    ctypes.byref(self._ws_state), _stream(masks_p))
-            _lib.check(rc, "dmm_match_forward_ws")
+            _lib.call("dmm_match_forward_ws", self.device,
+                      _ptr(masks_p), _ptr(masks_t), dt, _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, HW, D, sp_b,
+                      sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
+                      float(lr), int(is_test), _ptr(self.full_outmask), _ptr(self.match_score), _ptr(self.det_score),
+                      _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace), self.ws_bytes,
+                      ctypes.byref(self._ws_state), _stream(masks_p))
             return self.full_outmask, self.match_score, self.det_score
 
         es = masks_p.element_size()
@@ -1154,23 +1079,23 @@ class ForwardPlan:
             self.ev_start.record(main)
             # ---- latency lane: normalise + cosine for every frame --------------------------------------------
             side.wait_event(self.ev_start)
-            rc = self._feature_sim(L, feat_p, feat_t, n_valid, m_valid, ss)
+            self._feature_sim(feat_p, feat_t, n_valid, m_valid, ss)
             # ---- streaming lane: cost(A), cost(B) ------------------------------------------------------------
             for h, (b, e) in enumerate(self.halves):
                 inter, ap, at = self._tables(h)
                 self._mark("cost", main, True)
-                rc |= L.dmm_iou_counts(masks_p.data_ptr() + es * b * sp_b, masks_t.data_ptr() + es * b * st_b, dt,
-                                       e - b, N, M, HW, sp_b, sp_n, st_b, st_m, nv(n_valid, b), nv(m_valid, b),
-                                       _ptr(inter), _ptr(ap), _ptr(at), ms)
+                _lib.call("dmm_iou_counts", None, masks_p.data_ptr() + es * b * sp_b, masks_t.data_ptr() + es * b * st_b,
+                          dt, e - b, N, M, HW, sp_b, sp_n, st_b, st_m, nv(n_valid, b), nv(m_valid, b), _ptr(inter),
+                          _ptr(ap), _ptr(at), ms)
                 self._mark("cost", main, False)
                 self.ev_cost[h].record(main)
             # ---- latency lane: solver(h) as soon as cost(h) is done ------------------------------------------
             for h, (b, e) in enumerate(self.halves):
                 inter, ap, at = self._tables(h)
                 side.wait_event(self.ev_cost[h])
-                rc |= self._solver(L)(
-                    self.cos.data_ptr() + 4 * b * M * N, _ptr(inter), _ptr(ap), _ptr(at), score_p.data_ptr() + 4 * b * N,
-                    e - b, N, M, nv(n_valid, b), nv(m_valid, b), float(score_weight), int(max_iter), int(proj_iter),
+                _lib.call(
+                    self.solver_entry, None, self.cos.data_ptr() + 4 * b * M * N, _ptr(inter), _ptr(ap), _ptr(at),
+                    score_p.data_ptr() + 4 * b * N, e - b, N, M, nv(n_valid, b), nv(m_valid, b), float(score_weight), int(max_iter), int(proj_iter),
                     float(lr), int(is_test), self.sim.data_ptr() + 4 * b * M * N,
                     None if self.R is None else self.R.data_ptr() + 4 * b * M * Pp, self.Rb.data_ptr() + 4 * b * M * Pp,
                     self.match_score.data_ptr() + 4 * b * M, self.det_score.data_ptr() + 4 * b * M,
@@ -1180,10 +1105,9 @@ class ForwardPlan:
             for h, (b, e) in enumerate(self.halves):
                 main.wait_event(self.ev_solved[h])
                 self._mark("mix", main, True)
-                rc |= L.dmm_mask_mix_to(self.Rb.data_ptr() + 4 * b * M * Pp, masks_p.data_ptr() + es * b * sp_b, dt,
-                                        e - b, N, M, Pp, HW, sp_b, sp_n, nv(n_valid, b), nv(m_valid, b),
-                                        self.full_outmask.data_ptr() + self.full_outmask.element_size() * b * self.so_b,
-                                        _DT[self.out_dtype], self.so_b, self.so_m, ms)
+                _lib.call("dmm_mask_mix_to", None, self.Rb.data_ptr() + 4 * b * M * Pp,
+                          masks_p.data_ptr() + es * b * sp_b, dt, e - b, N, M, Pp, HW, sp_b, sp_n, nv(n_valid, b),
+                          nv(m_valid, b), self.full_outmask.data_ptr() + self.full_outmask.element_size() * b * self.so_b,
+                          _DT[self.out_dtype], self.so_b, self.so_m, ms)
                 self._mark("mix", main, False)
-        _lib.check(rc, "ForwardPlan.run (pipelined)")
         return self.full_outmask, self.match_score, self.det_score

@@ -77,12 +77,9 @@ def paste_masks(mask_prob: torch.Tensor, boxes: torch.Tensor, im_h: int, im_w: i
     packed = None
     if want_packed:
         packed = torch.empty((P, 4 * ((im_h * im_w + 255) // 256)), dtype=torch.int64, device=prob.device)
-    with _lib.device_guard(prob.device):
-        rc = _lib.load().dmm_paste_masks_f32(prob.data_ptr(), P, M, boxes.data_ptr(), int(im_h), int(im_w), float(thresh),
-                                             int(padding), planes.data_ptr(), im_h * im_w, nb.data_ptr(),
-                                             None if packed is None else packed.data_ptr(),
-                                             torch.cuda.current_stream(prob.device).cuda_stream)
-    _lib.check(rc, "dmm_paste_masks_f32")
+    _lib.call("dmm_paste_masks_f32", prob.device, prob.data_ptr(), P, M, boxes.data_ptr(), int(im_h), int(im_w),
+              float(thresh), int(padding), planes.data_ptr(), im_h * im_w, nb.data_ptr(),
+              None if packed is None else packed.data_ptr(), torch.cuda.current_stream(prob.device).cuda_stream)
     return (planes, nb, packed) if want_packed else (planes, nb)
 
 
@@ -95,11 +92,8 @@ def nms_batched(boxes: Sequence[torch.Tensor], scores: Sequence[torch.Tensor], t
     alls = torch.cat([s.float() for s in scores], 0).contiguous()
     keep = torch.empty((max(int(allb.shape[0]), 1),), dtype=torch.int32, device=dev)
     cnt = torch.empty((len(boxes),), dtype=torch.int32, device=dev)
-    with _lib.device_guard(dev):
-        rc = _lib.load().dmm_nms_f32(allb.data_ptr(), alls.data_ptr(), offs.data_ptr(), len(boxes), max(counts + [0]),
-                                     float(thresh), int(max_keep), keep.data_ptr(), cnt.data_ptr(),
-                                     torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc, "dmm_nms_f32")
+    _lib.call("dmm_nms_f32", dev, allb.data_ptr(), alls.data_ptr(), offs.data_ptr(), len(boxes), max(counts + [0]),
+              float(thresh), int(max_keep), keep.data_ptr(), cnt.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
     cnt_h = cnt.tolist()
     out, o = [], 0
     for i, n in enumerate(counts):
@@ -249,23 +243,17 @@ def prepare_slots(clip: ClipProposals, slots: ProposalSlots, nms_thresh: float, 
     if not clip.prob.is_cuda:
         raise _lib.DmmError("prepare_slots needs tensors on an MI355X device (no CPU fallback)")
     assert clip.B == slots.B and clip.R == slots.R
-    L = _lib.load()
-    s = torch.cuda.current_stream(clip.prob.device).cuda_stream
+    dev = clip.prob.device
+    s = torch.cuda.current_stream(dev).cuda_stream
     sp = None if step is None else step.data_ptr()
-    with _lib.device_guard(clip.prob.device):
-        rc = L.dmm_proposal_boxes_f32(clip.prob.data_ptr(), clip.boxes.data_ptr(), clip.counts.data_ptr(), clip.B, clip.R,
-                                      clip.M, slots.H, slots.W, float(mask_thresh), int(padding), sp,
-                                      slots.tight.data_ptr(), s)
-        _lib.check(rc, "dmm_proposal_boxes_f32")
-        rc = L.dmm_nms_slots_f32(slots.tight.data_ptr(), clip.scores.data_ptr(), clip.counts.data_ptr(), clip.B, clip.R,
-                                 float(nms_thresh), slots.K, sp, slots.keep.data_ptr(), slots.count.data_ptr(), s)
-        _lib.check(rc, "dmm_nms_slots_f32")
-        rc = L.dmm_paste_kept_f32(clip.prob.data_ptr(), clip.boxes.data_ptr(), clip.scores.data_ptr(),
-                                  slots.tight.data_ptr(), slots.keep.data_ptr(), slots.count.data_ptr(), clip.B, clip.R,
-                                  clip.M, slots.K, slots.H, slots.W, int(padding), sp,
-                                  None if img_base is None else img_base.data_ptr(),
-                                  None if slots.planes is None else slots.planes.data_ptr(),
-                                  slots.H * slots.W, slots.packed.data_ptr(), slots.boxes.data_ptr(),
-                                  slots.scores.data_ptr(), slots.rois.data_ptr(), s)
-        _lib.check(rc, "dmm_paste_kept_f32")
+    with _lib.device_guard(dev):
+        _lib.call("dmm_proposal_boxes_f32", None, clip.prob.data_ptr(), clip.boxes.data_ptr(), clip.counts.data_ptr(),
+                  clip.B, clip.R, clip.M, slots.H, slots.W, float(mask_thresh), int(padding), sp, slots.tight.data_ptr(), s)
+        _lib.call("dmm_nms_slots_f32", None, slots.tight.data_ptr(), clip.scores.data_ptr(), clip.counts.data_ptr(), clip.B,
+                  clip.R, float(nms_thresh), slots.K, sp, slots.keep.data_ptr(), slots.count.data_ptr(), s)
+        _lib.call("dmm_paste_kept_f32", None, clip.prob.data_ptr(), clip.boxes.data_ptr(), clip.scores.data_ptr(),
+                  slots.tight.data_ptr(), slots.keep.data_ptr(), slots.count.data_ptr(), clip.B, clip.R, clip.M, slots.K,
+                  slots.H, slots.W, int(padding), sp, None if img_base is None else img_base.data_ptr(),
+                  None if slots.planes is None else slots.planes.data_ptr(), slots.H * slots.W, slots.packed.data_ptr(),
+                  slots.boxes.data_ptr(), slots.scores.data_ptr(), slots.rois.data_ptr(), s)
     return slots

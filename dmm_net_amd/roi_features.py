@@ -65,12 +65,8 @@ def roialign4_mean_into(rois: torch.Tensor, feats, out: torch.Tensor) -> torch.T
     assert rois.is_contiguous() and rois.dtype == torch.float32 and out.is_contiguous() and out.shape == (R, 4 * C)
     Hs, Ws, sc = _arrays(feats)
     ptrs = (ctypes.c_void_p * 4)(*[f.data_ptr() for f in feats])
-    L = _lib.load()
-    with _lib.device_guard(rois.device):
-        rc = (L.dmm_roialign4_mean_nhwc_fwd if nhwc else L.dmm_roialign4_mean_fwd)(
-            ptrs, _DT[f0.dtype], B, C, Hs, Ws, sc, rois.data_ptr(), R, out.data_ptr(),
-            torch.cuda.current_stream(rois.device).cuda_stream)
-    _lib.check(rc, "dmm_roialign4_mean_nhwc_fwd" if nhwc else "dmm_roialign4_mean_fwd")
+    _lib.call("dmm_roialign4_mean_nhwc_fwd" if nhwc else "dmm_roialign4_mean_fwd", rois.device, ptrs, _DT[f0.dtype], B, C,
+              Hs, Ws, sc, rois.data_ptr(), R, out.data_ptr(), torch.cuda.current_stream(rois.device).cuda_stream)
     return out
 
 
@@ -104,17 +100,16 @@ class _RoiAlign4Mean(torch.autograd.Function):
         Ws = (ctypes.c_int * 4)(*[s[3] for s in ctx.shapes])
         sc = (ctypes.c_float * 4)(*SCALES)
         ptrs = (ctypes.c_void_p * 4)(*[d.data_ptr() for d in dfs])
-        L, R = _lib.load(), int(rois.shape[0])
+        R = int(rois.shape[0])
         stream = torch.cuda.current_stream(dout.device).cuda_stream
-        with _lib.device_guard(dout.device):
-            if ctx.det:                                   # a gather in a fixed roi order instead of the atomic scatter
-                ws = torch.empty((max(int(L.dmm_roialign4_mean_bwd_det_workspace_bytes(R, Hs, Ws)), 16),), dtype=torch.uint8,
-                                 device=dout.device)
-                rc = L.dmm_roialign4_mean_bwd_det(dout.data_ptr(), B, C, Hs, Ws, sc, rois.data_ptr(), R, ptrs, ws.data_ptr(),
-                                                  ws.numel(), stream)
-            else:
-                rc = L.dmm_roialign4_mean_bwd(dout.data_ptr(), B, C, Hs, Ws, sc, rois.data_ptr(), R, ptrs, stream)
-        _lib.check(rc, "dmm_roialign4_mean_bwd_det" if ctx.det else "dmm_roialign4_mean_bwd")
+        if ctx.det:                                       # a gather in a fixed roi order instead of the atomic scatter
+            ws = torch.empty((max(int(_lib.load().dmm_roialign4_mean_bwd_det_workspace_bytes(R, Hs, Ws)), 16),),
+                             dtype=torch.uint8, device=dout.device)
+            _lib.call("dmm_roialign4_mean_bwd_det", dout.device, dout.data_ptr(), B, C, Hs, Ws, sc, rois.data_ptr(), R, ptrs,
+                      ws.data_ptr(), ws.numel(), stream)
+        else:
+            _lib.call("dmm_roialign4_mean_bwd", dout.device, dout.data_ptr(), B, C, Hs, Ws, sc, rois.data_ptr(), R, ptrs,
+                      stream)
         return (None,) + tuple(d.to(ctx.dtype) for d in dfs)
 
 

@@ -144,7 +144,6 @@ class _BNActFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, running_mean, running_var, momentum, eps, relu, residual, groups=1, fork=False):
         from . import _lib
-        L = _lib.load()
         assert x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=_CL)
         B, C, H, W = x.shape
         assert B % groups == 0, (B, groups)
@@ -158,25 +157,20 @@ class _BNActFn(torch.autograd.Function):
         if residual is not None:
             assert residual.shape == x.shape and residual.dtype == x.dtype
             res = residual.contiguous(memory_format=_CL)
-        with _lib.device_guard(x.device):
-            if det:                                       # (the slab of per-workgroup partials, folded by the apply launch)
-                ws = _det_ws(int(L.dmm_bn_det_workspace_bytes(R, C, groups)), x.device)
-                _lib.check(L.dmm_bn_stats_det_grouped_bf16(x.data_ptr(), R, C, groups, ws.data_ptr(), ws.numel(), stream),
-                           "dmm_bn_stats_det_grouped_bf16")
-                _lib.check(L.dmm_bn_apply_det_grouped_bf16(
-                    x.data_ptr(), None if res is None else res.data_ptr(), R, C, groups, ws.data_ptr(), ws.numel(),
-                    weight.data_ptr(), bias.data_ptr(), None if running_mean is None else running_mean.data_ptr(),
-                    None if running_var is None else running_var.data_ptr(), float(momentum), float(eps), int(relu),
-                    y.data_ptr(), saved.data_ptr(), stream), "dmm_bn_apply_det_grouped_bf16")
-            else:
-                _lib.check(L.dmm_bn_stats_grouped_bf16(x.data_ptr(), R, C, groups, stats.data_ptr(), stream),
-                           "dmm_bn_stats_grouped_bf16")
-                _lib.check(L.dmm_bn_apply_grouped_bf16(x.data_ptr(), None if res is None else res.data_ptr(), R, C, groups,
-                                                       stats.data_ptr(), weight.data_ptr(), bias.data_ptr(),
-                                                       None if running_mean is None else running_mean.data_ptr(),
-                                                       None if running_var is None else running_var.data_ptr(),
-                                                       float(momentum), float(eps), int(relu), y.data_ptr(), saved.data_ptr(),
-                                                       stream), "dmm_bn_apply_grouped_bf16")
+        rm = None if running_mean is None else running_mean.data_ptr()
+        rv = None if running_var is None else running_var.data_ptr()
+        if det:                                           # (the slab of per-workgroup partials, folded by the apply launch)
+            ws = _det_ws(int(_lib.load().dmm_bn_det_workspace_bytes(R, C, groups)), x.device)
+            _lib.call("dmm_bn_stats_det_grouped_bf16", x.device, x.data_ptr(), R, C, groups, ws.data_ptr(), ws.numel(),
+                      stream)
+            _lib.call("dmm_bn_apply_det_grouped_bf16", x.device, x.data_ptr(), None if res is None else res.data_ptr(), R,
+                      C, groups, ws.data_ptr(), ws.numel(), weight.data_ptr(), bias.data_ptr(), rm, rv, float(momentum),
+                      float(eps), int(relu), y.data_ptr(), saved.data_ptr(), stream)
+        else:
+            _lib.call("dmm_bn_stats_grouped_bf16", x.device, x.data_ptr(), R, C, groups, stats.data_ptr(), stream)
+            _lib.call("dmm_bn_apply_grouped_bf16", x.device, x.data_ptr(), None if res is None else res.data_ptr(), R, C,
+                      groups, stats.data_ptr(), weight.data_ptr(), bias.data_ptr(), rm, rv, float(momentum), float(eps),
+                      int(relu), y.data_ptr(), saved.data_ptr(), stream)
         ctx.save_for_backward(x, y, weight, bias, saved)
         ctx.relu, ctx.has_res, ctx.groups, ctx.det = bool(relu), residual is not None, groups, det
         # fork: the output as TWO tensors (the second an alias) for its two consumers -- a residual block's first convolution and
@@ -187,7 +181,6 @@ class _BNActFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, dy, dy2=None):
         from . import _lib
-        L = _lib.load()
         x, y, weight, bias, saved = ctx.saved_tensors
         # no residual in front of the ReLU: the mask is recomputed from x (the forward's own fma), y is not read
         mode = 0 if not ctx.relu else (1 if ctx.has_res else 2)
@@ -205,29 +198,21 @@ class _BNActFn(torch.autograd.Function):
         dres = torch.empty_like(x, memory_format=_CL) if ctx.has_res else None
         dw = torch.empty((C,), dtype=torch.float32, device=x.device)
         db = torch.empty((C,), dtype=torch.float32, device=x.device)
+        p2 = None if dy2 is None else dy2.data_ptr()
+        pdres = None if dres is None else dres.data_ptr()
         if ctx.det:
-            ws = _det_ws(int(L.dmm_bn_det_workspace_bytes(R, C, groups)), x.device)
-            p2 = None if dy2 is None else dy2.data_ptr()
-            with _lib.device_guard(x.device):
-                _lib.check(L.dmm_bn_bwd_reduce_det_grouped_bf16(dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
-                                                                saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), mode,
-                                                                ws.data_ptr(), ws.numel(), stream),
-                           "dmm_bn_bwd_reduce_det_grouped_bf16")
-                _lib.check(L.dmm_bn_bwd_dx_det_grouped_bf16(dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
-                                                            saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), ws.data_ptr(),
-                                                            ws.numel(), mode, dx.data_ptr(),
-                                                            None if dres is None else dres.data_ptr(), dw.data_ptr(),
-                                                            db.data_ptr(), stream), "dmm_bn_bwd_dx_det_grouped_bf16")
+            ws = _det_ws(int(_lib.load().dmm_bn_det_workspace_bytes(R, C, groups)), x.device)
+            _lib.call("dmm_bn_bwd_reduce_det_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C,
+                      groups, saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), mode, ws.data_ptr(), ws.numel(), stream)
+            _lib.call("dmm_bn_bwd_dx_det_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C,
+                      groups, saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), ws.data_ptr(), ws.numel(), mode,
+                      dx.data_ptr(), pdres, dw.data_ptr(), db.data_ptr(), stream)
             return dx, dw, db, None, None, None, None, None, dres, None, None
-        with _lib.device_guard(x.device):
-            p2 = None if dy2 is None else dy2.data_ptr()
-            _lib.check(L.dmm_bn_bwd_reduce_grouped_bf16(dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
-                                                        saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), mode,
-                                                        sums.data_ptr(), stream), "dmm_bn_bwd_reduce_grouped_bf16")
-            _lib.check(L.dmm_bn_bwd_dx_grouped_bf16(dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups, saved.data_ptr(),
-                                                    weight.data_ptr(), bias.data_ptr(), sums.data_ptr(), mode, dx.data_ptr(),
-                                                    None if dres is None else dres.data_ptr(), dw.data_ptr(), db.data_ptr(),
-                                                    stream), "dmm_bn_bwd_dx_grouped_bf16")
+        _lib.call("dmm_bn_bwd_reduce_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
+                  saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), mode, sums.data_ptr(), stream)
+        _lib.call("dmm_bn_bwd_dx_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
+                  saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), sums.data_ptr(), mode, dx.data_ptr(), pdres,
+                  dw.data_ptr(), db.data_ptr(), stream)
         return dx, dw, db, None, None, None, None, None, dres, None, None
 
 
@@ -292,15 +277,13 @@ def _wgrad_launch(rec):
     if kind == "1x1":
         rows, co, ci = dims
         ws = torch.empty((max(int(L.dmm_wgrad_workspace_bytes(rows, co, ci)), 16),), dtype=torch.uint8, device=dev)
-        with _lib.device_guard(dev):
-            _lib.check(L.dmm_wgrad_bf16(dy.data_ptr(), x.data_ptr(), rows, co, ci, co, ci, dw.data_ptr(), ws.data_ptr(),
-                                        ws.numel(), stream), "dmm_wgrad_bf16")
+        _lib.call("dmm_wgrad_bf16", dev, dy.data_ptr(), x.data_ptr(), rows, co, ci, co, ci, dw.data_ptr(), ws.data_ptr(),
+                  ws.numel(), stream)
     else:
         B, H, W, ci, co, stride, Ho, Wo = dims
         ws = torch.empty((max(int(L.dmm_wgrad_workspace_bytes(B * Ho * Wo, co, 9 * ci)), 16),), dtype=torch.uint8, device=dev)
-        with _lib.device_guard(dev):
-            _lib.check(L.dmm_wgrad3x3_bf16(dy.data_ptr(), x.data_ptr(), B, H, W, ci, co, stride, dw.data_ptr(), ws.data_ptr(),
-                                           ws.numel(), stream), "dmm_wgrad3x3_bf16")
+        _lib.call("dmm_wgrad3x3_bf16", dev, dy.data_ptr(), x.data_ptr(), B, H, W, ci, co, stride, dw.data_ptr(),
+                  ws.data_ptr(), ws.numel(), stream)
 
 
 def _wgrad(rec):
@@ -323,9 +306,8 @@ def _subsample(x, stride: int):
     if stride == 2 and x.is_cuda and x.dtype == torch.bfloat16 and C % 8 == 0 and x.is_contiguous(memory_format=_CL):
         from . import _lib
         y = torch.empty((B, C, (H + 1) // 2, (W + 1) // 2), dtype=x.dtype, device=x.device, memory_format=_CL)
-        with _lib.device_guard(x.device):
-            _lib.check(_lib.load().dmm_subsample2_bf16(x.data_ptr(), B, H, W, C, y.data_ptr(),
-                                                       torch.cuda.current_stream(x.device).cuda_stream), "dmm_subsample2_bf16")
+        _lib.call("dmm_subsample2_bf16", x.device, x.data_ptr(), B, H, W, C, y.data_ptr(),
+                  torch.cuda.current_stream(x.device).cuda_stream)
         return y
     return x[:, :, ::stride, ::stride].contiguous(memory_format=_CL)
 
@@ -337,10 +319,8 @@ def _upsample_zero(dy, full, stride: int):
         from . import _lib
         dy = dy.contiguous(memory_format=_CL)
         dx = torch.empty(full, dtype=dy.dtype, device=dy.device, memory_format=_CL)
-        with _lib.device_guard(dy.device):
-            _lib.check(_lib.load().dmm_upsample2_zero_bf16(dy.data_ptr(), B, H, W, C, dx.data_ptr(),
-                                                           torch.cuda.current_stream(dy.device).cuda_stream),
-                       "dmm_upsample2_zero_bf16")
+        _lib.call("dmm_upsample2_zero_bf16", dy.device, dy.data_ptr(), B, H, W, C, dx.data_ptr(),
+                  torch.cuda.current_stream(dy.device).cuda_stream)
         return dx
     dx = torch.zeros(full, dtype=dy.dtype, device=dy.device).to(memory_format=_CL)
     dx[:, :, ::stride, ::stride] = dy
@@ -448,15 +428,12 @@ def _channel_sums(dy, det: bool = False):
             ws = _det_ws(int(L.dmm_bn_det_workspace_bytes(R, C, 1)), dy.device)
             stats = torch.empty((2 * C,), dtype=torch.float32, device=dy.device)
             stream = torch.cuda.current_stream(dy.device).cuda_stream
-            with _lib.device_guard(dy.device):
-                _lib.check(L.dmm_bn_stats_det_grouped_bf16(dy.data_ptr(), R, C, 1, ws.data_ptr(), ws.numel(), stream),
-                           "dmm_bn_stats_det_grouped_bf16")
-                _lib.check(L.dmm_bn_fold_det(ws.data_ptr(), ws.numel(), R, C, 1, stats.data_ptr(), stream), "dmm_bn_fold_det")
+            _lib.call("dmm_bn_stats_det_grouped_bf16", dy.device, dy.data_ptr(), R, C, 1, ws.data_ptr(), ws.numel(), stream)
+            _lib.call("dmm_bn_fold_det", dy.device, ws.data_ptr(), ws.numel(), R, C, 1, stats.data_ptr(), stream)
             return stats[:C]
         stats = _zeroed(2 * C, dy.device)
-        with _lib.device_guard(dy.device):
-            _lib.check(_lib.load().dmm_bn_stats_bf16(dy.data_ptr(), B * H * W, C, stats.data_ptr(),
-                                                     torch.cuda.current_stream(dy.device).cuda_stream), "dmm_bn_stats_bf16")
+        _lib.call("dmm_bn_stats_bf16", dy.device, dy.data_ptr(), B * H * W, C, stats.data_ptr(),
+                  torch.cuda.current_stream(dy.device).cuda_stream)
         return stats[:C]
     return dy.float().sum((0, 2, 3))
 
@@ -655,9 +632,7 @@ class TrainEncoder(nn.Module):
                 rec += [m.weight.data_ptr(), d.data_ptr(), n, blk]
                 blk += (n + 8191) // 8192
             got = memo[key] = (ptrs, _lib.small_to_device(rec, torch.int64, dev), blk)
-        with _lib.device_guard(dev):
-            _lib.check(_lib.load().dmm_cast_many_bf16(got[1].data_ptr(), len(convs), got[2],
-                                                      torch.cuda.current_stream(dev).cuda_stream), "dmm_cast_many_bf16")
+        _lib.call("dmm_cast_many_bf16", dev, got[1].data_ptr(), len(convs), got[2], torch.cuda.current_stream(dev).cuda_stream)
 
     def _prep_3x3(self, convs, t):
         """bf16 channels-last copies of the 3x3 weights of one segment (and the flipped + transposed ones their data gradients
@@ -686,9 +661,7 @@ class TrainEncoder(nn.Module):
             got = memo[key] = (ptrs, table, pairs, tile)
         _, table, pairs, tiles = got
         dev = convs[0].weight.device
-        with _lib.device_guard(dev):
-            _lib.check(_lib.load().dmm_wprep3x3_bf16(table.data_ptr(), len(convs), tiles,
-                                                     torch.cuda.current_stream(dev).cuda_stream), "dmm_wprep3x3_bf16")
+        _lib.call("dmm_wprep3x3_bf16", dev, table.data_ptr(), len(convs), tiles, torch.cuda.current_stream(dev).cuda_stream)
         for m, pr in zip(convs, pairs):
             t[id(m)] = pr
 

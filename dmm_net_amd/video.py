@@ -46,11 +46,8 @@ def mask_boxes(masks: torch.Tensor, thresh: float = 0.0):
         masks = masks.contiguous()
     boxes = torch.empty((R, 4), dtype=torch.float32, device=masks.device)
     valid = torch.empty((R,), dtype=torch.int32, device=masks.device)
-    with _lib.device_guard(masks.device):
-        rc = _lib.load().dmm_mask_boxes_f32(masks.data_ptr(), R, H, W, masks.stride(0) if R else H * W, float(thresh),
-                                            boxes.data_ptr(), valid.data_ptr(),
-                                            torch.cuda.current_stream(masks.device).cuda_stream)
-    _lib.check(rc, "dmm_mask_boxes_f32")
+    _lib.call("dmm_mask_boxes_f32", masks.device, masks.data_ptr(), R, H, W, masks.stride(0) if R else H * W,
+              float(thresh), boxes.data_ptr(), valid.data_ptr(), torch.cuda.current_stream(masks.device).cuda_stream)
     return boxes, valid
 
 
@@ -83,11 +80,8 @@ def merge_labels(outs: torch.Tensor, tplt_valid_batch: Optional[torch.Tensor] = 
         ov = tplt_valid_batch if tplt_valid_batch.dim() == 1 else tplt_valid_batch.sum(1)
         ov = ov.to(device=m.device, dtype=torch.int32).contiguous()
     labels = torch.empty((B, HW), dtype=torch.uint8, device=m.device)
-    with _lib.device_guard(m.device):
-        rc = _lib.load().dmm_merge_labels_f32(m.data_ptr(), B, O, HW, m.stride(0), m.stride(1),
-                                              None if ov is None else ov.data_ptr(), labels.data_ptr(),
-                                              torch.cuda.current_stream(m.device).cuda_stream)
-    _lib.check(rc, "dmm_merge_labels_f32")
+    _lib.call("dmm_merge_labels_f32", m.device, m.data_ptr(), B, O, HW, m.stride(0), m.stride(1),
+              None if ov is None else ov.data_ptr(), labels.data_ptr(), torch.cuda.current_stream(m.device).cuda_stream)
     return labels.view(B, *shape[2:])
 
 
@@ -268,10 +262,9 @@ class StepPlan:
         """The frame step as launches on the current stream (captured, or run directly)."""
         from . import ops
         from .roi_features import roialign4_mean_into
-        L = _lib.load()
         s = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.check(L.dmm_step_select_i32(self.tables.data_ptr(), self.step.data_ptr(), 2 * self.B, self.cur.data_ptr(), s),
-                   "dmm_step_select_i32")
+        _lib.call("dmm_step_select_i32", None, self.tables.data_ptr(), self.step.data_ptr(), 2 * self.B, self.cur.data_ptr(),
+                  s)
         prepare_slots(self.clip, self.slots, self.nms_thresh, self.mask_thresh, self.padding, step=self.step,
                       img_base=self.img_base)
         roialign4_mean_into(self.slots.rois, self.feats, self.feat_p)
@@ -285,13 +278,13 @@ class StepPlan:
             if self.row_scale is not None:
                 self.Rb.mul_(self.row_scale[:, :, None])         # rows of slots i < O with valid[i] == 0: zero weights
             c = self.clip
-            _lib.check(L.dmm_step_finish_f32(
-                self.Rb.data_ptr(), self.Pp, c.prob.data_ptr(), c.boxes.data_ptr(), self.slots.keep.data_ptr(),
-                self.slots.count.data_ptr(), self.B, c.R, c.M, self.K, self.O, self.H, self.W, self.padding,
-                self.step.data_ptr(), self.cur[0].data_ptr(), self.cur[1].data_ptr() if self.tail else None,
-                self.n_tplt.data_ptr(), self.full.data_ptr(), self.hist.data_ptr(), self.packed_hist.data_ptr(),
-                self.labels.data_ptr() if self.tail else None, s), "dmm_step_finish_f32")
-            _lib.check(L.dmm_step_advance(self.step.data_ptr(), s), "dmm_step_advance")
+            _lib.call("dmm_step_finish_f32", None,
+                      self.Rb.data_ptr(), self.Pp, c.prob.data_ptr(), c.boxes.data_ptr(), self.slots.keep.data_ptr(),
+                      self.slots.count.data_ptr(), self.B, c.R, c.M, self.K, self.O, self.H, self.W, self.padding,
+                      self.step.data_ptr(), self.cur[0].data_ptr(), self.cur[1].data_ptr() if self.tail else None,
+                      self.n_tplt.data_ptr(), self.full.data_ptr(), self.hist.data_ptr(), self.packed_hist.data_ptr(),
+                      self.labels.data_ptr() if self.tail else None, s)
+            _lib.call("dmm_step_advance", None, self.step.data_ptr(), s)
             return
         ops.match_forward_packed(self.slots.planes, self.slots.packed, self.hist, self.feat_p.view(self.B, self.K, self.D),
                                  self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0],
@@ -300,12 +293,11 @@ class StepPlan:
         if self.row_scale is not None:
             self.full.mul_(self.row_scale[:, :, None, None])
         if self.tail:
-            _lib.check(L.dmm_commit_masks_f32(self.full.data_ptr(), self.hist.data_ptr(), self.cur[1].data_ptr(), self.B,
-                                              self.O * self.H * self.W, s), "dmm_commit_masks_f32")
-            _lib.check(L.dmm_merge_labels_f32(self.full.data_ptr(), self.B, self.O, self.H * self.W,
-                                              self.O * self.H * self.W, self.H * self.W, self.n_tplt.data_ptr(),
-                                              self.labels.data_ptr(), s), "dmm_merge_labels_f32")
-        _lib.check(L.dmm_step_advance(self.step.data_ptr(), s), "dmm_step_advance")
+            _lib.call("dmm_commit_masks_f32", None, self.full.data_ptr(), self.hist.data_ptr(), self.cur[1].data_ptr(),
+                      self.B, self.O * self.H * self.W, s)
+            _lib.call("dmm_merge_labels_f32", None, self.full.data_ptr(), self.B, self.O, self.H * self.W,
+                      self.O * self.H * self.W, self.H * self.W, self.n_tplt.data_ptr(), self.labels.data_ptr(), s)
+        _lib.call("dmm_step_advance", None, self.step.data_ptr(), s)
 
     def run_step(self, graph: bool):
         if not graph:

@@ -25,6 +25,63 @@ def test_library_exports_every_declared_symbol():
     assert sorted(_lib.SYMBOLS) == syms, "dmm_net_amd/_lib.py binds a different symbol set than the header declares"
 
 
+
+def test_bindings_follow_the_header_declarations():
+    """_lib reads every argtypes / restype from include/dmm_match.h: one parameter bound per declared parameter, and one real
+    entry of each type class bound as its C type says."""
+    L = _lib.load()
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dmm_match.h")).read(), flags=re.S)
+    decls = re.findall(r"\bDMM_API\s+[^;(]*?\b(dmm_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt)
+    assert sorted(name for name, _ in decls) == header_symbols()
+    for name, params in decls:
+        n = 0 if params.strip() in ("", "void") else len(params.split(","))
+        assert len(getattr(L, name).argtypes) == n, name
+    assert L.dmm_iou_counts.argtypes[7] is ctypes.c_int64                       # int64_t sp_b
+    assert L.dmm_relax_match_f32.argtypes[13] is ctypes.c_float                 # float lr
+    assert L.dmm_relax_match_f32.argtypes[0] is ctypes.c_void_p                 # const float *
+    assert L.dmm_relax_match_f32.argtypes[-1] is ctypes.c_void_p                # dmm_stream_t
+    assert L.dmm_workspace_bytes.restype is ctypes.c_size_t
+    assert L.dmm_pack_words.restype is ctypes.c_int64
+    assert L.dmm_launch_count.restype is ctypes.c_longlong
+    assert L.dmm_status_string.restype is ctypes.c_char_p
+    assert L.dmm_iou_counts.restype is ctypes.c_int and L.dmm_abi_version.argtypes == []
+    assert L.dmm_match_forward_ws.argtypes[31] is ctypes.c_void_p              # int *ws_state: a host out-parameter
+    assert L.dmm_match_forward_ws.argtypes[30] is ctypes.c_size_t
+    assert L.dmm_pack_words(256) == 4 and L.dmm_pack_words(257) == 8
+    assert (_lib.DMM_OK, _lib.DMM_ERR_BAD_ARG, _lib.DMM_ERR_UNSUPPORTED, _lib.DMM_ERR_LAUNCH, _lib.DMM_ERR_WORKSPACE) == \
+        (0, 1, 2, 3, 4)
+    assert (_lib.DTYPE_F32, _lib.DTYPE_F16, _lib.DTYPE_BF16, _lib.DTYPE_PACKED1) == (0, 1, 2, 3)
+
+
+def test_header_parser_rejects_unmapped_types():
+    import pytest
+    decls, enums = _lib.parse_header("typedef enum dmm_x { DMM_A = 2, DMM_B } dmm_x;\n"
+                                     "DMM_API size_t dmm_ok(int64_t rows, const int H[4], void *p); /* (unsigned x) */\n"
+                                     "DMM_API void dmm_none(void);\n")
+    assert decls == {"dmm_ok": (ctypes.c_size_t, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]), "dmm_none": (None, [])}
+    assert enums == {"dmm_x": {"DMM_A": 2, "DMM_B": 3}}
+    for bad in ("DMM_API int dmm_bad(unsigned x, int y);", "DMM_API double dmm_bad(int y);", "DMM_API int dmm_bad(int);"):
+        with pytest.raises(_lib.DmmError, match="dmm_bad"):
+            _lib.parse_header(bad)
+    with pytest.raises(_lib.DmmError, match="'unsigned'"):
+        _lib.parse_header("DMM_API int dmm_bad(unsigned x);")
+
+
+def test_checked_call_names_the_entry_without_gpu():
+    """_lib.call raises DmmError naming the entry for a bad argument, and hands back a status listed in ``allow``."""
+    import pytest
+    with pytest.raises(_lib.DmmError, match=r"^dmm_iou_counts: bad argument"):
+        _lib.call("dmm_iou_counts", None, None, None, 0, 1, 4, 2, 16, 64, 16, 32, 16, None, None, None, None, None, None)
+    assert _lib.call("dmm_iou_counts", None, None, None, 0, 0, 4, 2, 16, 64, 16, 32, 16, None, None, None, None, None,
+                     None) == _lib.DMM_OK
+    one = ctypes.c_void_p(8)
+    args = (one, 1, 33, 40, None, None, 1, 1, 0.1, one, one, None, one, None)      # M beyond the solver envelope
+    with pytest.raises(_lib.DmmError, match=r"^dmm_relax_solve_f32: shape outside"):
+        _lib.call("dmm_relax_solve_f32", None, *args)
+    assert _lib.call("dmm_relax_solve_f32", None, *args, allow=(_lib.DMM_ERR_UNSUPPORTED,)) == 2
+    with pytest.raises(_lib.DmmError, match="dmm_relax_solve_f32"):               # allow lists only what it lists
+        _lib.call("dmm_relax_solve_f32", None, None, *args[1:], allow=(_lib.DMM_ERR_UNSUPPORTED,))
+
 def test_load_and_status_strings():
     if not os.path.exists(_lib.LIB_PATH):
         _lib.build()
