@@ -337,27 +337,39 @@ class _CosineFn(torch.autograd.Function):
         return (g_tf if ctx.needs_input_grad[0] else None), (g_pf if ctx.needs_input_grad[1] else None)
 
 
+# algo 'hun' assigns on the device (ops.hungarian_match: the same assignment as scipy); tests switch this off to compare
+# against the host route (scipy on the copied cost table, as the reference)
+_DEVICE_LSAP = True
+
+
 def _hungarian_forward(pf, tf, pm, tm, sc, targets, score_weight, is_test):
-    """algo 'hun' slot (match_model.py:122-123): same cost matrix, assignment from scipy (host)."""
+    """algo 'hun' slot (match_model.py:122-123): same cost matrix, exact assignment (scipy's) on the device inside the
+    solver envelope (one 4*B-byte status read, skipped under stream capture), scipy on the host outside it."""
     P, O = pm.shape[0], tm.shape[0]
     pm_b, tm_b = pm.unsqueeze(0), tm.unsqueeze(0)
     inter, ap, at = ops.iou_counts(pm_b, tm_b)
     cos = _CosineFn.apply(tf.unsqueeze(0), pf.unsqueeze(0))          # differentiable: cost_loss reaches the features
-    r = ops.relax_match(cos.detach(), inter, ap, at, sc.unsqueeze(0), score_weight=score_weight, max_iter=0,
-                        proj_iter=0, lr=0.0, is_test=is_test)
-    sim = r["sim"][0]
     Pp = ops.padded_width(P, O)
-    simp = sim.new_zeros((O, Pp))
-    simp[:, :P] = sim
-    R = hungarian_onehot(-simp)
-    maxv = R.max(dim=1, keepdim=True)[0]
-    logic = (R == maxv).float() if is_test else (R > 0.01).float()
-    Rb = R * logic
-    full = ops.mask_mix(Rb.unsqueeze(0), pm_b)[0]
-    ms = (R.clamp(0, 1) * simp).max(1)[0]
-    scp = sc.new_zeros(Pp)
-    scp[:P] = sc
-    ds = (scp.view(1, -1) * Rb).sum(1)
+    if _DEVICE_LSAP and O <= _lib.MAX_TEMPLATES and Pp <= _lib.MAX_PROPOSALS:
+        r = ops.hungarian_match(cos.detach(), inter, ap, at, sc.unsqueeze(0), score_weight=score_weight,
+                                is_test=is_test)
+        full = ops.mask_mix(r["Rb"], pm_b)[0]
+        ms, ds = r["match_score"][0], r["det_score"][0]
+    else:
+        r = ops.relax_match(cos.detach(), inter, ap, at, sc.unsqueeze(0), score_weight=score_weight, max_iter=0,
+                            proj_iter=0, lr=0.0, is_test=is_test)
+        sim = r["sim"][0]
+        simp = sim.new_zeros((O, Pp))
+        simp[:, :P] = sim
+        R = hungarian_onehot(-simp)
+        maxv = R.max(dim=1, keepdim=True)[0]
+        logic = (R == maxv).float() if is_test else (R > 0.01).float()
+        Rb = R * logic
+        full = ops.mask_mix(Rb.unsqueeze(0), pm_b)[0]
+        ms = (R.clamp(0, 1) * simp).max(1)[0]
+        scp = sc.new_zeros(Pp)
+        scp[:P] = sc
+        ds = (scp.view(1, -1) * Rb).sum(1)
     loss = pf.new_zeros(())
     if targets is not None:
         with torch.no_grad():                                        # gt one-hot carries no grad (match_helper.py:34-44)

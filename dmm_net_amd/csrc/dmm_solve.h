@@ -73,6 +73,13 @@ static inline int solver_block(int ng, int B) {
     const int helper_max = opt(DMM_OPT_SOLVER_HELPER_MAX);
     return B <= helper_max ? 128 : 64;
 }
+// dmm_lsap.hip: status [B] = 0 on `stream` (the Hungarian entries' answer for a call without templates)
+int lsap_zero_status(int32_t *status, int B, dmm_stream_t stream);
+// python: sim*(1-w) + iou*w with w a python float -> both scalars rounded to fp32 once
+static inline void sim_weights(float score_weight, float &w_feat, float &w_iou) {
+    w_feat = (float)(1.0 - (double)score_weight);
+    w_iou = score_weight;
+}
 }  // namespace dmm
 
 // Kernel selection: exact-row-count instantiations for the common small problems (one wave per

@@ -410,8 +410,8 @@ int dmm::relax_match_launch(const float *cos_in, const int32_t *inter, const int
     const int Pp = N > M ? N : M + 1;
     if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
     const dmm::RelaxParams prm{max_iter, proj_iter, lr};
-    // python: sim*(1-w) + iou*w with w a python float -> both scalars rounded to fp32 once
-    const float w_feat = (float)(1.0 - (double)score_weight), w_iou = score_weight;
+    float w_feat, w_iou;
+    dmm::sim_weights(score_weight, w_feat, w_iou);
     if (dmm::use_row_split(B, M, Pp))
         return dmm::launch_relax_match_rs(cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid, w_feat,
                                           w_iou, prm, is_test, sim_out, R_out, Rb_out, match_score, det_score,

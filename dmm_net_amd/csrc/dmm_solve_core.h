@@ -1118,6 +1118,15 @@ __device__ __forceinline__ int relax_core_h(const float (&C)[MT], int n, int m, 
 // relax_match_launch for the kernels built on relax_match_body)
 constexpr int kRelaxClearTables = 2;
 
+// sim = (1-w)*feature_sim + w*iou of one (template, proposal) entry from its counts: the prologue of every layer solver
+// (this one and the Hungarian one, dmm_lsap.hip), so that both hand the same sim on
+__device__ __forceinline__ float mix_sim(float cosv, int in, int ap, int at, float w_feat, float w_iou) {
+    const int un = ap + at - in;
+    const float iou = (float)in / ((float)un + 1e-6f);     // match_helper.py:24-27
+    const float a = cosv * w_feat, c = iou * w_iou;
+    return a + c;                                          // match_model.py:90
+}
+
 template <int MT, int NG, bool EXACT, bool HALF = false, bool W1TAPE = false>
 __device__ __forceinline__ void relax_match_body(
     const float *__restrict__ cos_in, const int32_t *__restrict__ inter, const int32_t *__restrict__ area_p,
@@ -1169,10 +1178,7 @@ __device__ __forceinline__ void relax_match_body(
             C[i] = 0.0f;
             if (DMM_ROW(i) && has_prop) {
                 const int in = inter_b[(int64_t)i * N + col];
-                const int un = ap + area_t[(int64_t)b * M + i] - in;
-                const float iou = (float)in / ((float)un + 1e-6f);     // match_helper.py:24-27
-                const float a = cos_b[(int64_t)i * N + col] * w_feat, c = iou * w_iou;
-                simv = a + c;                                          // match_model.py:90
+                simv = mix_sim(cos_b[(int64_t)i * N + col], in, ap, area_t[(int64_t)b * M + i], w_feat, w_iou);
                 sim_b[(int64_t)i * N + col] = simv;
             }
             if (DMM_ROW(i) && col < Pp) C[i] = -simv;                  // padded columns: -0.0

@@ -402,6 +402,106 @@ def relax_solve(C: torch.Tensor, max_iter: int, proj_iter: int, lr: float, rows_
     return dict(X=X, R=R, cost=cost, iters=iters)
 
 
+LSAP_INVALID, LSAP_INFEASIBLE = 1, 2          # dmm_lsap_f32's status codes
+_LSAP_MESSAGES = {LSAP_INVALID: "matrix contains invalid numeric entries", LSAP_INFEASIBLE: "cost matrix is infeasible"}
+
+
+def lsap_envelope(nr: int, nc: int) -> bool:
+    """Tables ``dmm_lsap_f32`` solves (after the transpose of a tall table)."""
+    nr, nc = min(nr, nc), max(nr, nc)
+    return nr <= _lib.MAX_TEMPLATES and nc <= _lib.MAX_PROPOSALS
+
+
+def check_lsap_status(status: torch.Tensor, where: str = "") -> None:
+    """Raise scipy's ``ValueError`` if a frame's assignment failed (reads the 4*B status bytes: one sync); nothing while a
+    stream capture is in progress (the status tensor is read after the graph has run)."""
+    if torch.cuda.is_current_stream_capturing():
+        return
+    st = status.cpu()
+    bad = torch.nonzero(st).flatten()
+    if bad.numel():
+        code = int(st[bad[0]])
+        raise ValueError(f"{_LSAP_MESSAGES.get(code, f'linear_sum_assignment status {code}')} ({where}frame {int(bad[0])})")
+
+
+def _lsap_host(C, rows_valid, cols_valid):
+    """scipy per frame: tables outside the kernel's envelope."""
+    import numpy as np
+    from scipy.optimize import linear_sum_assignment as lsa
+    B, nr, nc = C.shape
+    c = C.detach().cpu().numpy()
+    rv = [nr] * B if rows_valid is None else rows_valid.cpu().tolist()
+    cv = [nc] * B if cols_valid is None else cols_valid.cpu().tolist()
+    col = np.full((B, nr), -1, np.int32)
+    st = np.zeros((B,), np.int32)
+    for b in range(B):
+        try:
+            r, k = lsa(c[b, :rv[b], :cv[b]])
+        except ValueError as e:
+            st[b] = LSAP_INFEASIBLE if "infeasible" in str(e) else LSAP_INVALID
+            continue
+        col[b, r] = k
+    col_t = torch.from_numpy(col).to(C.device)
+    X = torch.zeros((B, nr, nc), dtype=torch.float32, device=C.device)
+    X.scatter_(2, col_t.clamp_min(0).long()[:, :, None], (col_t >= 0).float()[:, :, None])
+    return X, col_t, torch.from_numpy(st).to(C.device)
+
+
+def _i32(t):
+    return None if t is None else t.to(torch.int32).contiguous()
+
+
+def linear_sum_assignment(C: torch.Tensor, rows_valid=None, cols_valid=None, maximize: bool = False):
+    """scipy.optimize.linear_sum_assignment for B tables at once: C [B,nr,nc] -> (X [B,nr,nc] one-hot float32,
+    col_of_row [B,nr] int32 with -1 for an unassigned row, status [B] int32: 0 ok, LSAP_INVALID, LSAP_INFEASIBLE).
+    The same assignment as scipy, ties included (``dmm_lsap_f32``: fp64 on the float32 costs).  rows_valid / cols_valid
+    (int32 [B]) restrict frame b to its top-left block.  A tall table (nr > nc) is solved through its transpose, as scipy
+    does; tables outside the kernel's envelope (more than 32 x 256 after that) run scipy per frame on the host.  No status
+    is read here: ``check_lsap_status`` raises like scipy."""
+    _need_gpu(C)
+    C = C.float()
+    if maximize:
+        C = -C
+    B, nr, nc = C.shape
+    if not lsap_envelope(nr, nc):
+        return _lsap_host(C, rows_valid, cols_valid)
+    if nr > nc:
+        X_t, _, st = linear_sum_assignment(C.transpose(1, 2), cols_valid, rows_valid)
+        X = X_t.transpose(1, 2).contiguous()
+        col = torch.where(X.sum(2) > 0, X.argmax(2), -1).to(torch.int32)
+        return X, col, st
+    C = C.contiguous()
+    X = torch.empty((B, nr, nc), dtype=torch.float32, device=C.device)
+    col = torch.empty((B, nr), dtype=torch.int32, device=C.device)
+    st = torch.empty((B,), dtype=torch.int32, device=C.device)
+    _lib.call("dmm_lsap_f32", C.device, _ptr(C), B, nr, nc, _ptr(_i32(rows_valid)), _ptr(_i32(cols_valid)), _ptr(X),
+              _ptr(col), _ptr(st), _stream(C))
+    return X, col, st
+
+
+def hungarian_match(cos, inter, area_p, area_t, score_p, *, score_weight, is_test, n_valid=None, m_valid=None,
+                    check=True):
+    """``relax_match`` with the exact assignment (algo 'hun', ``dmm_hungarian_match_f32``): the same sim, C = -sim padded
+    to each frame's live width, R = Rb = the one-hot assignment scipy picks.  Returns dict(sim, R, Rb, match_score,
+    det_score, status).  ``check``: raise scipy's ValueError for a failed frame (reads the status: one sync, skipped
+    while a stream capture is in progress).  M <= 32 and Pp <= 256 only (DmmError otherwise)."""
+    _need_gpu(cos, inter)
+    B, M, N = cos.shape
+    Pp = padded_width(N, M)
+    dev = cos.device
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(sim=torch.empty((B, M, N), **f32), R=torch.empty((B, M, Pp), **f32), Rb=torch.empty((B, M, Pp), **f32),
+               match_score=torch.empty((B, M), **f32), det_score=torch.empty((B, M), **f32),
+               status=torch.empty((B,), dtype=torch.int32, device=dev))
+    cos, score_p = cos.contiguous().float(), score_p.contiguous().float()
+    _lib.call("dmm_hungarian_match_f32", dev, _ptr(cos), _ptr(inter), _ptr(area_p), _ptr(area_t), _ptr(score_p), B, N, M,
+              _ptr(n_valid), _ptr(m_valid), float(score_weight), int(is_test), _ptr(out["sim"]), _ptr(out["R"]),
+              _ptr(out["Rb"]), _ptr(out["match_score"]), _ptr(out["det_score"]), _ptr(out["status"]), _stream(cos))
+    if check:
+        check_lsap_status(out["status"])
+    return out
+
+
 def mask_mix(Rb: torch.Tensor, masks_p: torch.Tensor, n_valid=None, m_valid=None, out_dtype=None,
              shared: bool = False) -> torch.Tensor:
     """full_outmask [B,M,H,W] = Rb [B,M,Pp] @ masks_p [B,N,H*W] (zero planes for the padded columns).
@@ -807,6 +907,26 @@ def match_solve_packed(packed_p, packed_t, feat_p, feat_t, score_p, n_valid, m_v
               _ptr(score_p), B, N, M, int(HW), D, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter),
               int(proj_iter), float(lr), int(is_test), _ptr(Rb), _ptr(ms), _ptr(ds), None, None, _ptr(iters),
               _ptr(workspace), workspace.numel(), _stream(packed_p))
+    return out
+
+
+def match_solve_packed_hun(packed_p, packed_t, feat_p, feat_t, score_p, n_valid, m_valid, HW, *, score_weight, is_test,
+                           out, status, workspace):
+    """``match_solve_packed`` with the exact assignment (algo 'hun', ``dmm_match_solve_packed_hun``): ``out`` = (Rb,
+    match_score, det_score, ...) and ``status`` [B] int32 caller-owned, nothing allocated or read (a captured step)."""
+    _need_gpu(packed_p, packed_t, feat_p, feat_t, score_p)
+    B, N, wd = packed_p.shape
+    M, D = packed_t.shape[1], feat_p.shape[-1]
+    assert packed_p.is_contiguous() and packed_t.is_contiguous() and packed_t.shape == (B, M, wd) and wd == pack_words(HW)
+    assert feat_p.is_contiguous() and feat_t.is_contiguous() and score_p.is_contiguous()
+    Rb, ms, ds = out[:3]
+    assert Rb.is_contiguous() and Rb.shape == (B, M, padded_width(N, M))
+    assert status.dtype == torch.int32 and status.is_contiguous() and status.shape == (B,)
+    assert workspace.numel() >= int(_lib.load().dmm_workspace_bytes(B, N, M, D))
+    _lib.call("dmm_match_solve_packed_hun", packed_p.device, _ptr(packed_p), _ptr(packed_t), _ptr(feat_p), _ptr(feat_t),
+              _ptr(score_p), B, N, M, int(HW), D, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(is_test),
+              _ptr(Rb), _ptr(ms), _ptr(ds), None, None, _ptr(status), _ptr(workspace), workspace.numel(),
+              _stream(packed_p))
     return out
 
 

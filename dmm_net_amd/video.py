@@ -237,6 +237,9 @@ class StepPlan:
         self.row_scale_buf = torch.ones((B, O), **f32)           # fixed address: the captured step multiplies by it
         self.row_scale = None                                    # = row_scale_buf when the live templates are not a prefix
         self.labels = torch.zeros((B, H * W), dtype=torch.uint8, device=dev)
+        # algo 'hun': the assignment's status per frame step ([t, b], written by the graph at row *step), read once a clip
+        self.status = torch.zeros((B,), **i32)
+        self.status_all = torch.zeros((T_cap, B), **i32)
         self.graphs = {}                                         # row_scale? -> captured graph
         self.device = dev
 
@@ -268,13 +271,21 @@ class StepPlan:
         prepare_slots(self.clip, self.slots, self.nms_thresh, self.mask_thresh, self.padding, step=self.step,
                       img_base=self.img_base)
         roialign4_mean_into(self.slots.rois, self.feats, self.feat_p)
-        score_weight, max_iter, proj_iter, lr, is_test = self.cfg
+        score_weight, max_iter, proj_iter, lr, is_test, algo = self.cfg
         if self.fused:
-            ops.match_solve_packed(self.slots.packed, self.packed_hist, self.feat_p.view(self.B, self.K, self.D),
-                                   self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0], self.H * self.W,
-                                   score_weight=score_weight, max_iter=max_iter, proj_iter=proj_iter, lr=lr,
-                                   is_test=is_test, out=(self.Rb, self.out[1], self.out[2], self.out[3]),
-                                   workspace=self.workspace)
+            if algo == "hun":                                    # the exact assignment (scipy's), status per step
+                ops.match_solve_packed_hun(self.slots.packed, self.packed_hist, self.feat_p.view(self.B, self.K, self.D),
+                                           self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0],
+                                           self.H * self.W, score_weight=score_weight, is_test=is_test,
+                                           out=(self.Rb, self.out[1], self.out[2]), status=self.status,
+                                           workspace=self.workspace)
+                self.status_all.index_copy_(0, self.step.long(), self.status.view(1, self.B))
+            else:
+                ops.match_solve_packed(self.slots.packed, self.packed_hist, self.feat_p.view(self.B, self.K, self.D),
+                                       self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0], self.H * self.W,
+                                       score_weight=score_weight, max_iter=max_iter, proj_iter=proj_iter, lr=lr,
+                                       is_test=is_test, out=(self.Rb, self.out[1], self.out[2], self.out[3]),
+                                       workspace=self.workspace)
             if self.row_scale is not None:
                 self.Rb.mul_(self.row_scale[:, :, None])         # rows of slots i < O with valid[i] == 0: zero weights
             c = self.clip
@@ -286,6 +297,7 @@ class StepPlan:
                       self.labels.data_ptr() if self.tail else None, s)
             _lib.call("dmm_step_advance", None, self.step.data_ptr(), s)
             return
+        assert algo == "relax", "algo 'hun' runs in the fused epilogue form of the frame step only (FrameLoop._slots_ok)"
         ops.match_forward_packed(self.slots.planes, self.slots.packed, self.hist, self.feat_p.view(self.B, self.K, self.D),
                                  self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0],
                                  score_weight=score_weight, max_iter=max_iter, proj_iter=proj_iter, lr=lr, is_test=is_test,
@@ -346,7 +358,7 @@ class FrameLoop:
     ``encode_ahead = 1``.
 
     Two execution forms, bit-identical results (tests/test_gpu_video.py):
-    ``slots = True`` (default; raw proposal masks, ``algo: 'relax'``): the FIXED-SLOT frame step of ``StepPlan`` -- the
+    ``slots = True`` (default; raw proposal masks, ``algo: 'relax'``, or ``'hun'`` with the fused epilogue): the FIXED-SLOT frame step of ``StepPlan`` -- the
     clip's raw proposals are uploaded once (``proposals.ClipProposals``; ``run`` also accepts one directly), the proposals
     that survive NMS + top-k live in ``max_proposals`` slots per video with the live count on the device, the whole step is
     nine launches and, with ``graph = True``, ONE HIP-graph replay per frame: no host sync, upload or allocation per
@@ -354,7 +366,9 @@ class FrameLoop:
     pastes its selected proposals on the fly and emits ``out_mask_last``, the label map and the template history's 1-bit
     planes in the same pass.  ``on_labels(b, t, labels)`` receives a view of a per-clip buffer, valid in stream order.
     ``slots = False``: the BoxList path -- paste every raw proposal, NMS, index the kept ones (one host sync per frame),
-    ``DMM_Model.inference`` -- the reference's per-frame steps one to one (also taken for ``pasted = True`` / ``algo: 'hun'``).
+    ``DMM_Model.inference`` -- the reference's per-frame steps one to one (also taken for ``pasted = True``).  Under
+    ``algo: 'hun'`` the fixed-slot step keeps each step's assignment status on the device and reads the clip's once at its
+    end: a NaN / infeasible cost table raises scipy's ``ValueError`` naming the video and frame.
     """
 
     def __init__(self, encoder: Callable, dmm, refine: Optional[Callable] = None, nms_thresh: float = 0.4,
@@ -411,9 +425,11 @@ class FrameLoop:
 
     # ---- fixed-slot path ---------------------------------------------------------------------------------------------
     def _slots_ok(self, frames, proposals, O) -> bool:
-        """The fixed-slot step covers the product's configuration: raw mask probabilities, the relaxed solver, shapes
-        inside the kernels' envelopes.  Anything else takes the BoxList path."""
-        if not (self.slots and frames.is_cuda and not self.pasted and self.dmm.match_algo == "relax"):
+        """The fixed-slot step covers the product's configuration: raw mask probabilities, the relaxed solver (or the
+        Hungarian one in the fused epilogue form: <= 8 template slots, raw masks <= 30 x 30), shapes inside the kernels'
+        envelopes.  Anything else takes the BoxList path."""
+        algo = self.dmm.match_algo
+        if not (self.slots and frames.is_cuda and not self.pasted and algo in ("relax", "hun")):
             return False
         if isinstance(proposals, ClipProposals):
             R, Mm = proposals.R, proposals.M
@@ -423,7 +439,10 @@ class FrameLoop:
                 return False
             R, Mm = max(len(p) for p in ps), int(ps[0].get_field("mask").shape[-1])
         K = self.max_proposals if self.max_proposals > 0 else R
-        return 0 < R <= 1024 and Mm + 2 * self.padding <= 64 and frames.shape[0] * K <= 65535 and O <= 32 and K <= 256
+        ok = 0 < R <= 1024 and Mm + 2 * self.padding <= 64 and frames.shape[0] * K <= 65535 and O <= 32 and K <= 256
+        if algo == "hun":                                         # the Hungarian step exists in the fused epilogue form
+            ok = ok and self.fuse_epilogue and O <= 8 and Mm + 2 * self.padding <= 32
+        return ok
 
     def _run_slots(self, frames, first_masks, proposals, n_frames, targets, on_labels, next_frames=None):
         """``run`` on the fixed-slot step: zero host syncs per frame, and with ``graph`` one graph replay per frame.
@@ -519,7 +538,7 @@ class FrameLoop:
         K = self.max_proposals if self.max_proposals > 0 else R
         cfg = self.dmm.match_layer
         cfg = (float(cfg.cfgs["score_weight"]), int(cfg.max_iter), int(cfg.proj_iter), float(cfg.relax_lr),
-               int(bool(cfg.is_test)))
+               int(bool(cfg.is_test)), str(self.dmm.match_algo))
         tail = self.refine is None
         plan = self._plan
         if plan is None or plan.device != dev or not plan.key_fits(
@@ -541,6 +560,7 @@ class FrameLoop:
         plan.img_base[:T].copy_(_lib.small_to_device([(chunk_of[t] % 2) * G * B + (t - chunks[chunk_of[t]][0]) * B
                                                       for t in range(T)], torch.int32, dev))
         plan.step.zero_()
+        plan.status_all.zero_()
         y0 = first_masks.float().view(B, O, H * W)
         plan.hist.copy_(y0.view(B, O, H, W))
         if plan.fused:
@@ -625,6 +645,15 @@ class FrameLoop:
                         on_labels(b, t, lab_all[t, b])
             history.append(hist_all[t])
         self.last_iters = it_all
+        if cfg[5] == "hun" and not torch.cuda.is_current_stream_capturing():
+            # the clip's assignment statuses, one read: scipy's ValueError for a NaN / infeasible cost table
+            st = plan.status_all[:T].cpu()
+            bad = torch.nonzero(st)
+            if bad.numel():
+                t, b = (int(v) for v in bad[0])
+                from .ops import _LSAP_MESSAGES
+                raise ValueError(f"{_LSAP_MESSAGES.get(int(st[t, b]), 'linear_sum_assignment failed')} "
+                                 f"(video {b}, frame {t})")
         return history
 
     # model_encoder.py:115-134

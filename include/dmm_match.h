@@ -278,6 +278,29 @@ DMM_API int dmm_relax_solve_f32(const float *C, int B, int n, int m, const int32
                                 dmm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (3e) Exact linear sum assignment (the reference's algo 'hun', match_model.py:122-123: scipy.optimize.
+ * linear_sum_assignment, Crouse's shortest augmenting path in fp64).  One wave per frame; the same assignment as scipy
+ * on every input, ties included.  C [B,nr,nc]: frame b solves its top-left [rows_valid[b], cols_valid[b]] block
+ * (NULL = all), a block with more live rows than live columns through its transpose, as scipy does.
+ * Outputs: X [B,nr,nc] one-hot (may be NULL), col4row [B,nr] with -1 for an unassigned row (may be NULL), status [B]:
+ * 0 ok, 1 a NaN or -inf entry (scipy: "invalid numeric entries"), 2 no complete assignment (scipy: "cost matrix is
+ * infeasible"); the outputs of such a frame are zero (-1).  Requires nr <= nc, nr <= DMM_MAX_TEMPLATES and
+ * nc <= DMM_MAX_PROPOSALS (DMM_ERR_UNSUPPORTED otherwise).
+ * ------------------------------------------------------------------------------------------- */
+DMM_API int dmm_lsap_f32(const float *C, int B, int nr, int nc, const int32_t *rows_valid, const int32_t *cols_valid,
+                         float *X, int32_t *col4row, int32_t *status, dmm_stream_t stream);
+
+/* (3f) (3) with the assignment of (3e) in place of the relaxed solver: sim exactly as (3) computes it, C = -sim padded
+ * with -0.0 to each frame's live width Pp_b = max(n_b, m_b + 1), R = Rb = the one-hot assignment [B,M,Pp] (R may be
+ * NULL), match_score = max_p clamp(R,0,1)*sim_pad, det_score = sum_p score_p*Rb [B,M], status [B] as in (3e).  Same
+ * envelope as (3). */
+DMM_API int dmm_hungarian_match_f32(const float *cos_in, const int32_t *inter, const int32_t *area_p,
+                                    const int32_t *area_t, const float *score_p, int B, int N, int M,
+                                    const int32_t *n_valid, const int32_t *m_valid, float score_weight, int is_test,
+                                    float *sim_out, float *R_out, float *Rb_out, float *match_score, float *det_score,
+                                    int32_t *status, dmm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (3b) Backward of (3) with respect to sim (the reference gets it from torch autograd through
  * relax_match.py:68-98 and match_model.py:121-147; the greedy init, the masks and the early exits
  * carry no gradient).  The kernel re-runs the forward solver from the saved `sim` (same code, hence
@@ -423,6 +446,15 @@ DMM_API int dmm_match_solve_packed(const uint64_t *packed_p, const uint64_t *pac
                                    int proj_iter, float lr, int is_test, float *Rb_out, float *match_score,
                                    float *det_score, float *sim_out, float *R_out, int32_t *iters_out, void *workspace,
                                    size_t workspace_bytes, dmm_stream_t stream);
+
+/* (5c') (5c) with the assignment of (3f) in place of the relaxed solver (algo 'hun'): Rb [B,M,Pp] one-hot,
+ * match_score / det_score [B,M], sim (may be NULL), R (may be NULL), status [B] as in (3e).
+ * workspace >= dmm_workspace_bytes(B, N, M, D). */
+DMM_API int dmm_match_solve_packed_hun(const uint64_t *packed_p, const uint64_t *packed_t, const float *feat_p,
+                                       const float *feat_t, const float *score_p, int B, int N, int M, int HW, int D,
+                                       const int32_t *n_valid, const int32_t *m_valid, float score_weight, int is_test,
+                                       float *Rb_out, float *match_score, float *det_score, float *sim_out, float *R_out,
+                                       int32_t *status, void *workspace, size_t workspace_bytes, dmm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (1e) The tail of compute_matching_loss (match_helper.py:43-48) on the device, after the counts of (1b):
