@@ -52,6 +52,14 @@ def use_shipped_miopen_db(develop: bool = False, enable: bool = True):
     return dst
 
 
+def __getattr__(name):
+    # the refine decoder (decoder.py), exported lazily: importing the package stays as light as it was
+    if name in ("RSISMask", "RefineStep"):
+        from . import decoder
+        return getattr(decoder, name)
+    raise AttributeError(f"module 'dmm_net_amd' has no attribute '{name}'")
+
+
 _DB_SET_BY_US = None
 # (NOT called at import: importing the package -- e.g. only ``dmm_net_amd.match_model`` for the one-line swap -- leaves the
 # environment and ~/.cache alone.  The encoders call it when they are constructed: ``FeatureEncoder.__init__`` /

@@ -1,0 +1,293 @@
+// dmm_decoder.hip -- everything between the convolutions of the ConvLSTM refine decoder (include/dmm_match.h (12)).
+// Reference: dmm/modules/base.py:115-188 (RSISMask.forward), dmm/modules/clstm.py:80-131 (ConvLSTMCellMask.forward),
+// dmm/modules/evaluator.py:179-212 (the per-object loop of inference_timestep).
+//
+// Four streaming / pointwise kernels, fp32, plain C++: the mask pyramid (nested ceil-mode 2x2 max pools as clipped
+// 2^k windows, all levels and objects in one pass over the image-size planes), the fused LSTM cell (the three
+// evaluations of a level share one pre-activation; each mask plane's share is a 36-weight stencil per hidden channel),
+// the align-corners bilinear upsample written into a channel range of the next level's convolution input, and the
+// finish (upsample to image size, sigmoid, the valid-gated history write and the zero rows of the padded output).
+#include "dmm_common.h"
+
+#include <math.h>
+
+namespace dmm {
+
+// ---- (12a) mask pyramid ------------------------------------------------------------------------------------------
+// One workgroup = one 32 x 32 tile of one plane (video b, object t, source c): 256 lanes x one 16-byte load (rows are
+// only 4-byte aligned: float4u).  Lane l holds row l / 8, columns 4 * (l % 8) .. + 3 of the tile: its 4-wide maximum,
+// folded over the 4 rows of a 4 x 4 window by two lane exchanges (lanes l ^ 8, l ^ 16 -- one wave holds 8 rows), over
+// the 8 x 8 window by two more (l ^ 32, l ^ 1); the 16 x 16 and 32 x 32 windows combine the four waves through 16
+// floats of LDS.  Pixels outside the plane count as -inf (the clipped window of a ceil-mode pool without padding).
+__device__ __forceinline__ float fmax2(float a, float b) { return a > b ? a : b; }
+
+__global__ __launch_bounds__(256) void mask_pyramid_kernel(
+    const float *__restrict__ prev, const float *__restrict__ ymask, const float *__restrict__ init, int64_t sb_prev,
+    int64_t so_prev, int64_t sb_y, int64_t so_y, int64_t sb_i, int64_t so_i, int B, int H, int W, int tiles_x,
+    float *__restrict__ out5, float *__restrict__ out4, float *__restrict__ out3, float *__restrict__ out2) {
+    __shared__ float s8[16];
+    const int plane = blockIdx.y;                      // (t * B + b) * 3 + c : the layout of the outputs
+    const int c = plane % 3, tb = plane / 3, b = tb % B, t = tb / B;
+    const float *src = c == 0 ? prev + (int64_t)b * sb_prev + (int64_t)t * so_prev
+                     : c == 1 ? ymask + (int64_t)b * sb_y + (int64_t)t * so_y
+                              : init + (int64_t)b * sb_i + (int64_t)t * so_i;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int l = threadIdx.x;
+    const int row = ty * 32 + (l >> 3), col = tx * 32 + 4 * (l & 7);
+    const float ninf = -INFINITY;
+    float m = ninf;
+    if (row < H && col < W) {
+        const float *p = src + (int64_t)row * W + col;
+        if (col + 3 < W) {
+            const float4u v = __builtin_nontemporal_load(reinterpret_cast<const float4u *>(p));
+            m = fmax2(fmax2(v.x, v.y), fmax2(v.z, v.w));
+        } else {
+            for (int k = 0; col + k < W; ++k) m = fmax2(m, p[k]);
+        }
+    }
+    const int h2 = (H + 3) >> 2, w2 = (W + 3) >> 2, h3 = (H + 7) >> 3, w3 = (W + 7) >> 3;
+    const int h4 = (H + 15) >> 4, w4 = (W + 15) >> 4, h5 = (H + 31) >> 5, w5 = (W + 31) >> 5;
+    // 4 x 4 windows: rows l>>3 = 4r .. 4r+3 of this wave
+    m = fmax2(m, __shfl_xor(m, 8));
+    m = fmax2(m, __shfl_xor(m, 16));
+    if ((l & 24) == 0) {                               // lanes of window-row 2 * wave (l < 8) and 2 * wave + 1 (32 <= l < 40)
+        const int y = ty * 8 + (l >> 5), x = tx * 8 + (l & 7);
+        if (y < h2 && x < w2) out2[((int64_t)plane * h2 + y) * w2 + x] = m;
+    }
+    // 8 x 8 windows: the wave's two window-rows, two neighbouring columns
+    m = fmax2(m, __shfl_xor(m, 32));
+    m = fmax2(m, __shfl_xor(m, 1));
+    const int wave = l >> 6, ll = l & 63;
+    if ((ll & 57) == 0) {                              // ll in {0, 2, 4, 6}
+        const int y = ty * 4 + wave, x = tx * 4 + (ll >> 1);
+        if (y < h3 && x < w3) out3[((int64_t)plane * h3 + y) * w3 + x] = m;
+        s8[wave * 4 + (ll >> 1)] = m;
+    }
+    __syncthreads();
+    if (l < 4) {                                       // 16 x 16 windows (2 x 2 of them)
+        const int r = l >> 1, q = l & 1;
+        const float a = fmax2(fmax2(s8[(2 * r) * 4 + 2 * q], s8[(2 * r) * 4 + 2 * q + 1]),
+                              fmax2(s8[(2 * r + 1) * 4 + 2 * q], s8[(2 * r + 1) * 4 + 2 * q + 1]));
+        const int y = ty * 2 + r, x = tx * 2 + q;
+        if (y < h4 && x < w4) out4[((int64_t)plane * h4 + y) * w4 + x] = a;
+    }
+    if (l == 0) {                                      // the 32 x 32 window (the tile starts inside the plane)
+        float a = s8[0];
+#pragma unroll
+        for (int k = 1; k < 16; ++k) a = fmax2(a, s8[k]);
+        if (ty < h5 && tx < w5) out5[((int64_t)plane * h5 + ty) * w5 + tx] = a;
+    }
+}
+
+// ---- (12b) fused LSTM cell -----------------------------------------------------------------------------------------
+// A lane owns one position (b, y, x) and CH consecutive hidden channels: the 27 stencil inputs (3 planes x 3 x 3,
+// zero padded) are loaded once, the 36 weights of a channel are wave-uniform, every gate / state access is coalesced
+// over the positions.
+constexpr int kGateCh = 4;
+
+__device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__global__ __launch_bounds__(256) void clstm_gates_kernel(
+    const float *__restrict__ pre0, const float *__restrict__ pre1, const float *__restrict__ pre2, int64_t sb0, int64_t sb1,
+    int64_t sb2, const float *__restrict__ masks, int64_t sb_m, const float *__restrict__ wm, const float *__restrict__ c_prev,
+    int B, int Hd, int h, int w, float *__restrict__ hidden, float *__restrict__ cell, float *__restrict__ hidden2,
+    int64_t sb_h2) {
+    const int hw = h * w;
+    const int pos = blockIdx.x * 256 + threadIdx.x;
+    if (pos >= B * hw) return;
+    const int b = pos / hw, p = pos - b * hw, y = p / w, x = p - y * w;
+    float mk[3][9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float *mp = masks + (int64_t)b * sb_m + (int64_t)k * hw;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int yy = y + dy - 1, xx = x + dx - 1;
+                mk[k][dy * 3 + dx] = (yy >= 0 && yy < h && xx >= 0 && xx < w) ? mp[yy * w + xx] : 0.0f;
+            }
+    }
+    const int ch0 = blockIdx.y * kGateCh;
+    for (int ch = ch0; ch < ch0 + kGateCh && ch < Hd; ++ch) {
+        float g[4];                                    // in, remember, out, cell: the reference's chunk(4, 1)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int64_t off = (int64_t)(q * Hd + ch) * hw + p;
+            float v = pre0[(int64_t)b * sb0 + off];
+            if (pre1) v = v + pre1[(int64_t)b * sb1 + off];
+            if (pre2) v = v + pre2[(int64_t)b * sb2 + off];
+            g[q] = v;
+        }
+        const int64_t so = ((int64_t)b * Hd + ch) * hw + p;
+        const float cp = c_prev ? c_prev[so] : 0.0f;
+        float hk[3], ck[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            float s[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float *wq = wm + (int64_t)(q * Hd + ch) * 9;
+                float a = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 9; ++j) a = __builtin_fmaf(wq[j], mk[k][j], a);
+                s[q] = g[q] + a;
+            }
+            const float gi = sigmoid_f32(s[0]), gr = sigmoid_f32(s[1]), go = sigmoid_f32(s[2]), gc = tanhf(s[3]);
+            ck[k] = (gr * cp) + (gi * gc);
+            hk[k] = go * tanhf(ck[k]);
+        }
+        // the reference's order: prev_mask (plane 0), init_pred (plane 2), y_mask (plane 1); (a + b + c) / 3
+        const float hv = ((hk[0] + hk[2]) + hk[1]) / 3.0f;
+        const float cv = ((ck[0] + ck[2]) + ck[1]) / 3.0f;
+        hidden[so] = hv;
+        cell[so] = cv;
+        if (hidden2) hidden2[(int64_t)b * sb_h2 + (int64_t)ch * hw + p] = hv;
+    }
+}
+
+// ---- (12c) / (12d) align-corners bilinear -----------------------------------------------------------------------------
+// ATen's upsample_bilinear2d with align_corners = True: scale = (in - 1) / (out - 1) (0 for out == 1), src = scale * dst,
+// lower index by truncation, lambda1 = src - lower, lambda0 = 1 - lambda1.
+struct Lerp { int i0, step; float l0, l1; };
+__device__ __forceinline__ Lerp lerp_of(int dst, float scale, int in) {
+    const float s = scale * (float)dst;
+    Lerp r;
+    r.i0 = (int)s;
+    if (r.i0 > in - 1) r.i0 = in - 1;                  // (never taken for exact arithmetic; keeps every read in bounds)
+    r.step = r.i0 < in - 1 ? 1 : 0;
+    r.l1 = s - (float)r.i0;
+    r.l0 = 1.0f - r.l1;
+    return r;
+}
+__device__ __forceinline__ float bilerp(const float *__restrict__ p, int w, const Lerp &ly, const Lerp &lx) {
+    const float *r0 = p + (int64_t)ly.i0 * w + lx.i0, *r1 = r0 + (int64_t)ly.step * w;
+    return ly.l0 * (lx.l0 * r0[0] + lx.l1 * r0[lx.step]) + ly.l1 * (lx.l0 * r1[0] + lx.l1 * r1[lx.step]);
+}
+__host__ __device__ __forceinline__ float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f; }
+
+template <int MODE>   // 0 write, 1 add, 2 mul
+__global__ __launch_bounds__(256) void upsample_into_kernel(const float *__restrict__ src, int64_t sb_src, int C, int h, int w,
+                                                            float *__restrict__ dst, int64_t sb_dst, int c0, int H, int W,
+                                                            float sy, float sx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int X = (int)(i % W);
+    int64_t r = i / W;
+    const int Y = (int)(r % H);
+    r /= H;
+    const int c = (int)(r % C), b = (int)(r / C);
+    const float v = bilerp(src + (int64_t)b * sb_src + (int64_t)c * h * w, w, lerp_of(Y, sy, h), lerp_of(X, sx, w));
+    float *d = dst + (int64_t)b * sb_dst + ((int64_t)(c0 + c) * H + Y) * W + X;
+    if (MODE == 0) *d = v;
+    else if (MODE == 1) *d = *d + v;
+    else *d = *d * v;
+}
+
+// One lane = 4 consecutive pixels of a row of outs[b, t] (rows are 4-byte aligned: float4u stores).
+__global__ __launch_bounds__(256) void refine_finish_kernel(const float *__restrict__ logits, int64_t sb_l, int64_t so_l, int h,
+                                                            int w, const int *__restrict__ valid, int B, int O, int n_obj, int H,
+                                                            int W, int Wq, float sy, float sx, float *__restrict__ outs,
+                                                            float *__restrict__ hist, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int X = 4 * (int)(i % Wq);
+    int64_t r = i / Wq;
+    const int Y = (int)(r % H);
+    r /= H;
+    const int t = (int)(r % O), b = (int)(r / O);
+    const int64_t o = (((int64_t)b * O + t) * H + Y) * W + X;
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    const bool live = t < n_obj;
+    if (live) {
+        const float *p = logits + (int64_t)b * sb_l + (int64_t)t * so_l;
+        const Lerp ly = lerp_of(Y, sy, h);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (X + k < W) v[k] = sigmoid_f32(bilerp(p, w, ly, lerp_of(X + k, sx, w)));
+    }
+    const bool keep = live && hist && valid[b * O + t] != 0;
+    if (X + 3 < W) {
+        float4u q;
+        q.x = v[0]; q.y = v[1]; q.z = v[2]; q.w = v[3];
+        __builtin_nontemporal_store(q, reinterpret_cast<float4u *>(outs + o));
+        if (keep) __builtin_nontemporal_store(q, reinterpret_cast<float4u *>(hist + o));
+    } else {
+        for (int k = 0; X + k < W; ++k) {
+            outs[o + k] = v[k];
+            if (keep) hist[o + k] = v[k];
+        }
+    }
+}
+
+}  // namespace dmm
+
+extern "C" int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
+                                    int64_t so_prev, int64_t sb_y, int64_t so_y, int64_t sb_init, int64_t so_init, int B,
+                                    int n_obj, int H, int W, float *out5, float *out4, float *out3, float *out2,
+                                    dmm_stream_t stream) {
+    if (B < 0 || n_obj < 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || n_obj == 0) return DMM_OK;
+    if (!prev_mask || !y_mask || !init_pred || !out5 || !out4 || !out3 || !out2) return DMM_ERR_BAD_ARG;
+    if (sb_prev < 0 || so_prev < 0 || sb_y < 0 || so_y < 0 || sb_init < 0 || so_init < 0) return DMM_ERR_BAD_ARG;
+    const int tiles_x = (W + 31) / 32, tiles_y = (H + 31) / 32;
+    const int64_t planes = (int64_t)B * n_obj * 3;
+    if (planes > 65535 || (int64_t)tiles_x * tiles_y > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::mask_pyramid_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)planes), dim3(256), 0,
+                       (hipStream_t)stream, prev_mask, y_mask, init_pred, sb_prev, so_prev, sb_y, so_y, sb_init, so_init, B, H, W,
+                       tiles_x, out5, out4, out3, out2);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_clstm_gates_f32(const float *pre0, const float *pre1, const float *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                   const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                   int hidden_size, int h, int w, float *hidden, float *cell, float *hidden_copy,
+                                   int64_t sb_copy, dmm_stream_t stream) {
+    if (B < 0 || hidden_size <= 0 || h <= 0 || w <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0) return DMM_OK;
+    if (!pre0 || !masks || !w_mask || !hidden || !cell) return DMM_ERR_BAD_ARG;
+    const int64_t hw = (int64_t)h * w;
+    if (sb0 < 0 || sb1 < 0 || sb2 < 0 || sb_masks < 3 * hw || (hidden_copy && sb_copy < (int64_t)hidden_size * hw))
+        return DMM_ERR_BAD_ARG;
+    const int64_t blocks = ((int64_t)B * hw + 255) / 256, groups = (hidden_size + dmm::kGateCh - 1) / dmm::kGateCh;
+    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::clstm_gates_kernel, dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0, (hipStream_t)stream, pre0,
+                       pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, B, hidden_size, h, w, hidden, cell,
+                       hidden_copy, sb_copy);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int B, int C, int h, int w, float *dst,
+                                              int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream) {
+    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C_dst <= 0) return DMM_ERR_BAD_ARG;
+    if (c0 < 0 || c0 + C > C_dst || mode < 0 || mode > 2) return DMM_ERR_BAD_ARG;   // the channel range lies inside dst
+    if (B == 0) return DMM_OK;
+    if (!src || !dst) return DMM_ERR_BAD_ARG;
+    if (sb_src < (int64_t)C * h * w || sb_dst < (int64_t)C_dst * H * W) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * C * H * W, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    const float sy = dmm::ac_scale(h, H), sx = dmm::ac_scale(w, W);
+#define DMM_UP(MODE_)                                                                                                     \
+    hipLaunchKernelGGL((dmm::upsample_into_kernel<MODE_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src,  \
+                       sb_src, C, h, w, dst, sb_dst, c0, H, W, sy, sx, n)
+    if (mode == 0) DMM_UP(0);
+    else if (mode == 1) DMM_UP(1);
+    else DMM_UP(2);
+#undef DMM_UP
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
+                                     int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist,
+                                     dmm_stream_t stream) {
+    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || O == 0) return DMM_OK;
+    if (!outs || (n_obj > 0 && !logits) || (mask_hist && !valid)) return DMM_ERR_BAD_ARG;
+    if (sb_logits < 0 || so_logits < 0) return DMM_ERR_BAD_ARG;
+    const int Wq = (W + 3) / 4;
+    const int64_t n = (int64_t)B * O * H * Wq, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::refine_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, sb_logits,
+                       so_logits, h, w, valid, B, O, n_obj, H, W, Wq, dmm::ac_scale(h, H), dmm::ac_scale(w, W), outs, mask_hist, n);
+    return dmm::check_launch();
+}

@@ -1,0 +1,525 @@
+"""The recurrent refine decoder of DMM-Net and its per-frame driver.
+
+Counterparts in the reference:
+
+* ``RSISMask``  -- ``dmm/modules/base.py:71-188`` with the cells of ``dmm/modules/clstm.py:68-131`` (``ConvLSTMCellMask``):
+  same constructor attributes, the same parameter names and shapes (``clstm_list.{0..3}.Gates.{weight,bias}``,
+  ``conv_out.{weight,bias}``: a reference checkpoint's decoder ``state_dict`` loads with ``strict=True``), the same
+  ``forward(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal) -> (out_mask, hidden_list)``.
+* ``RefineStep``  -- the object loop of ``Evaler.inference_timestep`` (``dmm/modules/evaluator.py:179-212``) behind the
+  ``refine`` contract of ``video.FrameLoop``.
+
+Two execution forms behind the one ``forward``:
+
+* the STOCK form: the reference's arithmetic op for op in torch.  Runs wherever torch runs and under autograd; taken when
+  gradients are required, in ``train()`` mode with ``dropout > 0``, for ``kernel_size == 1``, ``prev_mask_d != 1``,
+  non-fp32 or CPU tensors.  Training through the decoder works this way and is not accelerated.
+* the FUSED form (HIP tensors, fp32, no grad, 3x3): the three cell evaluations of a level get the same input, the same
+  spatial state and the same temporal hidden and differ in the one-channel mask plane only; a convolution is linear in
+  its input channels, so
+
+      Gates(cat[x, m_k, h_s, h_t]) = [W_x * x + W_hs * h_s + W_ht * h_t + b] + W_m * m_k          (k = 0, 2, 1)
+
+  The bracket is ONE convolution per level instead of three; ``W_m * m_k`` is a 36-weight stencil per hidden channel and
+  lives in the pointwise kernel (``dmm_clstm_gates_f32``) with the gate non-linearities, the state update and the mean
+  over k.  Of the bracket, the skip map's share of ``W_x * x`` is the same for every object of a frame (computed once per
+  frame by ``RefineStep``), the ``W_ht * h_t`` share does not depend on the object chain (one batched convolution for all
+  objects); only ``W_hs * h_s`` and the share of the upsampled hidden of the level above are computed per object.  The
+  convolutions stay on the library (``F.conv2d`` -> MIOpen); what lies between them is ``csrc/dmm_decoder.hip``.  A
+  reordering of fp32 sums, not an approximation.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _lib
+
+_SKIP_MODES = ("concat", "sum", "mul", "none")
+_UP_MODE = {"write": 0, "add": 1, "mul": 2}
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# launchers of csrc/dmm_decoder.hip (tensor in, tensor out; the module and the tests share them)
+# ------------------------------------------------------------------------------------------------------------------
+def _need_device(t: torch.Tensor):
+    if not t.is_cuda:
+        raise _lib.DmmError("the fused decoder kernels need tensors on an MI355X device (the stock form runs on the CPU)")
+
+
+def _stream(t: torch.Tensor):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def _plane_strides(t: torch.Tensor, H: int, W: int):
+    """[B, O, H*W] or [B, O, H, W] fp32 with dense planes -> (tensor, batch stride, object stride)."""
+    assert t.dtype == torch.float32 and t.dim() in (3, 4), (t.shape, t.dtype)
+    dense = t.stride(-1) == 1 and (t.dim() == 3 or t.stride(2) == W)
+    if not dense:
+        t = t.contiguous()
+    return t, t.stride(0), t.stride(1)
+
+
+def pyramid_sizes(H: int, W: int):
+    """Sizes after 5, 4, 3, 2 nested ceil-mode 2x2 pools: coarsest first, the order of ``refine_input_feat``."""
+    return [(-(-H // (1 << k)), -(-W // (1 << k))) for k in (5, 4, 3, 2)]
+
+
+def mask_pyramid(prev_mask, y_mask, init_pred, n_obj: int, H: int, W: int, out: Optional[Sequence[torch.Tensor]] = None):
+    """evaluator.py:188-195 for objects 0..n_obj-1 in one launch -> 4 tensors [n_obj, B, 3, h_l, w_l], coarsest first."""
+    _need_device(prev_mask)
+    prev_mask, sbp, sop = _plane_strides(prev_mask, H, W)
+    y_mask, sby, soy = _plane_strides(y_mask, H, W)
+    init_pred, sbi, soi = _plane_strides(init_pred, H, W)
+    B = prev_mask.shape[0]
+    assert n_obj <= min(prev_mask.shape[1], y_mask.shape[1], init_pred.shape[1])
+    if out is None:
+        out = [torch.empty((n_obj, B, 3, h, w), dtype=torch.float32, device=prev_mask.device) for h, w in pyramid_sizes(H, W)]
+    _lib.call("dmm_mask_pyramid_f32", prev_mask.device, prev_mask.data_ptr(), y_mask.data_ptr(), init_pred.data_ptr(),
+              sbp, sop, sby, soy, sbi, soi, B, n_obj, H, W, *[o.data_ptr() for o in out], _stream(prev_mask))
+    return list(out)
+
+
+def _dense_batch(t: torch.Tensor):
+    """[B, C, h, w] with dense [C, h, w] samples -> (tensor, batch stride)."""
+    C, h, w = t.shape[1:]
+    if not (t.stride(3) == 1 and t.stride(2) == w and t.stride(1) == h * w):
+        t = t.contiguous()
+    return t, (t.stride(0) if t.shape[0] > 1 else C * h * w)
+
+
+def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev, hidden, cell, hidden_copy=None):
+    """``dmm_clstm_gates_f32``: pre = up to three addends [B, 4*Hd, h, w]; masks [B, 3, h, w]; w_mask [4*Hd, 9]; cell_prev
+    [B, Hd, h, w] or None; writes ``hidden`` / ``cell`` (dense) and, when given, ``hidden_copy`` (a channel slice of the
+    next evaluation's convolution input)."""
+    _need_device(masks)
+    pre = [p for p in pre if p is not None]
+    assert 1 <= len(pre) <= 3
+    B, Hd, h, w = hidden.shape
+    ptrs, strides = [], []
+    keep = []
+    for p in pre:
+        assert tuple(p.shape) == (B, 4 * Hd, h, w) and p.dtype == torch.float32, (p.shape, hidden.shape)
+        p, sb = _dense_batch(p)
+        keep.append(p)
+        ptrs.append(p.data_ptr())
+        strides.append(sb)
+    ptrs += [None] * (3 - len(ptrs))
+    strides += [0] * (3 - len(strides))
+    masks, sbm = _dense_batch(masks)
+    assert tuple(masks.shape) == (B, 3, h, w) and w_mask.is_contiguous() and tuple(w_mask.shape) == (4 * Hd, 9)
+    assert hidden.is_contiguous() and cell.is_contiguous() and tuple(cell.shape) == (B, Hd, h, w)
+    if cell_prev is not None:
+        cell_prev = cell_prev.contiguous()
+        assert tuple(cell_prev.shape) == (B, Hd, h, w)
+    sbc = 0
+    if hidden_copy is not None:
+        assert tuple(hidden_copy.shape) == (B, Hd, h, w) and hidden_copy.stride(3) == 1 and hidden_copy.stride(2) == w \
+            and hidden_copy.stride(1) == h * w
+        sbc = hidden_copy.stride(0) if B > 1 else max(hidden_copy.stride(0), Hd * h * w)
+    _lib.call("dmm_clstm_gates_f32", masks.device, *ptrs, *strides, masks.data_ptr(), sbm, w_mask.data_ptr(),
+              None if cell_prev is None else cell_prev.data_ptr(), B, Hd, h, w, hidden.data_ptr(), cell.data_ptr(),
+              None if hidden_copy is None else hidden_copy.data_ptr(), sbc, _stream(masks))
+    return hidden, cell
+
+
+def upsample_bilinear_into(src, dst, c0: int = 0, mode: str = "write"):
+    """``dmm_upsample_bilinear_into_f32``: UpsamplingBilinear2d(src [B,C,h,w]) to dst's size, combined into
+    dst[:, c0:c0+C] ([B, C', H, W] dense) by ``mode`` ('write' | 'add' | 'mul')."""
+    _need_device(src)
+    src, sbs = _dense_batch(src)
+    B, C, h, w = src.shape
+    Bd, Cd, H, W = dst.shape
+    assert Bd == B and dst.dtype == src.dtype == torch.float32 and dst.stride(3) == 1 and dst.stride(2) == W and \
+        dst.stride(1) == H * W, (src.shape, dst.shape, dst.stride())
+    sbd = dst.stride(0) if B > 1 else max(dst.stride(0), Cd * H * W)
+    _lib.call("dmm_upsample_bilinear_into_f32", src.device, src.data_ptr(), sbs, B, C, h, w, dst.data_ptr(), sbd, Cd, int(c0),
+              H, W, _UP_MODE[mode], _stream(src))
+    return dst
+
+
+def refine_finish(logits, valid_i32, outs, mask_hist, n_obj: int):
+    """``dmm_refine_finish_f32``: logits [B, n_obj, h, w] (any batch / object strides, dense planes) -> outs [B,O,H,W]
+    (sigmoid of the upsampled logits, zero rows beyond n_obj) and mask_hist[b, t] where valid_i32[b, t]."""
+    _need_device(outs)
+    B, O, H, W = outs.shape
+    assert outs.is_contiguous() and outs.dtype == torch.float32
+    assert mask_hist is None or (mask_hist.is_contiguous() and tuple(mask_hist.shape) == (B, O, H, W) and
+                                 mask_hist.dtype == torch.float32)
+    assert valid_i32 is None or (valid_i32.dtype == torch.int32 and valid_i32.is_contiguous() and
+                                 tuple(valid_i32.shape) == (B, O))
+    h, w = logits.shape[-2:]
+    assert logits.shape[0] == B and logits.shape[1] >= n_obj and logits.stride(3) == 1 and logits.stride(2) == w
+    _lib.call("dmm_refine_finish_f32", outs.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w,
+              None if valid_i32 is None else valid_i32.data_ptr(), B, O, int(n_obj), H, W, outs.data_ptr(),
+              None if mask_hist is None else mask_hist.data_ptr(), _stream(outs))
+    return outs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the module
+# ------------------------------------------------------------------------------------------------------------------
+class ConvLSTMCellMask(nn.Module):
+    """clstm.py:68-131: one ``Gates`` convolution over cat[input, prev_mask, hidden_spatial, hidden_temporal]."""
+
+    def __init__(self, args, input_size: int, hidden_size: int, kernel_size: int, padding: int):
+        super().__init__()
+        self.input_size, self.hidden_size = int(input_size), int(hidden_size)
+        self.Gates = nn.Conv2d(self.input_size + 2 * self.hidden_size + int(args.prev_mask_d), 4 * self.hidden_size,
+                               kernel_size, padding=padding)
+
+    def forward(self, input_, prev_mask, prev_state_spatial, hidden_state_temporal):
+        B = input_.shape[0]
+        size = (B, self.hidden_size) + tuple(input_.shape[2:])
+        if prev_state_spatial is None:
+            prev_state_spatial = (input_.new_zeros(size), input_.new_zeros(size))
+        if hidden_state_temporal is None:
+            hidden_state_temporal = input_.new_zeros(size)
+        h_s, c_s = prev_state_spatial
+        gates = self.Gates(torch.cat([input_, prev_mask, h_s, hidden_state_temporal], 1))
+        i, r, o, g = gates.chunk(4, 1)
+        i, r, o, g = torch.sigmoid(i), torch.sigmoid(r), torch.sigmoid(o), torch.tanh(g)
+        cell = (r * c_s) + (i * g)
+        return [o * torch.tanh(cell), cell]
+
+
+class RSISMask(nn.Module):
+    """The recurrent decoder (base.py:71-188).  ``args``: hidden_size, kernel_size, dropout, skip_mode, prev_mask_d
+    (``use_gpu`` is accepted and ignored: states are allocated on the input's device)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.hidden_size = args.hidden_size
+        self.kernel_size = args.kernel_size
+        self.dropout = args.dropout
+        self.skip_mode = args.skip_mode
+        self.prev_mask_d = int(getattr(args, "prev_mask_d", 1))
+        padding = 0 if self.kernel_size == 1 else 1
+        hs = int(self.hidden_size)
+        self.skip_dims_out = [hs, int(hs / 2), int(hs / 4), int(hs / 8)]
+        self.clstm_list = nn.ModuleList()
+        for i, out_dim in enumerate(self.skip_dims_out):
+            in_dim = hs if i == 0 else self.skip_dims_out[i - 1] * (2 if self.skip_mode == "concat" else 1)
+            self.clstm_list.append(ConvLSTMCellMask(args, in_dim, out_dim, self.kernel_size, padding))
+        self.conv_out = nn.Conv2d(self.skip_dims_out[-1], 1, self.kernel_size, padding=padding)
+        self.fused = True                    # False: always the stock form (A/B timing, tests)
+        self._slices = None                  # (key, per-level weight slices) of the fused form
+        self.conv_calls = 0                  # convolutions issued by the fused form (diagnostic, like dmm_launch_count)
+
+    # ---- dispatch ------------------------------------------------------------------------------------------------
+    def fused_ok(self, tensors: Sequence[torch.Tensor]) -> bool:
+        """Does the fused form cover this call?  (Anything else is the stock form -- same results, torch ops.)"""
+        if not self.fused or self.skip_mode not in _SKIP_MODES or int(self.kernel_size) != 3 or self.prev_mask_d != 1:
+            return False
+        if self.training and self.dropout > 0:
+            return False
+        params = list(self.parameters())
+        if torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + params):
+            return False
+        return all(t.is_cuda and t.dtype == torch.float32 for t in list(tensors) + params)
+
+    def forward(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
+        ts = list(skip_feats) + list(prev_mask_list)
+        if prev_state_spatial is not None:
+            ts += [t for st in prev_state_spatial for t in st]
+        if prev_hidden_temporal is not None:
+            ts += list(prev_hidden_temporal)
+        if self.fused_ok(ts):
+            return self._forward_fused(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
+        return self.forward_stock(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
+
+    # ---- stock form: base.py:115-188 op for op ----------------------------------------------------------------------
+    def forward_stock(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
+        clstm_in = skip_feats[0]
+        skips = skip_feats[1:]
+        hidden_list = []
+        for i, cell in enumerate(self.clstm_list):
+            m = prev_mask_list[i]
+            st = None if prev_state_spatial is None else prev_state_spatial[i]
+            ht = None if prev_hidden_temporal is None else prev_hidden_temporal[i]
+            a = cell(clstm_in, m[:, 0:1], st, ht)                 # prev_mask
+            b = cell(clstm_in, m[:, 2:], st, ht)                  # init_pred
+            c = cell(clstm_in, m[:, 1:2], st, ht)                 # y_mask
+            state = [(a[0] + b[0] + c[0]) / 3, (a[1] + b[1] + c[1]) / 3]
+            hidden_list.append(state)
+            hidden = state[0]
+            if self.dropout > 0:
+                hidden = F.dropout2d(hidden, self.dropout, training=self.training)
+            if i < len(skips):
+                skip = skips[i]
+                hidden = F.interpolate(hidden, size=tuple(skip.shape[-2:]), mode="bilinear", align_corners=True)
+                if self.skip_mode == "concat":
+                    clstm_in = torch.cat([hidden, skip], 1)
+                elif self.skip_mode == "sum":
+                    clstm_in = hidden + skip
+                elif self.skip_mode == "mul":
+                    clstm_in = hidden * skip
+                elif self.skip_mode == "none":
+                    clstm_in = hidden
+                else:
+                    raise Exception("Skip connection mode not supported !")
+            else:
+                clstm_in = F.interpolate(hidden, size=(hidden.shape[-2] * 2, hidden.shape[-1] * 2), mode="bilinear",
+                                         align_corners=True)
+        return self.conv_out(clstm_in), hidden_list
+
+    # ---- fused form ------------------------------------------------------------------------------------------------------
+    def weight_slices(self):
+        """Per level the contiguous slices of ``Gates.weight`` ([4*Hd, Cin + 1 + 2*Hd, 3, 3], input channels in the order
+        x, mask, h_s, h_t): ``up`` = the share of the upsampled hidden of the level above (levels >= 1), ``skip`` = the skip
+        map's share (all of x at level 0; levels >= 1: the second half under 'concat', all of x under 'sum', none under
+        'mul' / 'none'), ``m`` [4*Hd, 9], ``hs``, ``ht``, ``cat`` = [up | hs] (one chain convolution).  Made once and kept
+        against the parameters' versions and storages."""
+        key = tuple((p.data_ptr(), p._version, p.device) for p in self.parameters())
+        if self._slices is not None and self._slices[0] == key:
+            return self._slices[1]
+        out = []
+        with torch.no_grad():
+            for i, cell in enumerate(self.clstm_list):
+                Wt, Hd = cell.Gates.weight, cell.hidden_size
+                cin = cell.input_size
+                x, m = Wt[:, :cin], Wt[:, cin:cin + 1]
+                hs, ht = Wt[:, cin + 1:cin + 1 + Hd], Wt[:, cin + 1 + Hd:]
+                d = {"m": m.reshape(4 * Hd, 9).contiguous(), "hs": hs.contiguous(), "ht": ht.contiguous(),
+                     "bias": cell.Gates.bias.detach(), "up": None, "skip": None, "cat": None}
+                if i == 0:
+                    d["skip"] = x.contiguous()
+                else:
+                    cup = self.skip_dims_out[i - 1]
+                    d["up"] = x[:, :cup].contiguous()
+                    if self.skip_mode == "concat":
+                        d["skip"] = x[:, cup:].contiguous()
+                    elif self.skip_mode == "sum":
+                        d["skip"] = d["up"]
+                    d["cat"] = torch.cat([d["up"], d["hs"]], 1).contiguous()
+                out.append(d)
+        self._slices = (key, out)
+        return out
+
+    def _conv(self, x, w, b=None):
+        self.conv_calls += 1
+        return F.conv2d(x, w, b, padding=1)
+
+    def skip_terms(self, skip_feats):
+        """The object-independent share of every level's pre-activation: conv(skip map, W_skip) + bias (None where the
+        level has no such term: 'mul' / 'none' above level 0).  Once per frame."""
+        sl = self.weight_slices()
+        return [None if d["skip"] is None else self._conv(f, d["skip"], d["bias"]) for d, f in zip(sl, skip_feats)]
+
+    def temporal_terms(self, hidden_temporal):
+        """conv(h_t, W_ht) per level; ``hidden_temporal[i]`` may stack every object of the frame along the batch."""
+        sl = self.weight_slices()
+        return [self._conv(h, d["ht"]) for d, h in zip(sl, hidden_temporal)]
+
+    def _level(self, i, d, bufs, skip_term, temporal_term, skip, masks, state_spatial, hidden, cell, up_src):
+        """One level of one object: the chain convolution + the gate launch.  ``up_src``: the hidden of the level above
+        (None at level 0); ``bufs``: this level's scratch ('cat' [B, Cup + Hd, h, w] whose upper channels hold the previous
+        object's hidden of this level, 'up' [B, Cup, h, w])."""
+        chain = None
+        bias_in_chain = None if skip_term is not None else d["bias"]
+        if i == 0:
+            if state_spatial is not None:
+                chain = self._conv(state_spatial[0], d["hs"])
+        else:
+            cup = self.skip_dims_out[i - 1]
+            if state_spatial is None:
+                dst, wgt = bufs["up"], d["up"]
+            else:
+                dst, wgt = bufs["cat"], d["cat"]
+                if state_spatial[0].data_ptr() != dst[:, cup:].data_ptr() and not bufs.get("cat_holds_state"):
+                    dst[:, cup:].copy_(state_spatial[0])
+            if self.skip_mode == "mul":
+                dst[:, :cup].copy_(skip)
+                upsample_bilinear_into(up_src, dst, 0, "mul")
+            else:
+                upsample_bilinear_into(up_src, dst, 0, "write")
+            chain = self._conv(dst, wgt, bias_in_chain)
+        pre = [skip_term, temporal_term, chain]
+        cell_prev = None if state_spatial is None else state_spatial[1]
+        clstm_gates(pre, masks, d["m"], cell_prev, hidden, cell, bufs.get("next_copy"))
+        return hidden, cell
+
+    def _forward_fused(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
+        sl = self.weight_slices()
+        skip_terms = self.skip_terms(skip_feats)
+        temporal = [None] * 4 if prev_hidden_temporal is None else self.temporal_terms(prev_hidden_temporal)
+        hidden_list, up_src = [], None
+        for i, d in enumerate(sl):
+            f = skip_feats[i]
+            B, (h, w) = f.shape[0], f.shape[-2:]
+            Hd = self.skip_dims_out[i]
+            bufs = {}
+            if i > 0:
+                cup = self.skip_dims_out[i - 1]
+                if prev_state_spatial is None:
+                    bufs["up"] = f.new_empty((B, cup, h, w))
+                else:
+                    bufs["cat"] = f.new_empty((B, cup + Hd, h, w))
+            hidden, cell = f.new_empty((B, Hd, h, w)), f.new_empty((B, Hd, h, w))
+            st = None if prev_state_spatial is None else prev_state_spatial[i]
+            self._level(i, d, bufs, skip_terms[i], temporal[i], f, prev_mask_list[i], st, hidden, cell, up_src)
+            hidden_list.append([hidden, cell])
+            up_src = hidden
+        h, w = up_src.shape[-2:]
+        top = up_src.new_empty((up_src.shape[0], self.skip_dims_out[-1], 2 * h, 2 * w))
+        upsample_bilinear_into(up_src, top, 0, "write")
+        return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# the per-frame driver
+# ------------------------------------------------------------------------------------------------------------------
+class RefineState:
+    """What ``RefineStep`` carries from frame to frame: ``n_obj`` (valid_num_obj_max, read from ``valid`` once per clip)
+    and ``thid`` = per object the list of per-level temporal hiddens (the reference's prev_thid_list; None before the first
+    frame has run, and for ever under ``only_spatial``).  In the fused form the hiddens are views of the step's own
+    buffers: they are rewritten in place by the next frame (after their temporal convolutions have been taken)."""
+
+    def __init__(self, n_obj: int, thid=None):
+        self.n_obj, self.thid = int(n_obj), thid
+
+    def __len__(self):
+        return 0 if self.thid is None else len(self.thid)
+
+    def __getitem__(self, t):
+        return self.thid[t]
+
+
+class RefineStep:
+    """``refine(features, prev_mask, y_mask, init_pred, mask_hist_new, valid, state) -> (outs, mask_hist_new, state)`` for
+    ``video.FrameLoop``: evaluator.py:179-212.  ``prev_mask`` / ``y_mask`` [B,O,HW], ``init_pred`` / ``mask_hist_new``
+    [B,O,H,W], ``valid`` [B,O]; ``outs`` [B,O,HW], zero for objects >= valid_num_obj_max; ``mask_hist_new[b, t]`` is
+    written only where ``valid[b, t]``.
+
+    Fused form (the decoder's ``fused_ok``): one pyramid launch, the hoisted skip convolutions, one batched temporal
+    convolution per level, per object and level one chain convolution + one gate launch + one upsample launch, one
+    upsample + ``conv_out`` for all objects, one finish launch.  ``valid_num_obj_max`` is read when ``state is None``
+    (frame 0 of a clip) and kept in the state: afterwards no host sync, and every buffer is kept by shape, so the step can
+    be captured into a graph and replayed.  ``mask_hist_new`` is then updated in place (FrameLoop hands over a tensor of
+    its own for that)."""
+
+    def __init__(self, decoder: RSISMask, only_spatial: bool = False, only_temporal: bool = False):
+        self.decoder, self.only_spatial, self.only_temporal = decoder, bool(only_spatial), bool(only_temporal)
+        self._bufs = {}
+
+    def __call__(self, features, prev_mask, y_mask, init_pred, mask_hist_new, valid, state):
+        low = (torch.float16, torch.bfloat16)                    # a bf16 encoder's maps: the decoder's arithmetic is fp32
+        feats = [f.float() if f.dtype in low else f for f in features["refine_input_feat"]]
+        B, O = init_pred.shape[:2]
+        H, W = init_pred.shape[-2:]
+        if state is None:
+            # valid_num_obj_max (evaluator.py:179): the clip's one host read of the decoder
+            state = RefineState(max(1, int((valid.sum(0) > 0).sum())))
+        n_obj = min(state.n_obj, O)
+        init_pred = init_pred.float() if init_pred.dtype in low else init_pred
+        ts = feats + [prev_mask, y_mask, init_pred, mask_hist_new]
+        if self.decoder.fused_ok(ts):
+            return self._fused(feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W)
+        return self._stock(feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W)
+
+    # ---- evaluator.py:179-212 in torch -----------------------------------------------------------------------------------
+    def _stock(self, feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W):
+        dec = self.decoder
+        prev_thid = state.thid
+        hidden_spatial, thid, logits = None, [], []
+        pool = lambda x: F.max_pool2d(x, (2, 2), ceil_mode=True)
+        for t in range(n_obj):
+            hidden_temporal = None
+            if prev_thid is not None:
+                hidden_temporal = prev_thid[t]
+                if self.only_temporal:
+                    hidden_spatial = None
+            m = torch.stack([prev_mask[:, t].reshape(B, H, W), y_mask[:, t].reshape(B, H, W),
+                             init_pred[:, t].reshape(B, H, W)], 1).to(feats[0].dtype)
+            m = pool(m)
+            pyr = []
+            for _ in range(len(feats)):
+                m = pool(m)
+                pyr.append(m)
+            out_mask, hidden = dec.forward_stock(feats, pyr[::-1], hidden_spatial, hidden_temporal)
+            hidden_spatial = hidden
+            thid.append([hc[0] for hc in hidden])
+            up = F.interpolate(out_mask, size=(H, W), mode="bilinear", align_corners=True)
+            for b in range(B):
+                # (:202-205 video by video, as the reference evaluates it; the gate stays on the device)
+                mask_hist_new[b, t:t + 1] = torch.where(valid[b, t] != 0, torch.sigmoid(up[b]).to(mask_hist_new.dtype),
+                                                        mask_hist_new[b, t:t + 1])
+            logits.append(up)
+        probs = torch.sigmoid(torch.cat(logits, 1))                             # [B, n_obj, H, W]
+        outs = probs.new_zeros((B, O, H * W))
+        outs[:, :n_obj] = probs.view(B, n_obj, H * W)
+        return outs, mask_hist_new, RefineState(state.n_obj, prev_thid if self.only_spatial else thid)
+
+    # ---- the fused step ----------------------------------------------------------------------------------------------------
+    def _buffers(self, feats, n_obj, B, O, H, W):
+        dec = self.decoder
+        dev = feats[0].device
+        key = (dev, n_obj, B, O, H, W, dec.skip_mode, tuple(tuple(f.shape) for f in feats))
+        b = self._bufs.get(key)
+        if b is not None:
+            return b
+        sizes = pyramid_sizes(H, W)
+        for f, s in zip(feats, sizes):
+            assert tuple(f.shape[-2:]) == s, ("refine_input_feat does not sit on the mask pyramid", f.shape, s)
+        new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        dims = dec.skip_dims_out
+        h3, w3 = sizes[-1]
+        b = {"pyr": [new(n_obj, B, 3, h, w) for h, w in sizes],
+             # hidden / cell of every object and level: the spatial chain of this frame, the temporal state of the next
+             "hid": [new(n_obj, B, dims[i], *sizes[i]) for i in range(4)],
+             "cell": [new(n_obj, B, dims[i], *sizes[i]) for i in range(4)],
+             "cat": [None] + [new(B, dims[i - 1] + dims[i], *sizes[i]) for i in range(1, 4)],
+             "up": [None] + [new(B, dims[i - 1], *sizes[i]) for i in range(1, 4)],
+             "top": new(n_obj * B, dims[-1], 2 * h3, 2 * w3),
+             "outs": new(B, O, H, W), "valid": torch.zeros((B, O), dtype=torch.int32, device=dev)}
+        self._bufs[key] = b
+        return b
+
+    def _fused(self, feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W):
+        dec = self.decoder
+        bufs = self._buffers(feats, n_obj, B, O, H, W)
+        sl = dec.weight_slices()
+        dims = dec.skip_dims_out
+        if not mask_hist_new.is_contiguous():
+            mask_hist_new = mask_hist_new.contiguous()
+        bufs["valid"].copy_(valid)
+        mask_pyramid(prev_mask, y_mask, init_pred, n_obj, H, W, out=bufs["pyr"])
+        skip_terms = dec.skip_terms(feats)
+        # the temporal terms read last frame's hiddens from the very buffers this frame's object loop overwrites: taken
+        # for every object and level BEFORE the loop (one batched convolution per level)
+        have_t = state.thid is not None
+        temporal = None
+        if have_t:
+            temporal = dec.temporal_terms([bufs["hid"][i].view(n_obj * B, dims[i], *bufs["hid"][i].shape[-2:])
+                                           for i in range(4)])
+        spatial = None                                            # [(hidden, cell)] per level of the previous object
+        for t in range(n_obj):
+            if have_t and self.only_temporal:
+                spatial = None
+            up_src, cur = None, []
+            for i, d in enumerate(sl):
+                hidden, cell = bufs["hid"][i][t], bufs["cell"][i][t]
+                lb = {"cat_holds_state": True}
+                if i > 0:
+                    lb["cat"], lb["up"] = bufs["cat"][i], bufs["up"][i]
+                    # this object's hidden goes, besides its own slot, into the next object's convolution input
+                    if t + 1 < n_obj and not (have_t and self.only_temporal):
+                        lb["next_copy"] = bufs["cat"][i][:, dims[i - 1]:]
+                tt = None if temporal is None else temporal[i][t * B:(t + 1) * B]
+                dec._level(i, d, lb, skip_terms[i], tt, feats[i], bufs["pyr"][i][t], None if spatial is None else spatial[i],
+                           hidden, cell, up_src)
+                cur.append((hidden, cell))
+                up_src = hidden
+            spatial = cur
+        upsample_bilinear_into(bufs["hid"][3].view(n_obj * B, dims[3], *bufs["hid"][3].shape[-2:]), bufs["top"], 0, "write")
+        logits = dec._conv(bufs["top"], dec.conv_out.weight, dec.conv_out.bias)    # [n_obj * B, 1, 2h, 2w]
+        logits = logits.view(n_obj, B, *logits.shape[-2:]).transpose(0, 1)          # [B, n_obj, 2h, 2w] (strided view)
+        refine_finish(logits, bufs["valid"], bufs["outs"], mask_hist_new, n_obj)
+        if self.only_spatial:
+            thid = state.thid
+        else:
+            thid = [[bufs["hid"][i][t] for i in range(4)] for t in range(n_obj)]
+        return bufs["outs"].view(B, O, H * W), mask_hist_new, RefineState(state.n_obj, thid)

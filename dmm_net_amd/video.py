@@ -16,7 +16,7 @@ Counterparts in the reference:
   without importing maskrcnn_benchmark.
 * ``FrameLoop``  -- the frame loop of ``Evaler.forward`` / ``inference_timestep`` (``evaluator.py:63-213``) with every
   video of the batch in one ragged launch per frame and ``mask_hist`` resident on the device.  The decoder
-  (ConvLSTM refinement, out of scope for this package) is injected as ``refine``.
+  (ConvLSTM refinement) is injected as ``refine``: ``decoder.RefineStep(decoder.RSISMask(args))``.
 
 Nothing here has a CPU implementation of the device work: CPU tensors raise ``DmmError``.
 """

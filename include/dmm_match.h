@@ -802,6 +802,49 @@ DMM_API int dmm_wgrad3x3_bf16(const void *dy, const void *x, int B, int H, int W
  * ------------------------------------------------------------------------------------------- */
 DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, int *n_memcpy, int *n_left);
 
+/* ---------------------------------------------------------------------------------------------
+ * (12) The ConvLSTM refine decoder (dmm/modules/base.py:71-188 RSISMask, dmm/modules/clstm.py:68-131 ConvLSTMCellMask, driven
+ * per object by dmm/modules/evaluator.py:179-212): everything BETWEEN its convolutions.  fp32, dense planes (row stride =
+ * width, channel stride = plane), batch / object strides in elements; nothing allocates, no memset nodes.  Used by
+ * dmm_net_amd/decoder.py, which keeps the convolutions on the library.
+ *
+ * (12a) dmm_mask_pyramid_f32 -- evaluator.py:188-195: MaxPool2d((2,2), ceil_mode=True) applied 5, 4, 3 and 2 times to the planes
+ *   prev_mask[b, t], y_mask[b, t], init_pred[b, t] (each H x W at base + b * sb + t * so), b < B, t < n_obj, in ONE launch and
+ *   without the reference's cat.  k nested ceil-mode pools = the maximum over the clipped 2^k x 2^k window, size ceil(H / 2^k):
+ *   bit exact.  out_k: [n_obj, B, 3, ceil(H / 2^k), ceil(W / 2^k)] dense, plane order (prev_mask, y_mask, init_pred) -- object
+ *   t's slice is the [B, 3, h, w] entry of the reference's mask_lstm.  B * n_obj * 3 <= 65535.
+ *
+ * (12b) dmm_clstm_gates_f32 -- clstm.py:112-129 for the three cell evaluations of a level (base.py:134-153), which differ in
+ *   the one-channel mask plane only:  gates_k = (pre0 + pre1 + pre2) + stencil3x3(w_mask, m_k), k = plane 0, 2, 1 (prev_mask,
+ *   init_pred, y_mask: base.py:116-118, 134-150); gate order in / remember / out / cell (chunk(4, 1)); cell_k = sigmoid(remember)
+ *   * cell_prev + sigmoid(in) * tanh(cellgate), hidden_k = sigmoid(out) * tanh(cell_k); hidden = (h_0 + h_2 + h_1) / 3, cell
+ *   likewise (base.py:152-153).  pre0..2: the shared pre-activation [B, 4 * hidden_size, h, w] as up to three addends (batch
+ *   strides sb0..2; pre1 / pre2 may be null); masks [B, 3, h, w] (batch stride sb_masks); w_mask [4 * hidden_size, 9] = the mask
+ *   channel of Gates.weight; cell_prev [B, hidden_size, h, w] dense or null (= zeros, the reference's None state); hidden /
+ *   cell [B, hidden_size, h, w] dense; hidden_copy (may be null; batch stride sb_copy): a second copy of hidden, written into
+ *   the convolution input of the next object's evaluation of this level.
+ *
+ * (12c) dmm_upsample_bilinear_into_f32 -- base.py:165-175, 179-181: UpsamplingBilinear2d (align_corners = True, coordinates
+ *   and weights as ATen computes them) of src [B, C, h, w] to H x W, combined into channels c0 .. c0 + C of dst [B, C_dst, H, W]
+ *   by mode 0 = write (skip modes 'concat' / 'none'), 1 = add ('sum'), 2 = multiply ('mul').
+ *
+ * (12d) dmm_refine_finish_f32 -- evaluator.py:200-212 for every object of the frame in one launch: logits[b, t] (h x w at base +
+ *   b * sb_logits + t * so_logits, conv_out's output) -> bilinear (align_corners = True) to H x W -> sigmoid -> outs[b, t]; the
+ *   same value into mask_hist[b, t] where valid[b * O + t] != 0 (int32, read on the device; mask_hist may be null); rows
+ *   n_obj <= t < O of outs are zeroed.  outs / mask_hist [B, O, H, W] dense.
+ * ------------------------------------------------------------------------------------------- */
+DMM_API int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
+                                 int64_t so_prev, int64_t sb_y, int64_t so_y, int64_t sb_init, int64_t so_init, int B, int n_obj,
+                                 int H, int W, float *out5, float *out4, float *out3, float *out2, dmm_stream_t stream);
+DMM_API int dmm_clstm_gates_f32(const float *pre0, const float *pre1, const float *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                int hidden_size, int h, int w, float *hidden, float *cell, float *hidden_copy, int64_t sb_copy,
+                                dmm_stream_t stream);
+DMM_API int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int B, int C, int h, int w, float *dst,
+                                           int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream);
+DMM_API int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
+                                  int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist, dmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
