@@ -1,23 +1,15 @@
-// dmm_api.hip -- C-ABI glue of libdmm_match.so: status/reporting and the fused forward entry point
-// that chains the four kernels of MatchModel.forward (dmm/modules/match_model.py:24-47) on one stream.
+// dmm_api.hip -- C-ABI glue of libdmm_match.so: status/reporting and the one-call forward entries that chain the
+// kernels of MatchModel.forward (dmm/modules/match_model.py:24-47) on one stream: validate, carve the workspace, front
+// (similarity + counts: match_front, dmm_front.hip), solver, mix.
 #include <limits.h>
 #include <stdlib.h>
 
 #include <atomic>
 
-#include "dmm_common.h"
+#include "dmm_launchers.h"
 #include "dmm_solve.h"
 
 namespace dmm {
-int cosine_lanes_launch(const float *feat_t, const float *feat_p, int B, int N, int M, int D, float *cos_out,
-                        hipStream_t stream, int32_t *zero_ptr, int64_t zero_words, const int32_t *n_valid);
-int front_small_launch(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, const float *feat_t,
-                       const float *feat_p, int B, int N, int M, int HW, int D, int64_t sp_b, int64_t sp_n, int64_t st_b,
-                       int64_t st_m, int64_t st2_b, int64_t st2_m, float *cos_out, int32_t *inter, int32_t *area_p,
-                       int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zero, hipStream_t stream);
-int iou_counts_prezeroed(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW, int64_t sp_b,
-                         int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid, const int32_t *m_valid,
-                         int32_t *inter, int32_t *area_p, int32_t *area_t, dmm_stream_t stream);
 static thread_local int g_last_hip_error = 0;
 void set_last_hip_error(int e) { g_last_hip_error = e; }
 static std::atomic<long long> g_launches{0};
@@ -67,7 +59,7 @@ static Workspace carve(void *base, int B, int N, int M, int D) {
         off += align_up(n, 256);
         return p;
     };
-    // inter | area_p | area_t back to back: dmm_iou_counts clears them with one memset
+    // inter | area_p | area_t back to back: the front clears them in one pass (match_front, dmm_front.hip)
     w.inter = (int32_t *)take(sizeof(int32_t) * ((size_t)B * M * N + (size_t)B * N + (size_t)B * M));
     w.area_p = w.inter ? w.inter + (size_t)B * M * N : nullptr;
     w.area_t = w.area_p ? w.area_p + (size_t)B * N : nullptr;
@@ -81,6 +73,35 @@ static Workspace carve(void *base, int B, int N, int M, int D) {
         w.wide = (float *)take(sizeof(float) * (size_t)B * wide_scratch_floats(M, Pp));
     w.bytes = off;
     return w;
+}
+
+static float *or_ws(float *out, float *ws) { return out ? out : ws; }   // an output the caller did not ask for: workspace
+
+// the front on the carved workspace: cosine into w.cosv, counts into the three tables (the entry sets the flags)
+static Front ws_front(const Workspace &w, const void *masks_p, const void *masks_t, int dtype, int64_t sp_b, int64_t sp_n,
+                      int64_t st_b, int64_t st_m, const float *feat_p, const float *feat_t, int B, int N, int M, int HW, int D,
+                      const int32_t *n_valid, const int32_t *m_valid) {
+    Front f{};
+    f.masks_p = masks_p; f.masks_t = masks_t; f.dtype = dtype;
+    f.sp_b = sp_b; f.sp_n = sp_n; f.st_b = st_b; f.st_m = st_m;
+    f.feat_p = feat_p; f.feat_t = feat_t;
+    f.B = B; f.N = N; f.M = M; f.HW = HW; f.D = D;
+    f.n_valid = n_valid; f.m_valid = m_valid;
+    f.cos = w.cosv;
+    f.inter = w.inter; f.area_p = w.area_p; f.area_t = w.area_t;
+    f.table_words = (size_t)B * M * N + (size_t)B * N + (size_t)B * M;
+    f.featn_p = w.featn_p; f.featn_t = w.featn_t;
+    return f;
+}
+// the front of the entries whose planes are 1-bit words on both sides (dmm_pack_words(HW) per plane)
+static Front packed_front(const Workspace &w, const uint64_t *packed_p, int64_t pk_b, int64_t pk_n, const uint64_t *packed_t,
+                          const float *feat_p, const float *feat_t, int B, int N, int M, int HW, int D,
+                          const int32_t *n_valid, const int32_t *m_valid) {
+    const int64_t wd = dmm_pack_words(HW);
+    Front f = ws_front(w, packed_p, packed_t, DMM_PACKED1, pk_b, pk_n, (int64_t)M * wd, wd, feat_p, feat_t, B, N, M, HW, D,
+                       n_valid, m_valid);
+    f.ragged_lanes = true;
+    return f;
 }
 }  // namespace dmm
 
@@ -167,26 +188,23 @@ extern "C" int dmm_match_forward_ws(const void *masks_p, const void *masks_t, in
                                     size_t workspace_bytes, int *ws_state, dmm_stream_t stream) {
     const bool tables_zero = ws_state && *ws_state == DMM_WS_TABLES_ZERO;
     if (ws_state) *ws_state = DMM_WS_UNKNOWN;
-    int cleared = 0;
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || D < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!masks_p || !masks_t || !feat_p || !feat_t || !score_p || !full_outmask || !match_score || !det_score ||
-        !workspace)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    // the mix needs the pixel values: 1-bit planes are an input format of dmm_iou_counts only (reject before any launch)
-    if (mask_dtype != DMM_F32 && mask_dtype != DMM_F16 && mask_dtype != DMM_BF16) return DMM_ERR_BAD_ARG;
-    dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
+    bool go;
+    int rc = dmm::one_call_check(B, N, M, HW, D, masks_p && masks_t && feat_p && feat_t && score_p && full_outmask &&
+                                 match_score && det_score && workspace, &go);
+    if (!go) return rc;
+    if (!dmm::soft_planes(mask_dtype)) return DMM_ERR_BAD_ARG;   // (reject before any launch)
+    const dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
     if (workspace_bytes < w.bytes) return DMM_ERR_WORKSPACE;
-    float *sim = sim_out ? sim_out : w.sim;
-    float *Rb = Rb_out ? Rb_out : w.Rb;
+    const dmm::SolveIn in{w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid};
+    const dmm::SolveOut out{dmm::or_ws(sim_out, w.sim), R_out, dmm::or_ws(Rb_out, w.Rb), match_score, det_score, iters_out,
+                            nullptr};
+    const dmm::RelaxParams prm{max_iter, proj_iter, lr};
     if (dmm::wide_shape(N, M)) {
         // Outside the envelope of the fast kernels (M <= 32, Pp <= 256): counts (they tile any N x M), the features
         // normalised, then the general kernels -- same operations, same order, any size (dmm_wide.hip).
         if (!w.wide || B > 65535) return DMM_ERR_UNSUPPORTED;
-        int rc = dmm_iou_counts(masks_p, masks_t, mask_dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, n_valid, m_valid, w.inter,
-                                w.area_p, w.area_t, stream);
+        rc = dmm_iou_counts(masks_p, masks_t, mask_dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, n_valid, m_valid, w.inter,
+                            w.area_p, w.area_t, stream);
         if (rc != DMM_OK) return rc;
         rc = dmm_feature_normalize_f32(feat_p, (int64_t)B * N, D, w.featn_p, nullptr, stream);
         if (rc != DMM_OK) return rc;
@@ -194,71 +212,29 @@ extern "C" int dmm_match_forward_ws(const void *masks_p, const void *masks_t, in
         if (rc != DMM_OK) return rc;
         rc = dmm::launch_cosine_wide(w.featn_t, w.featn_p, B, N, M, D, n_valid, m_valid, w.cosv, (hipStream_t)stream);
         if (rc != DMM_OK) return rc;
-        if (max_iter < 0 || proj_iter < 0) return DMM_ERR_BAD_ARG;
-        const float w_feat = (float)(1.0 - (double)score_weight);
-        rc = dmm::launch_relax_match_wide(w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid, w_feat,
-                                          score_weight, dmm::RelaxParams{max_iter, proj_iter, lr}, is_test, sim, R_out, Rb,
-                                          match_score, det_score, iters_out, nullptr, w.wide, (hipStream_t)stream);
+        rc = dmm::solve_entry_check(in, out, max_iter, proj_iter, false, &is_test, &go);
+        if (!go) return rc;
+        float w_feat, w_iou;
+        dmm::sim_weights(score_weight, w_feat, w_iou);
+        rc = dmm::launch_relax_match_wide(in, w_feat, w_iou, prm, is_test, out, w.wide, (hipStream_t)stream);
         if (rc != DMM_OK) return rc;
-        return dmm_mask_mix(Rb, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                            (int64_t)M * HW, HW, stream);
+        return dmm_mask_mix(out.Rb, masks_p, mask_dtype, B, N, M, dmm::padded_width(N, M), HW, sp_b, sp_n, n_valid, m_valid,
+                            full_outmask, (int64_t)M * HW, HW, stream);
     }
-    // Feature similarity FIRST when the batch is dense and D is one the lanes kernel takes: that launch also clears the
-    // three count tables (contiguous in the workspace), so the counts start without a memset node -- 4.6 us of a
-    // one-frame call's 135.  Otherwise counts (with their memset), then the tile kernel or normalise x 2 + cosine.
-    const bool force_tile = dmm::opt(DMM_OPT_COSINE_KERNEL) == 1;
-    int rc = DMM_ERR_UNSUPPORTED;
-    // a handful of dense frames: table clear, then similarity and counts beside each other in ONE launch
-    if (!n_valid && !m_valid && !force_tile) {
-        rc = dmm::front_small_launch(masks_p, masks_t, nullptr, mask_dtype, feat_t, feat_p, B, N, M, HW, D, sp_b, sp_n, st_b,
-                                     st_m, 0, 0, w.cosv, w.inter, w.area_p, w.area_t, nullptr, nullptr, tables_zero,
-                                     (hipStream_t)stream);
-        if (rc == DMM_OK) {
-            // the solver reads the tables and (asked to) leaves them zero for the next call on this workspace
-            rc = dmm::relax_match_launch(w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid,
-                                         score_weight, max_iter, proj_iter, lr, is_test, sim, R_out, Rb, match_score,
-                                         det_score, iters_out, nullptr, ws_state != nullptr, &cleared, stream);
-            if (rc != DMM_OK) return rc;
-            goto mix;
-        }
-        if (rc != DMM_ERR_UNSUPPORTED) return rc;
-    }
-    if (!n_valid && !m_valid && !force_tile)
-        rc = dmm::cosine_lanes_launch(feat_t, feat_p, B, N, M, D, w.cosv, (hipStream_t)stream, w.inter,
-                                      (int64_t)B * M * N + (int64_t)B * N + (int64_t)B * M, nullptr);
-    if (rc == DMM_OK) {
-        rc = dmm::iou_counts_prezeroed(masks_p, masks_t, mask_dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, n_valid, m_valid,
-                                       w.inter, w.area_p, w.area_t, stream);
-        if (rc != DMM_OK) return rc;
-    } else if (rc != DMM_ERR_UNSUPPORTED) {
-        return rc;
-    } else {
-        rc = dmm_iou_counts(masks_p, masks_t, mask_dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, n_valid, m_valid, w.inter,
-                            w.area_p, w.area_t, stream);
-        if (rc != DMM_OK) return rc;
-        rc = (!n_valid && !m_valid) ? dmm_cosine_features_f32(feat_t, feat_p, B, N, M, D, w.cosv, stream)
-                                    : DMM_ERR_UNSUPPORTED;
-    }
-    if (rc == DMM_ERR_UNSUPPORTED) {
-        rc = dmm_feature_normalize_f32(feat_p, (int64_t)B * N, D, w.featn_p, nullptr, stream);
-        if (rc != DMM_OK) return rc;
-        rc = dmm_feature_normalize_f32(feat_t, (int64_t)B * M, D, w.featn_t, nullptr, stream);
-        if (rc != DMM_OK) return rc;
-        rc = dmm_cosine_f32(w.featn_t, w.featn_p, B, N, M, D, n_valid, m_valid, w.cosv, stream);
-    }
+    // ragged batches keep the three-launch similarity here; dense ones may take the tile kernel
+    dmm::Front f = dmm::ws_front(w, masks_p, masks_t, mask_dtype, sp_b, sp_n, st_b, st_m, feat_p, feat_t, B, N, M, HW, D,
+                                 n_valid, m_valid);
+    f.tables_zero = tables_zero;
+    f.dense_tile = true;
+    f.split_norm = true;
+    bool fused;
+    rc = dmm::match_front(f, (hipStream_t)stream, &fused);
     if (rc != DMM_OK) return rc;
-    rc = dmm_relax_match_f32(w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid, score_weight,
-                             max_iter, proj_iter, lr, is_test, sim, R_out, Rb, match_score, det_score, iters_out,
-                             nullptr, stream);
+    // behind the fused front the solver reads the tables and (asked to) leaves them zero for the next call on this workspace
+    int cleared = 0;
+    rc = dmm::relax_match_launch(in, score_weight, prm, is_test, out, fused && ws_state, &cleared, stream);
     if (rc != DMM_OK) return rc;
-mix:
-    // train mode keeps every R > 0.01: the rows share planes -> the union of the supports is streamed once
-    if (!is_test)
-        rc = dmm_mask_mix_shared_to(Rb, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                                    DMM_F32, (int64_t)M * HW, HW, stream);
-    else
-        rc = dmm_mask_mix(Rb, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                          (int64_t)M * HW, HW, stream);
+    rc = dmm::match_mix(out.Rb, masks_p, mask_dtype, B, N, M, HW, sp_b, sp_n, n_valid, m_valid, is_test, full_outmask, stream);
     if (rc == DMM_OK && ws_state && cleared) *ws_state = DMM_WS_TABLES_ZERO;
     return rc;
 }
@@ -285,110 +261,53 @@ extern "C" int dmm_match_forward_packed(const void *masks_p, const uint64_t *pac
                                         int max_iter, int proj_iter, float lr, int is_test, float *full_outmask,
                                         float *match_score, float *det_score, float *sim_out, float *R_out, float *Rb_out,
                                         int32_t *iters_out, void *workspace, size_t workspace_bytes, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || D < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!masks_p || !packed_p || !masks_t || !feat_p || !feat_t || !score_p || !full_outmask || !match_score ||
-        !det_score || !workspace)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
-    if (mask_dtype != DMM_F32 && mask_dtype != DMM_F16 && mask_dtype != DMM_BF16) return DMM_ERR_BAD_ARG;
+    bool go;
+    int rc = dmm::one_call_check(B, N, M, HW, D, masks_p && packed_p && masks_t && feat_p && feat_t && score_p &&
+                                 full_outmask && match_score && det_score && workspace, &go);
+    if (!go) return rc;
+    if (!dmm::in_fast_envelope(N, M)) return DMM_ERR_UNSUPPORTED;
+    if (!dmm::soft_planes(mask_dtype)) return DMM_ERR_BAD_ARG;
     if (st_b != (int64_t)M * st_m) return DMM_ERR_UNSUPPORTED;          // templates: one plane stride over the batch
-    dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
-    const int64_t wd = dmm_pack_words(HW);
+    const dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
     if (workspace_bytes < w.bytes + packed_t_bytes(B, M, HW)) return DMM_ERR_WORKSPACE;
     uint64_t *packed_t = (uint64_t *)((char *)workspace + w.bytes);
-    float *sim = sim_out ? sim_out : w.sim;
-    float *Rb = Rb_out ? Rb_out : w.Rb;
-    int rc = dmm_pack_masks(masks_t, mask_dtype, (int64_t)B * M, HW, st_m, packed_t, wd, stream);
+    const dmm::SolveIn in{w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid};
+    const dmm::SolveOut out{dmm::or_ws(sim_out, w.sim), R_out, dmm::or_ws(Rb_out, w.Rb), match_score, det_score, iters_out,
+                            nullptr};
+    rc = dmm_pack_masks(masks_t, mask_dtype, (int64_t)B * M, HW, st_m, packed_t, dmm_pack_words(HW), stream);
     if (rc != DMM_OK) return rc;
-    // Feature similarity of all frames in the one-launch kernel, which also clears the count tables: every frame in the
-    // summation order of ITS live proposal count (n_valid), template rows past m_valid are computed and never read (the
-    // solver masks them; the order over D does not depend on the template count) -- bit identical to the ragged
-    // three-launch form on every live entry.
-    const bool force_tile = dmm::opt(DMM_OPT_COSINE_KERNEL) == 1;
-    rc = force_tile ? DMM_ERR_UNSUPPORTED
-                    : dmm::cosine_lanes_launch(feat_t, feat_p, B, N, M, D, w.cosv, (hipStream_t)stream, w.inter,
-                                               (int64_t)B * M * N + (int64_t)B * N + (int64_t)B * M, n_valid);
-    if (rc == DMM_OK) {
-        rc = dmm::iou_counts_prezeroed(packed_p, packed_t, DMM_PACKED1, B, N, M, HW, pk_b, pk_n, (int64_t)M * wd, wd,
-                                       n_valid, m_valid, w.inter, w.area_p, w.area_t, stream);
-        if (rc != DMM_OK) return rc;
-    } else if (rc != DMM_ERR_UNSUPPORTED) {
-        return rc;
-    } else {
-        rc = dmm_iou_counts(packed_p, packed_t, DMM_PACKED1, B, N, M, HW, pk_b, pk_n, (int64_t)M * wd, wd, n_valid,
-                            m_valid, w.inter, w.area_p, w.area_t, stream);
-        if (rc != DMM_OK) return rc;
-        rc = dmm_feature_normalize_f32(feat_p, (int64_t)B * N, D, w.featn_p, nullptr, stream);
-        if (rc != DMM_OK) return rc;
-        rc = dmm_feature_normalize_f32(feat_t, (int64_t)B * M, D, w.featn_t, nullptr, stream);
-        if (rc != DMM_OK) return rc;
-        rc = dmm_cosine_f32(w.featn_t, w.featn_p, B, N, M, D, n_valid, m_valid, w.cosv, stream);
-        if (rc != DMM_OK) return rc;
-    }
-    rc = dmm_relax_match_f32(w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid, score_weight,
-                             max_iter, proj_iter, lr, is_test, sim, R_out, Rb, match_score, det_score, iters_out,
-                             nullptr, stream);
+    rc = dmm::match_front(dmm::packed_front(w, packed_p, pk_b, pk_n, packed_t, feat_p, feat_t, B, N, M, HW, D, n_valid, m_valid),
+                          (hipStream_t)stream);
     if (rc != DMM_OK) return rc;
-    // train mode keeps every R > 0.01: the rows share planes -> the union of the supports is streamed once
-    if (!is_test)
-        return dmm_mask_mix_shared_to(Rb, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                                      DMM_F32, (int64_t)M * HW, HW, stream);
-    return dmm_mask_mix(Rb, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                        (int64_t)M * HW, HW, stream);
-}
-
-// cosine + counts of (5c) and its hungarian twin: the count tables and the cosine land in the carved workspace `w`
-static int solve_packed_front(const uint64_t *packed_p, const uint64_t *packed_t, const float *feat_p, const float *feat_t,
-                              int B, int N, int M, int HW, int D, const int32_t *n_valid, const int32_t *m_valid,
-                              const dmm::Workspace &w, dmm_stream_t stream) {
-    const int64_t wd = dmm_pack_words(HW);
-    const bool force_tile = dmm::opt(DMM_OPT_COSINE_KERNEL) == 1;
-    int rc = force_tile ? DMM_ERR_UNSUPPORTED
-                        : dmm::cosine_lanes_launch(feat_t, feat_p, B, N, M, D, w.cosv, (hipStream_t)stream, w.inter,
-                                                   (int64_t)B * M * N + (int64_t)B * N + (int64_t)B * M, n_valid);
-    if (rc == DMM_OK) {
-        return dmm::iou_counts_prezeroed(packed_p, packed_t, DMM_PACKED1, B, N, M, HW, (int64_t)N * wd, wd,
-                                         (int64_t)M * wd, wd, n_valid, m_valid, w.inter, w.area_p, w.area_t, stream);
-    } else if (rc != DMM_ERR_UNSUPPORTED) {
-        return rc;
-    }
-    rc = dmm_iou_counts(packed_p, packed_t, DMM_PACKED1, B, N, M, HW, (int64_t)N * wd, wd, (int64_t)M * wd, wd, n_valid,
-                        m_valid, w.inter, w.area_p, w.area_t, stream);
+    rc = dmm::relax_match_launch(in, score_weight, {max_iter, proj_iter, lr}, is_test, out, 0, nullptr, stream);
     if (rc != DMM_OK) return rc;
-    rc = dmm_feature_normalize_f32(feat_p, (int64_t)B * N, D, w.featn_p, nullptr, stream);
-    if (rc != DMM_OK) return rc;
-    rc = dmm_feature_normalize_f32(feat_t, (int64_t)B * M, D, w.featn_t, nullptr, stream);
-    if (rc != DMM_OK) return rc;
-    return dmm_cosine_f32(w.featn_t, w.featn_p, B, N, M, D, n_valid, m_valid, w.cosv, stream);
+    return dmm::match_mix(out.Rb, masks_p, mask_dtype, B, N, M, HW, sp_b, sp_n, n_valid, m_valid, is_test, full_outmask, stream);
 }
 
 // (5c) Cost + assignment of the fixed-slot frame step, BOTH sides of the cost pass on 1-bit planes and no mix: the
 // proposals' words from dmm_paste_kept_f32, the templates' words from the previous frame's dmm_step_finish_f32.
-// cosine (dense, also clears the count tables) -> counts on the words -> solver; Rb / scores / iters out.
+// cosine (also clears the count tables) -> counts on the words -> solver; Rb / scores / iters out.
 extern "C" int dmm_match_solve_packed(const uint64_t *packed_p, const uint64_t *packed_t, const float *feat_p,
                                       const float *feat_t, const float *score_p, int B, int N, int M, int HW, int D,
                                       const int32_t *n_valid, const int32_t *m_valid, float score_weight, int max_iter,
                                       int proj_iter, float lr, int is_test, float *Rb_out, float *match_score,
                                       float *det_score, float *sim_out, float *R_out, int32_t *iters_out, void *workspace,
                                       size_t workspace_bytes, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || D < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!packed_p || !packed_t || !feat_p || !feat_t || !score_p || !Rb_out || !match_score || !det_score || !workspace)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
-    dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
+    bool go;
+    int rc = dmm::one_call_check(B, N, M, HW, D, packed_p && packed_t && feat_p && feat_t && score_p && Rb_out &&
+                                 match_score && det_score && workspace, &go);
+    if (!go) return rc;
+    if (!dmm::in_fast_envelope(N, M)) return DMM_ERR_UNSUPPORTED;
+    const dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
     if (workspace_bytes < w.bytes) return DMM_ERR_WORKSPACE;
-    float *sim = sim_out ? sim_out : w.sim;
-    const int rc = solve_packed_front(packed_p, packed_t, feat_p, feat_t, B, N, M, HW, D, n_valid, m_valid, w, stream);
+    const int64_t wd = dmm_pack_words(HW);
+    rc = dmm::match_front(dmm::packed_front(w, packed_p, (int64_t)N * wd, wd, packed_t, feat_p, feat_t, B, N, M, HW, D, n_valid,
+                                            m_valid), (hipStream_t)stream);
     if (rc != DMM_OK) return rc;
-    return dmm_relax_match_f32(w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid, score_weight,
-                               max_iter, proj_iter, lr, is_test, sim, R_out, Rb_out, match_score, det_score, iters_out,
-                               nullptr, stream);
+    return dmm::relax_match_launch({w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid}, score_weight,
+                                   {max_iter, proj_iter, lr}, is_test,
+                                   {dmm::or_ws(sim_out, w.sim), R_out, Rb_out, match_score, det_score, iters_out, nullptr}, 0,
+                                   nullptr, stream);
 }
 
 // (5c') the same with the Hungarian solver (algo 'hun')
@@ -398,20 +317,20 @@ extern "C" int dmm_match_solve_packed_hun(const uint64_t *packed_p, const uint64
                                           float *Rb_out, float *match_score, float *det_score, float *sim_out,
                                           float *R_out, int32_t *status, void *workspace, size_t workspace_bytes,
                                           dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || D < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0) return DMM_OK;
-    if (M == 0) return dmm::lsap_zero_status(status, B, stream);
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!packed_p || !packed_t || !feat_p || !feat_t || !score_p || !Rb_out || !match_score || !det_score || !status ||
-        !workspace)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
-    dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
+    (void)is_test;                                               // a one-hot row keeps its one under both logic rules
+    if (B > 0 && M == 0 && N >= 0 && HW >= 0 && D >= 0) return dmm::lsap_zero_status(status, B, stream);
+    bool go;
+    int rc = dmm::one_call_check(B, N, M, HW, D, packed_p && packed_t && feat_p && feat_t && score_p && Rb_out &&
+                                 match_score && det_score && status && workspace, &go);
+    if (!go) return rc;
+    if (!dmm::in_fast_envelope(N, M)) return DMM_ERR_UNSUPPORTED;
+    const dmm::Workspace w = dmm::carve(workspace, B, N, M, D);
     if (workspace_bytes < w.bytes) return DMM_ERR_WORKSPACE;
-    float *sim = sim_out ? sim_out : w.sim;
-    const int rc = solve_packed_front(packed_p, packed_t, feat_p, feat_t, B, N, M, HW, D, n_valid, m_valid, w, stream);
+    const int64_t wd = dmm_pack_words(HW);
+    rc = dmm::match_front(dmm::packed_front(w, packed_p, (int64_t)N * wd, wd, packed_t, feat_p, feat_t, B, N, M, HW, D, n_valid,
+                                            m_valid), (hipStream_t)stream);
     if (rc != DMM_OK) return rc;
-    return dmm_hungarian_match_f32(w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid, score_weight,
-                                   is_test, sim, R_out, Rb_out, match_score, det_score, status, stream);
+    return dmm::hungarian_match_launch({w.cosv, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid}, score_weight,
+                                       {dmm::or_ws(sim_out, w.sim), R_out, Rb_out, match_score, det_score, nullptr, nullptr},
+                                       status, stream);
 }

@@ -8,6 +8,7 @@
 // the table is bit exact against the reference -- it feeds the solver, whose exit tests are sensitive to
 // the last ulp.  Work is tiny (M*N*D = 256 kFLOP per frame at the BASELINE config); the kernels are laid
 // out for exactness first, parallelism across frames second.
+#include "dmm_launchers.h"
 #include "dmm_solve.h"
 #include "dmm_torch_order.h"
 
@@ -551,12 +552,6 @@ extern "C" int dmm_cosine_f32(const float *featn_t, const float *featn_p, int B,
     return dmm::check_launch();
 }
 
-namespace dmm {
-int cosine_lanes_launch(const float *feat_t, const float *feat_p, int B, int N, int M, int D, float *cos_out,
-                        hipStream_t stream, int32_t *zero_ptr = nullptr, int64_t zero_words = 0,
-                        const int32_t *n_valid = nullptr);
-}
-
 extern "C" int dmm_cosine_features_f32(const float *feat_t, const float *feat_p, int B, int N, int M, int D,
                                        float *cos_out, dmm_stream_t stream) {
     if (B < 0 || N < 0 || M < 0 || D < 0) return DMM_ERR_BAD_ARG;
@@ -973,7 +968,8 @@ extern "C" int dmm_feature_sim_bwd_f32(const float *dsim, const float *cosv, con
     // any N, M whose longer side fits the default dynamic-LDS limit (the row's dcos slice: 4 bytes per entry)
     const size_t coef_bytes = sizeof(float) * (size_t)(N > M ? N : M);
     if (coef_bytes > 60 * 1024 || B > 65535 || (int64_t)N + M > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
-    const float w_feat = (float)(1.0 - (double)score_weight);
+    float w_feat, w_iou;
+    dmm::sim_weights(score_weight, w_feat, w_iou);                  // (the IoU term has no feature gradient)
     // one workgroup per frame, thread = feature column, while the template rows fit a thread's registers (M <= 32) and D is
     // a whole number of waves up to one workgroup; anything else: the block-per-row form
     const int nw = D / 64;

@@ -23,6 +23,7 @@
 // overlap the arithmetic of the others.  The division by the norm is the hardware's own refinement sequence with the
 // denominator part hoisted out of the row (RowDiv below), falling back to a true division where scaling would matter.
 #include "dmm_cosine_lanes.h"
+#include "dmm_launchers.h"
 
 namespace dmm {
 

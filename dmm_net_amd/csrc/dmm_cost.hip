@@ -25,7 +25,7 @@
 
 #include <type_traits>
 
-#include "dmm_common.h"
+#include "dmm_launchers.h"
 #include "dmm_cosine_lanes.h"
 
 namespace dmm {

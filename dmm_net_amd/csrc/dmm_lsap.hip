@@ -301,25 +301,30 @@ extern "C" int dmm_lsap_f32(const float *C, int B, int nr, int nc, const int32_t
     return dmm::check_launch();
 }
 
+// dmm_hungarian_match_f32 proper (a one-hot row keeps its one under both logic rules: no is_test)
+int dmm::hungarian_match_launch(const SolveIn &in, float score_weight, const SolveOut &out, int32_t *status,
+                                dmm_stream_t stream) {
+    if (in.B > 0 && in.N >= 0 && in.M == 0) return lsap_zero_status(status, in.B, stream);
+    int is_test = 0;
+    bool go;
+    const int rc = solve_entry_check(in, out, 0, 0, false, &is_test, &go);
+    if (!go) return rc;
+    if (!status) return DMM_ERR_BAD_ARG;
+    if (!in_fast_envelope(in.N, in.M)) return DMM_ERR_UNSUPPORTED;
+    float w_feat, w_iou;
+    sim_weights(score_weight, w_feat, w_iou);
+    hipLaunchKernelGGL(hungarian_match_kernel, dim3(in.B), dim3(64), (size_t)in.M * padded_width(in.N, in.M) * sizeof(float),
+                       (hipStream_t)stream, in.cos, in.inter, in.area_p, in.area_t, in.score_p, in.N, in.M, in.n_valid,
+                       in.m_valid, w_feat, w_iou, out.sim, out.R, out.Rb, out.match_score, out.det_score, status);
+    return check_launch();
+}
+
 extern "C" int dmm_hungarian_match_f32(const float *cos_in, const int32_t *inter, const int32_t *area_p,
                                        const int32_t *area_t, const float *score_p, int B, int N, int M,
                                        const int32_t *n_valid, const int32_t *m_valid, float score_weight, int is_test,
                                        float *sim_out, float *R_out, float *Rb_out, float *match_score,
                                        float *det_score, int32_t *status, dmm_stream_t stream) {
-    (void)is_test;                                               // a one-hot row keeps its one under both logic rules
-    if (B < 0 || N < 0 || M < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0) return DMM_OK;
-    if (M == 0) return dmm::lsap_zero_status(status, B, stream);
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!cos_in || !inter || !area_p || !area_t || !score_p || !sim_out || !Rb_out || !match_score || !det_score ||
-        !status)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
-    float w_feat, w_iou;
-    dmm::sim_weights(score_weight, w_feat, w_iou);
-    hipLaunchKernelGGL(dmm::hungarian_match_kernel, dim3(B), dim3(64), (size_t)M * Pp * sizeof(float), (hipStream_t)stream,
-                       cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, sim_out, R_out,
-                       Rb_out, match_score, det_score, status);
-    return dmm::check_launch();
+    (void)is_test;
+    return dmm::hungarian_match_launch({cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid}, score_weight,
+                                       {sim_out, R_out, Rb_out, match_score, det_score, nullptr, nullptr}, status, stream);
 }

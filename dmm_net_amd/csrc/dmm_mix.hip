@@ -10,7 +10,7 @@
 
 #include <type_traits>
 
-#include "dmm_common.h"
+#include "dmm_launchers.h"
 
 namespace dmm {
 

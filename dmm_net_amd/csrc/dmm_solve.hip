@@ -40,7 +40,10 @@ bool use_row_split(int B, int M, int Pp) {
 }
 
 
-template <int MT, int NG, bool EXACT>
+// TAPED (the TRAINING forward, dmm_match_train_forward; one wave per frame): the solver records its sweeps -- gate bits per
+// column and sweep into tape_bits, executed sweeps per outer iteration into tape_sweeps -- for the backward, and X_final is
+// not written.  Untaped instantiations never touch the two tape pointers.
+template <int MT, int NG, bool EXACT, bool TAPED = false>
 // (4-wave instantiations up to 20 rows are capped at 256 registers -- 4 spilled -- so that two frames share a CU:
 // 20 x 200 needed 256 VGPRs + 12 AGPRs = one wave per SIMD, i.e. 256 frames filled the chip and 512 took twice as long)
 __global__ __launch_bounds__(NG == 1 ? 128 : 64 * NG, (NG == 4 && MT <= 20) ? 2 : 1) void relax_match_kernel(
@@ -49,106 +52,57 @@ __global__ __launch_bounds__(NG == 1 ? 128 : 64 * NG, (NG == 4 && MT <= 20) ? 2 
     const int32_t *__restrict__ n_valid, const int32_t *__restrict__ m_valid, float w_feat, float w_iou,
     RelaxParams prm, int is_test, float *__restrict__ sim_out, float *__restrict__ R_out, float *__restrict__ Rb_out,
     float *__restrict__ match_score, float *__restrict__ det_score, int32_t *__restrict__ iters_out,
-    float *__restrict__ X_final) {
+    float *__restrict__ X_final, uint2 *__restrict__ tape_bits, int *__restrict__ tape_sweeps) {
+    static_assert(!TAPED || NG == 1, "the tape is the one-wave kernels'");
     __shared__ float red_buf[2 * NG * (MT + 1)];
     __shared__ float xbuf[MT * 64 * NG];
     __shared__ float rsbuf[MT + 1];
     __shared__ int hs[4];
     if (NG == 1 && solver_helper_entry(xbuf, hs)) return;       // 128-thread workgroups: wave 1 is the norm helper
-    relax_match_body<MT, NG, EXACT>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm,
-                                    is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final, red_buf,
-                                    xbuf, rsbuf, hs);
+    relax_match_body<MT, NG, EXACT, false, TAPED>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou,
+                                                  prm, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out,
+                                                  TAPED ? nullptr : X_final, red_buf, xbuf, rsbuf, hs,
+                                                  TAPED ? tape_bits : nullptr, TAPED ? tape_sweeps : nullptr);
     if (NG == 1) solver_helper_stop(hs);                        // (paths that never reached the solver)
 }
 
-// The same kernel for the TRAINING forward (dmm_match_train_forward): one wave per frame, and the solver records its sweeps
-// (gate bits per column and sweep, executed sweeps per outer iteration) for the backward.  Kernels of their own so that the
-// evaluator's solve stays the code it was.
-template <int MT, bool EXACT>
-__global__ __launch_bounds__(128) void relax_match_taped_kernel(
-    const float *__restrict__ cos_in, const int32_t *__restrict__ inter, const int32_t *__restrict__ area_p,
-    const int32_t *__restrict__ area_t, const float *__restrict__ score_p, int N, int M,
-    const int32_t *__restrict__ n_valid, const int32_t *__restrict__ m_valid, float w_feat, float w_iou,
-    RelaxParams prm, int is_test, float *__restrict__ sim_out, float *__restrict__ R_out, float *__restrict__ Rb_out,
-    float *__restrict__ match_score, float *__restrict__ det_score, int32_t *__restrict__ iters_out,
-    uint2 *__restrict__ tape_bits, int *__restrict__ tape_sweeps) {
-    __shared__ float red_buf[2 * (MT + 1)];
-    __shared__ float xbuf[MT * 64];
-    __shared__ float rsbuf[MT + 1];
-    __shared__ int hs[4];
-    if (solver_helper_entry(xbuf, hs)) return;
-    relax_match_body<MT, 1, EXACT, false, true>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou,
-                                                prm, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out,
-                                                nullptr, red_buf, xbuf, rsbuf, hs, tape_bits, tape_sweeps);
-    solver_helper_stop(hs);
-}
+// Ragged template counts, one wave per frame: the wave runs the EXACT-row-count body of ITS frame -- BODY(K, true) for
+// Mb = 2 .. MTMAX -- and the guarded one-row body for 1 template and for dead frames (Mb <= 0: zeros).
+#define DMM_RAGGED_CASE(K, MTMAX, BODY)         \
+    case K:                                     \
+        if constexpr (K <= MTMAX) BODY(K, true); \
+        break;
+#define DMM_RAGGED_SWITCH(Mb, MTMAX, BODY)                                                                      \
+    switch (Mb) {                                                                                               \
+        DMM_RAGGED_CASE(2, MTMAX, BODY) DMM_RAGGED_CASE(3, MTMAX, BODY) DMM_RAGGED_CASE(4, MTMAX, BODY)         \
+        DMM_RAGGED_CASE(5, MTMAX, BODY) DMM_RAGGED_CASE(6, MTMAX, BODY) DMM_RAGGED_CASE(7, MTMAX, BODY)         \
+        DMM_RAGGED_CASE(8, MTMAX, BODY)                                                                         \
+        default: BODY(1, false); break;                                                                         \
+    }
 
-// Ragged batches of small problems (the product: up to maxseqlen = 5 templates per video, a different count per video):
-// one wave per frame picks the EXACT-row-count body of ITS frame.  The guarded MT = 8 instantiation carried 8 rows and a
-// row guard on every element for every frame (5 templates, eval setting 40 x 5: 183 us per solve; exact: ~120).
-template <int MTMAX>
+// Ragged batches of small problems (the product: up to maxseqlen = 5 templates per video, a different count per video).
+// The guarded MT = 8 instantiation carried 8 rows and a row guard on every element for every frame (5 templates, eval
+// setting 40 x 5: 183 us per solve; exact: ~120).  TAPED: as in relax_match_kernel.
+template <int MTMAX, bool TAPED>
 __global__ __launch_bounds__(128) void relax_match_ragged_kernel(
     const float *__restrict__ cos_in, const int32_t *__restrict__ inter, const int32_t *__restrict__ area_p,
     const int32_t *__restrict__ area_t, const float *__restrict__ score_p, int N, int M,
     const int32_t *__restrict__ n_valid, const int32_t *__restrict__ m_valid, float w_feat, float w_iou,
     RelaxParams prm, int is_test, float *__restrict__ sim_out, float *__restrict__ R_out, float *__restrict__ Rb_out,
     float *__restrict__ match_score, float *__restrict__ det_score, int32_t *__restrict__ iters_out,
-    float *__restrict__ X_final) {
+    float *__restrict__ X_final, uint2 *__restrict__ tape_bits, int *__restrict__ tape_sweeps) {
     __shared__ float red_buf[2 * (MTMAX + 1)];
     __shared__ float xbuf[MTMAX * 64];
     __shared__ float rsbuf[MTMAX + 1];
     __shared__ int hs[4];
     if (solver_helper_entry(xbuf, hs)) return;
     const int Mb = m_valid ? m_valid[blockIdx.x] : M;
-#define DMM_BODY(K)                                                                                                     \
-    case K:                                                                                                             \
-        if constexpr (K <= MTMAX)                                                                                       \
-            relax_match_body<K, 1, true>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, \
-                                         prm, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out,       \
-                                         X_final, red_buf, xbuf, rsbuf, hs);                                            \
-        break;
-    switch (Mb) {
-        DMM_BODY(2) DMM_BODY(3) DMM_BODY(4) DMM_BODY(5) DMM_BODY(6) DMM_BODY(7) DMM_BODY(8)
-        default:                                            // 1 template, and dead frames (Mb <= 0: zeros)
-            relax_match_body<1, 1, false>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm,
-                                          is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final,
-                                          red_buf, xbuf, rsbuf, hs);
-            break;
-    }
-#undef DMM_BODY
-    solver_helper_stop(hs);
-}
-
-// ... and its taped twin for the training forward (see relax_match_taped_kernel)
-template <int MTMAX>
-__global__ __launch_bounds__(128) void relax_match_ragged_taped_kernel(
-    const float *__restrict__ cos_in, const int32_t *__restrict__ inter, const int32_t *__restrict__ area_p,
-    const int32_t *__restrict__ area_t, const float *__restrict__ score_p, int N, int M,
-    const int32_t *__restrict__ n_valid, const int32_t *__restrict__ m_valid, float w_feat, float w_iou,
-    RelaxParams prm, int is_test, float *__restrict__ sim_out, float *__restrict__ R_out, float *__restrict__ Rb_out,
-    float *__restrict__ match_score, float *__restrict__ det_score, int32_t *__restrict__ iters_out,
-    uint2 *__restrict__ tape_bits, int *__restrict__ tape_sweeps) {
-    __shared__ float red_buf[2 * (MTMAX + 1)];
-    __shared__ float xbuf[MTMAX * 64];
-    __shared__ float rsbuf[MTMAX + 1];
-    __shared__ int hs[4];
-    if (solver_helper_entry(xbuf, hs)) return;
-    const int Mb = m_valid ? m_valid[blockIdx.x] : M;
-#define DMM_BODY(K)                                                                                                     \
-    case K:                                                                                                             \
-        if constexpr (K <= MTMAX)                                                                                       \
-            relax_match_body<K, 1, true, false, true>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, \
-                                                      w_iou, prm, is_test, sim_out, R_out, Rb_out, match_score, det_score,   \
-                                                      iters_out, nullptr, red_buf, xbuf, rsbuf, hs, tape_bits, tape_sweeps); \
-        break;
-    switch (Mb) {
-        DMM_BODY(2) DMM_BODY(3) DMM_BODY(4) DMM_BODY(5) DMM_BODY(6) DMM_BODY(7) DMM_BODY(8)
-        default:
-            relax_match_body<1, 1, false, false, true>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat,
-                                                       w_iou, prm, is_test, sim_out, R_out, Rb_out, match_score, det_score,
-                                                       iters_out, nullptr, red_buf, xbuf, rsbuf, hs, tape_bits, tape_sweeps);
-            break;
-    }
+#define DMM_BODY(K, EX)                                                                                                  \
+    relax_match_body<K, 1, EX, false, TAPED>(cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, \
+                                             prm, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out,     \
+                                             TAPED ? nullptr : X_final, red_buf, xbuf, rsbuf, hs,                         \
+                                             TAPED ? tape_bits : nullptr, TAPED ? tape_sweeps : nullptr)
+    DMM_RAGGED_SWITCH(Mb, MTMAX, DMM_BODY)
 #undef DMM_BODY
     solver_helper_stop(hs);
 }
@@ -353,19 +307,10 @@ __global__ __launch_bounds__(64) void relax_match_bwd_ragged_kernel(
     __shared__ float rsbuf[MTMAX + 1];
     __shared__ int sweeps_s[kMaxTapeOuter];
     const int Mb = m_valid ? m_valid[blockIdx.x] : M;
-#define DMM_BODY(K)                                                                                                       \
-    case K:                                                                                                               \
-        if constexpr (K <= MTMAX)                                                                                         \
-            relax_match_bwd_body<K, 1, true>(sim_in, score_p, N, M, n_valid, m_valid, prm, is_test, dRb_in, dms_in, dds_in, \
-                                             dsim_out, tape_ws, red_buf, xbuf, rsbuf, sweeps_s, R_saved, iters_saved);    \
-        break;
-    switch (Mb) {
-        DMM_BODY(2) DMM_BODY(3) DMM_BODY(4) DMM_BODY(5) DMM_BODY(6) DMM_BODY(7) DMM_BODY(8)
-        default:                                            // 1 template, and dead frames (Mb <= 0: zeros)
-            relax_match_bwd_body<1, 1, false>(sim_in, score_p, N, M, n_valid, m_valid, prm, is_test, dRb_in, dms_in, dds_in,
-                                              dsim_out, tape_ws, red_buf, xbuf, rsbuf, sweeps_s, R_saved, iters_saved);
-            break;
-    }
+#define DMM_BODY(K, EX)                                                                                                \
+    relax_match_bwd_body<K, 1, EX>(sim_in, score_p, N, M, n_valid, m_valid, prm, is_test, dRb_in, dms_in, dds_in, dsim_out, \
+                                   tape_ws, red_buf, xbuf, rsbuf, sweeps_s, R_saved, iters_saved)
+    DMM_RAGGED_SWITCH(Mb, MTMAX, DMM_BODY)
 #undef DMM_BODY
 }
 
@@ -377,9 +322,9 @@ extern "C" int dmm_relax_match_f32(const float *cos_in, const int32_t *inter, co
                                    int proj_iter, float lr, int is_test, float *sim_out, float *R_out, float *Rb_out,
                                    float *match_score, float *det_score, int32_t *iters_out, float *X_final,
                                    dmm_stream_t stream) {
-    return dmm::relax_match_launch(cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid, score_weight, max_iter,
-                                   proj_iter, lr, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out,
-                                   X_final, 0, nullptr, stream);
+    return dmm::relax_match_launch({cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid}, score_weight,
+                                   {max_iter, proj_iter, lr}, is_test,
+                                   {sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final}, 0, nullptr, stream);
 }
 
 // Bytes of the tape dmm_match_train_forward keeps for dmm_match_train_backward: per frame max_iter * proj_iter sweep records of
@@ -394,44 +339,36 @@ size_t dmm::relax_tape_bytes(int B, int N, int M, int max_iter, int proj_iter) {
 // dmm_relax_match_f32 proper.  clear_tables (dmm_match_forward_ws only; the tables are then its workspace, not the
 // caller's): ask the kernel to zero inter / area_p / area_t once it has read them; *cleared says whether the kernel that
 // was launched does that (the thread-per-column kernels on dense frames do, the other mappings do not).
-int dmm::relax_match_launch(const float *cos_in, const int32_t *inter, const int32_t *area_p, const int32_t *area_t,
-                            const float *score_p, int B, int N, int M, const int32_t *n_valid, const int32_t *m_valid,
-                            float score_weight, int max_iter, int proj_iter, float lr, int is_test, float *sim_out,
-                            float *R_out, float *Rb_out, float *match_score, float *det_score, int32_t *iters_out,
-                            float *X_final, int clear_tables, int *cleared, dmm_stream_t stream, void *tape, int *taped) {
+// tape / taped (dmm_match_train_forward): room for the solver's tape, and whether the launched kernel wrote it.
+int dmm::relax_match_launch(const SolveIn &in, float score_weight, RelaxParams prm, int is_test, const SolveOut &out,
+                            int clear_tables, int *cleared, dmm_stream_t stream, void *tape, int *taped) {
     if (cleared) *cleared = 0;
     if (taped) *taped = 0;
-    is_test = is_test != 0;                       // the upper bits of the kernels' argument are the library's own
-    if (B < 0 || N < 0 || M < 0 || max_iter < 0 || proj_iter < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!cos_in || !inter || !area_p || !area_t || !score_p || !sim_out || !Rb_out || !match_score || !det_score)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
-    const dmm::RelaxParams prm{max_iter, proj_iter, lr};
+    bool go;
+    const int rc = solve_entry_check(in, out, prm.max_iter, prm.proj_iter, true, &is_test, &go);
+    if (!go) return rc;
+    const int B = in.B, M = in.M, Pp = padded_width(in.N, M);
+    hipStream_t s = (hipStream_t)stream;
     float w_feat, w_iou;
-    dmm::sim_weights(score_weight, w_feat, w_iou);
-    if (dmm::use_row_split(B, M, Pp))
-        return dmm::launch_relax_match_rs(cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid, w_feat,
-                                          w_iou, prm, is_test, sim_out, R_out, Rb_out, match_score, det_score,
-                                          iters_out, X_final, (hipStream_t)stream);
-    const bool exact_ok = (m_valid == nullptr);   // every frame has exactly M templates
+    sim_weights(score_weight, w_feat, w_iou);
+    if (use_row_split(B, M, Pp)) return launch_relax_match_rs(in, w_feat, w_iou, prm, is_test, out, s);
+    const bool exact_ok = (in.m_valid == nullptr);   // every frame has exactly M templates
+    const dim3 wave1(solver_block(1, B));
+    uint2 *tape_bits = nullptr;
+    int *tape_sweeps = nullptr;
     // the tape (dmm_match_train_forward): the taped one-wave kernels write it -- dense batches of <= 16 templates, ragged
     // ones of <= 8; anything else is not taped (the backward re-runs the solver)
-    if (tape && taped && !X_final && dmm::relax_tape_bytes(B, N, M, max_iter, proj_iter) > 0 && (exact_ok ? M <= 16 : M <= 8)) {
-        uint2 *tape_bits = (uint2 *)tape;
-        int *tape_sweeps = (int *)(tape_bits + (size_t)B * max_iter * proj_iter * 64);
+    if (tape && taped && !out.X_final && relax_tape_bytes(B, in.N, M, prm.max_iter, prm.proj_iter) > 0 &&
+        (exact_ok ? M <= 16 : M <= 8)) {
+        tape_bits = (uint2 *)tape;
+        tape_sweeps = (int *)(tape_bits + (size_t)B * prm.max_iter * prm.proj_iter * 64);
         *taped = 1;
-#define DMM_TAPED(MT_)                                                                                                   \
-    hipLaunchKernelGGL((dmm::relax_match_taped_kernel<MT_, true>), dim3(B), dim3(dmm::solver_block(1, B)), 0,            \
-                       (hipStream_t)stream, cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, \
-                       prm, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out, tape_bits, tape_sweeps)
+#define DMM_TAPED(MT_)                                                                \
+    hipLaunchKernelGGL((relax_match_kernel<MT_, 1, true, true>), dim3(B), wave1, 0, s, \
+                       DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final, tape_bits, tape_sweeps)
         if (!exact_ok) {
-            hipLaunchKernelGGL((dmm::relax_match_ragged_taped_kernel<8>), dim3(B), dim3(dmm::solver_block(1, B)), 0,
-                               (hipStream_t)stream, cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat,
-                               w_iou, prm, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out, tape_bits,
-                               tape_sweeps);
+            hipLaunchKernelGGL((relax_match_ragged_kernel<8, true>), dim3(B), wave1, 0, s,
+                               DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final, tape_bits, tape_sweeps);
         } else {
             switch (M) {
                 case 1: DMM_TAPED(1); break;   case 2: DMM_TAPED(2); break;   case 3: DMM_TAPED(3); break;
@@ -443,25 +380,23 @@ int dmm::relax_match_launch(const float *cos_in, const int32_t *inter, const int
             }
         }
 #undef DMM_TAPED
-        return dmm::check_launch();
+        return check_launch();
     }
     if (!exact_ok && M <= 8 && Pp <= 64) {        // ragged template counts, one wave per frame: per-frame exact bodies
-        hipLaunchKernelGGL((dmm::relax_match_ragged_kernel<8>), dim3(B), dim3(dmm::solver_block(1, B)), 0, (hipStream_t)stream, cos_in, inter,
-                           area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm, is_test, sim_out, R_out,
-                           Rb_out, match_score, det_score, iters_out, X_final);
-        return dmm::check_launch();
+        hipLaunchKernelGGL((relax_match_ragged_kernel<8, false>), dim3(B), wave1, 0, s,
+                           DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final, tape_bits, tape_sweeps);
+        return check_launch();
     }
-#define DMM_CALL(MT_, NG_, EX_)                                                                                    \
-    hipLaunchKernelGGL((dmm::relax_match_kernel<MT_, NG_, EX_>), dim3(B), dim3(dmm::solver_block(NG_, B)), 0, (hipStream_t)stream,   \
-                       cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm, is_test, \
-                       sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final)
-    if (clear_tables && cleared && !n_valid && !m_valid) {
-        is_test |= dmm::kRelaxClearTables;
+#define DMM_CALL(MT_, NG_, EX_)                                                                           \
+    hipLaunchKernelGGL((relax_match_kernel<MT_, NG_, EX_>), dim3(B), dim3(solver_block(NG_, B)), 0, s,     \
+                       DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final, tape_bits, tape_sweeps)
+    if (clear_tables && cleared && !in.n_valid && !in.m_valid) {
+        is_test |= kRelaxClearTables;
         *cleared = 1;
     }
     DMM_DISPATCH_SOLVER(M, Pp, exact_ok, DMM_CALL);
 #undef DMM_CALL
-    return dmm::check_launch();
+    return check_launch();
 }
 
 // (3) for ANY N, M: the general solver (dmm_wide.hip) keeps its state in caller-provided scratch.  Inside the fast kernels'
@@ -477,22 +412,19 @@ extern "C" int dmm_relax_match_any_f32(const float *cos_in, const int32_t *inter
                                        int proj_iter, float lr, int is_test, float *sim_out, float *R_out, float *Rb_out,
                                        float *match_score, float *det_score, int32_t *iters_out, float *X_final,
                                        void *scratch, size_t scratch_bytes, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || max_iter < 0 || proj_iter < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M <= DMM_MAX_TEMPLATES && Pp <= DMM_MAX_PROPOSALS && dmm::opt(DMM_OPT_FORCE_WIDE) != 1)
-        return dmm_relax_match_f32(cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid, score_weight, max_iter,
-                                   proj_iter, lr, is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out,
-                                   X_final, stream);
-    if (!cos_in || !inter || !area_p || !area_t || !score_p || !sim_out || !Rb_out || !match_score || !det_score || !scratch)
-        return DMM_ERR_BAD_ARG;
+    const dmm::SolveIn in{cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid};
+    const dmm::SolveOut out{sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final};
+    const dmm::RelaxParams prm{max_iter, proj_iter, lr};
+    if (dmm::in_fast_envelope(N, M) && dmm::opt(DMM_OPT_FORCE_WIDE) != 1)
+        return dmm::relax_match_launch(in, score_weight, prm, is_test, out, 0, nullptr, stream);
+    bool go;
+    const int rc = dmm::solve_entry_check(in, out, max_iter, proj_iter, false, &is_test, &go);
+    if (!go) return rc;
+    if (!scratch) return DMM_ERR_BAD_ARG;
     if (scratch_bytes < dmm_relax_any_scratch_bytes(B, N, M)) return DMM_ERR_WORKSPACE;
-    const float w_feat = (float)(1.0 - (double)score_weight);
-    return dmm::launch_relax_match_wide(cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid, w_feat,
-                                        score_weight, dmm::RelaxParams{max_iter, proj_iter, lr}, is_test, sim_out, R_out,
-                                        Rb_out, match_score, det_score, iters_out, X_final, (float *)scratch,
-                                        (hipStream_t)stream);
+    float w_feat, w_iou;
+    dmm::sim_weights(score_weight, w_feat, w_iou);
+    return dmm::launch_relax_match_wide(in, w_feat, w_iou, prm, is_test, out, (float *)scratch, (hipStream_t)stream);
 }
 
 extern "C" size_t dmm_relax_bwd_workspace_bytes(int B, int N, int M, int max_iter, int proj_iter) {

@@ -35,21 +35,19 @@ extern "C" int dmm_relax_match_f16s(const float *cos_in, const int32_t *inter, c
                                     int proj_iter, float lr, int is_test, float *sim_out, float *R_out, float *Rb_out,
                                     float *match_score, float *det_score, int32_t *iters_out, float *X_final,
                                     dmm_stream_t stream) {
-    is_test = is_test != 0;                       // the upper bits of the kernels' argument are the library's own
-    if (B < 0 || N < 0 || M < 0 || max_iter < 0 || proj_iter < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!cos_in || !inter || !area_p || !area_t || !score_p || !sim_out || !Rb_out || !match_score || !det_score)
-        return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS) return DMM_ERR_UNSUPPORTED;
+    const dmm::SolveIn in{cos_in, inter, area_p, area_t, score_p, B, N, M, n_valid, m_valid};
+    const dmm::SolveOut out{sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final};
+    bool go;
+    const int rc = dmm::solve_entry_check(in, out, max_iter, proj_iter, true, &is_test, &go);
+    if (!go) return rc;
+    const int Pp = dmm::padded_width(N, M);
     const dmm::RelaxParams prm{max_iter, proj_iter, lr};
-    const float w_feat = (float)(1.0 - (double)score_weight), w_iou = score_weight;
+    float w_feat, w_iou;
+    dmm::sim_weights(score_weight, w_feat, w_iou);
     const int ng = (Pp + 63) / 64 <= 1 ? 1 : ((Pp + 63) / 64 == 2 ? 2 : 4);
 #define DMM_CALLH(MT_, NG_, EX_)                                                                                        \
     hipLaunchKernelGGL((dmm::relax_match_h_kernel<MT_, NG_, EX_>), dim3(B), dim3(64 * NG_), 0, (hipStream_t)stream,     \
-                       cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm, is_test,     \
-                       sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final)
+                       DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), X_final)
 #define DMM_PICKH(NG_)                                                                  \
     do {                                                                                \
         if (M <= 8) DMM_CALLH(8, NG_, false);                                           \

@@ -568,21 +568,16 @@ static int rs_prepare(K kernel, size_t smem) {
     return DMM_OK;
 }
 
-int launch_relax_match_rs(const float *cos_in, const int32_t *inter, const int32_t *area_p, const int32_t *area_t,
-                          const float *score_p, int B, int N, int M, const int32_t *n_valid, const int32_t *m_valid,
-                          float w_feat, float w_iou, RelaxParams prm, int is_test, float *sim_out, float *R_out,
-                          float *Rb_out, float *match_score, float *det_score, int32_t *iters_out, float *X_final,
+int launch_relax_match_rs(const SolveIn &in, float w_feat, float w_iou, RelaxParams prm, int is_test, const SolveOut &out,
                           hipStream_t stream) {
-    const int PpS = N > M ? N : M + 1;
-    const RsShape s = rs_shape(M, PpS);
+    const RsShape s = rs_shape(in.M, padded_width(in.N, in.M));
 #define DMM_CALL(RW_, CG_)                                                                                           \
     do {                                                                                                             \
         const size_t smem_ = rs::Smem<RW_, CG_>::bytes();                                                            \
         int rc_ = rs_prepare(rs::relax_match_rs_kernel<RW_, CG_>, smem_);                                            \
         if (rc_ != DMM_OK) return rc_;                                                                               \
-        hipLaunchKernelGGL((rs::relax_match_rs_kernel<RW_, CG_>), dim3(B), dim3(64 * s.RG * s.CG), smem_, stream,     \
-                           cos_in, inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm,        \
-                           is_test, sim_out, R_out, Rb_out, match_score, det_score, iters_out, X_final);              \
+        hipLaunchKernelGGL((rs::relax_match_rs_kernel<RW_, CG_>), dim3(in.B), dim3(64 * s.RG * s.CG), smem_, stream,  \
+                           DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final);                       \
     } while (0)
     DMM_RS_DISPATCH(s.RW, s.CG, DMM_CALL);
 #undef DMM_CALL

@@ -11,29 +11,10 @@
 //                                   feature-similarity backward, 4 launches
 //   dmm_matching_loss_f32     (1e)  compute_matching_loss's tail on the device: gt IoU -> greedy one-hot -> mse
 // Same kernels as the granular entries (bit-identical results); only the loss tail is new arithmetic here.
-#include "dmm_common.h"
+#include "dmm_launchers.h"
 #include "dmm_solve.h"
 
 namespace dmm {
-int cosine_lanes_launch(const float *feat_t, const float *feat_p, int B, int N, int M, int D, float *cos_out,
-                        hipStream_t stream, int32_t *zero_ptr, int64_t zero_words, const int32_t *n_valid);
-int front_small_launch(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, const float *feat_t,
-                       const float *feat_p, int B, int N, int M, int HW, int D, int64_t sp_b, int64_t sp_n, int64_t st_b,
-                       int64_t st_m, int64_t st2_b, int64_t st2_m, float *cos_out, int32_t *inter, int32_t *area_p,
-                       int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zero, hipStream_t stream);
-int iou_counts_prezeroed(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW, int64_t sp_b,
-                         int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid, const int32_t *m_valid,
-                         int32_t *inter, int32_t *area_p, int32_t *area_t, dmm_stream_t stream);
-int iou_counts_dual_prezeroed(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, int B, int N, int M,
-                              int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
-                              const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
-                              int32_t *area_t, int32_t *inter2, int32_t *area_t2, dmm_stream_t stream);
-int feature_normalize2_launch(const float *in_a, int64_t rows_a, float *out_a, float *norms_a, const float *in_b,
-                              int64_t rows_b, float *out_b, float *norms_b, int D, hipStream_t stream, void *zero_ptr = nullptr,
-                              size_t zero_bytes = 0);
-int mask_mix_bwd_prezeroed(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M, int Pp,
-                           int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, float *dRb,
-                           dmm_stream_t stream);
 
 // ---------------------------------------------------------------------------------------------------------------------
 // compute_matching_loss after the counts (dmm/utils/match_helper.py:43-48):
@@ -228,64 +209,36 @@ extern "C" int dmm_match_train_forward(const void *masks_p, const void *masks_t,
                                        size_t workspace_bytes, void *tape, size_t tape_bytes, int *taped,
                                        dmm_stream_t stream) {
     if (taped) *taped = 0;
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || D < 0 || max_iter < 0 || proj_iter < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (N == 0) return DMM_ERR_BAD_ARG;
-    if (!masks_p || !masks_t || !feat_p || !feat_t || !score_p || !full_outmask || !match_score || !det_score || !cos_out ||
-        !sim_out || !Rb_out || !workspace)
-        return DMM_ERR_BAD_ARG;
+    if (max_iter < 0 || proj_iter < 0) return DMM_ERR_BAD_ARG;
+    bool go;
+    int rc = dmm::one_call_check(B, N, M, HW, D, masks_p && masks_t && feat_p && feat_t && score_p && full_outmask &&
+                                 match_score && det_score && cos_out && sim_out && Rb_out && workspace, &go);
+    if (!go) return rc;
     if (targets && (!cost_loss || !gt_out)) return DMM_ERR_BAD_ARG;
-    if (mask_dtype != DMM_F32 && mask_dtype != DMM_F16 && mask_dtype != DMM_BF16) return DMM_ERR_BAD_ARG;
-    const int Pp = N > M ? N : M + 1;
+    if (!dmm::soft_planes(mask_dtype)) return DMM_ERR_BAD_ARG;
     // the fast kernels' envelope; wider tables train through the granular entries (any size)
-    if (M > DMM_MAX_TEMPLATES || Pp > DMM_MAX_PROPOSALS || B > 65535 || dmm::opt(DMM_OPT_FORCE_WIDE) == 1)
-        return DMM_ERR_UNSUPPORTED;
-    dmm::TrainFwdWs w = dmm::carve_train_fwd(workspace, B, N, M, D);
+    if (!dmm::in_fast_envelope(N, M) || B > 65535 || dmm::opt(DMM_OPT_FORCE_WIDE) == 1) return DMM_ERR_UNSUPPORTED;
+    const dmm::TrainFwdWs w = dmm::carve_train_fwd(workspace, B, N, M, D);
     if (workspace_bytes < w.bytes) return DMM_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const bool dense = !n_valid && !m_valid;
     // one pass over the proposal planes for both IoU tables while both template sets fit one tile (<= 16 rows each)
     const bool dual = targets && M <= 16;
-    const bool force_tile = dmm::opt(DMM_OPT_COSINE_KERNEL) == 1;
-    int rc = DMM_ERR_UNSUPPORTED;
-    bool counted = false;
-    if (dense && !force_tile && (dual || !targets)) {      // (proposal planes behind a pointer table included: frame_base)
-        // a handful of dense frames: similarity and counts beside each other in ONE launch (behind one clearing launch)
-        rc = dmm::front_small_launch(masks_p, masks_t, dual ? targets : nullptr, mask_dtype, feat_t, feat_p, B, N, M, HW, D,
-                                     sp_b, sp_n, st_b, st_m, sg_b, sg_m, cos_out, w.inter, w.area_p, w.area_t,
-                                     dual ? w.inter2 : nullptr, dual ? w.area_t2 : nullptr, false, s);
-        if (rc == DMM_OK) counted = true;
-        else if (rc != DMM_ERR_UNSUPPORTED) return rc;
-    }
-    if (!counted) {
-        // the one-launch similarity kernel, which also clears the five count tables: every frame in the summation order of
-        // ITS live proposal count; template rows past m_valid are computed and never read (every consumer masks them)
-        rc = force_tile ? DMM_ERR_UNSUPPORTED
-                        : dmm::cosine_lanes_launch(feat_t, feat_p, B, N, M, D, cos_out, s, w.inter, (int64_t)w.table_words,
-                                                   n_valid);
-        if (rc != DMM_OK && rc != DMM_ERR_UNSUPPORTED) return rc;
-        const bool zeroed = rc == DMM_OK;
-        if (!zeroed) {
-            DMM_HIP_TRY(dmm::zero_async(w.inter, sizeof(int32_t) * w.table_words, s));
-            rc = dense ? dmm_cosine_features_f32(feat_t, feat_p, B, N, M, D, cos_out, stream) : DMM_ERR_UNSUPPORTED;
-            if (rc == DMM_ERR_UNSUPPORTED) {
-                rc = dmm::feature_normalize2_launch(feat_p, (int64_t)B * N, w.featn_p, nullptr, feat_t, (int64_t)B * M,
-                                                    w.featn_t, nullptr, D, s);
-                if (rc != DMM_OK) return rc;
-                rc = dmm_cosine_f32(w.featn_t, w.featn_p, B, N, M, D, n_valid, m_valid, cos_out, stream);
-            }
-            if (rc != DMM_OK) return rc;
-        }
-        if (dual) {
-            rc = dmm::iou_counts_dual_prezeroed(masks_p, masks_t, targets, mask_dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m,
-                                                sg_b, sg_m, n_valid, m_valid, w.inter, w.area_p, w.area_t, w.inter2,
-                                                w.area_t2, stream);
-        } else {
-            rc = dmm::iou_counts_prezeroed(masks_p, masks_t, mask_dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, n_valid, m_valid,
-                                           w.inter, w.area_p, w.area_t, stream);
-        }
-        if (rc != DMM_OK) return rc;
-    }
+    // the front clears all five tables at once; ragged batches take the lanes kernel, dense ones may take the tile kernel
+    // (proposal planes behind a pointer table included: frame_base)
+    dmm::Front f{};
+    f.masks_p = masks_p; f.masks_t = masks_t; f.dtype = mask_dtype;
+    f.sp_b = sp_b; f.sp_n = sp_n; f.st_b = st_b; f.st_m = st_m;
+    if (dual) { f.targets = targets; f.sg_b = sg_b; f.sg_m = sg_m; f.inter2 = w.inter2; f.area_t2 = w.area_t2; }
+    f.feat_p = feat_p; f.feat_t = feat_t;
+    f.B = B; f.N = N; f.M = M; f.HW = HW; f.D = D;
+    f.n_valid = n_valid; f.m_valid = m_valid;
+    f.cos = cos_out;
+    f.inter = w.inter; f.area_p = w.area_p; f.area_t = w.area_t;
+    f.table_words = w.table_words;
+    f.featn_p = w.featn_p; f.featn_t = w.featn_t;
+    f.ragged_lanes = true;
+    f.dense_tile = true;
+    rc = dmm::match_front(f, (hipStream_t)stream);
+    if (rc != DMM_OK) return rc;
     if (targets && !dual) {
         // > 16 rows per set: the targets in a count pass of their own
         rc = dmm_iou_counts(masks_p, targets, mask_dtype, B, N, M, HW, sp_b, sp_n, sg_b, sg_m, n_valid, m_valid, w.inter2,
@@ -298,18 +251,13 @@ extern "C" int dmm_match_train_forward(const void *masks_p, const void *masks_t,
         const bool keep = tape && taped && iters_out && need > 0 && tape_bytes >= need;
         float *R_keep = keep ? (float *)tape : nullptr;
         void *records = keep ? (void *)((char *)tape + dmm::train_tape_r_bytes(B, N, M)) : nullptr;
-        rc = dmm::relax_match_launch(cos_out, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid, score_weight,
-                                     max_iter, proj_iter, lr, is_test, sim_out, R_keep, Rb_out, match_score, det_score,
-                                     iters_out, nullptr, 0, nullptr, stream, records, keep ? taped : nullptr);
+        rc = dmm::relax_match_launch({cos_out, w.inter, w.area_p, w.area_t, score_p, B, N, M, n_valid, m_valid}, score_weight,
+                                     {max_iter, proj_iter, lr}, is_test,
+                                     {sim_out, R_keep, Rb_out, match_score, det_score, iters_out, nullptr}, 0, nullptr, stream,
+                                     records, keep ? taped : nullptr);
     }
     if (rc != DMM_OK) return rc;
-    // train mode keeps every R > 0.01: the rows share planes -> the union of the supports is streamed once
-    if (!is_test)
-        rc = dmm_mask_mix_shared_to(Rb_out, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                                    DMM_F32, (int64_t)M * HW, HW, stream);
-    else
-        rc = dmm_mask_mix(Rb_out, masks_p, mask_dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, full_outmask,
-                          (int64_t)M * HW, HW, stream);
+    rc = dmm::match_mix(Rb_out, masks_p, mask_dtype, B, N, M, HW, sp_b, sp_n, n_valid, m_valid, is_test, full_outmask, stream);
     if (rc != DMM_OK || !targets) return rc;
     return dmm_matching_loss_f32(w.inter2, w.area_p, w.area_t2, cos_out, B, N, M, n_valid, m_valid, gt_out, cost_loss,
                                  stream);

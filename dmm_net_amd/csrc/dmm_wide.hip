@@ -553,12 +553,9 @@ __global__ __launch_bounds__(kWideRegThreads) void relax_match_wide_reg_kernel(
     }
 }
 
-int launch_relax_match_wide(const float *cos_in, const int32_t *inter, const int32_t *area_p, const int32_t *area_t,
-                            const float *score_p, int B, int N, int M, const int32_t *n_valid, const int32_t *m_valid,
-                            float w_feat, float w_iou, RelaxParams prm, int is_test, float *sim_out, float *R_out,
-                            float *Rb_out, float *match_score, float *det_score, int32_t *iters_out, float *X_final,
+int launch_relax_match_wide(const SolveIn &in, float w_feat, float w_iou, RelaxParams prm, int is_test, const SolveOut &out,
                             float *scratch, hipStream_t stream) {
-    const int PpS = N > M ? N : M + 1;
+    const int B = in.B, M = in.M, PpS = padded_width(in.N, M);
     const int64_t stride = (int64_t)wide_scratch_floats(M, PpS);
     // register-resident form while a thread's share of the table is <= 12 elements and the two LDS tables fit
     {
@@ -572,9 +569,8 @@ int launch_relax_match_wide(const float *cos_in, const int32_t *inter, const int
                                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_reg);               \
             if (e != hipSuccess) { set_last_hip_error((int)e); return DMM_ERR_LAUNCH; }                                 \
         }                                                                                                               \
-        hipLaunchKernelGGL(relax_match_wide_reg_kernel<K_>, dim3(B), dim3(kWideRegThreads), lds_reg, stream, cos_in,    \
-                           inter, area_p, area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm, is_test, sim_out, \
-                           R_out, Rb_out, match_score, det_score, iters_out, X_final, scratch, stride);                 \
+        hipLaunchKernelGGL(relax_match_wide_reg_kernel<K_>, dim3(B), dim3(kWideRegThreads), lds_reg, stream,            \
+                           DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final, scratch, stride);        \
     } while (0)
             if (cap <= 8 * (size_t)kWideRegThreads) DMM_WREG(8);
             else if (cap <= 16 * (size_t)kWideRegThreads) DMM_WREG(16);
@@ -593,9 +589,8 @@ int launch_relax_match_wide(const float *cos_in, const int32_t *inter, const int
                                            (int)lds);
         if (e != hipSuccess) { set_last_hip_error((int)e); return DMM_ERR_LAUNCH; }
     }
-    hipLaunchKernelGGL(relax_match_wide_kernel, dim3(B), dim3(kWideSolverThreads), lds, stream, cos_in, inter, area_p,
-                       area_t, score_p, N, M, n_valid, m_valid, w_feat, w_iou, prm, is_test, sim_out, R_out, Rb_out,
-                       match_score, det_score, iters_out, X_final, scratch, stride, x_in_lds);
+    hipLaunchKernelGGL(relax_match_wide_kernel, dim3(B), dim3(kWideSolverThreads), lds, stream,
+                       DMM_SOLVE_KARGS(in, w_feat, w_iou, prm, is_test, out), out.X_final, scratch, stride, x_in_lds);
     return check_launch();
 }
 
