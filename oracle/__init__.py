@@ -52,6 +52,8 @@ def lib():
         L.dmmo_greedy_init.restype = None
         L.dmmo_relax.argtypes = [_f32p, c_int, c_int, c_int, c_int, c_float, _vp, _vp, _vp, _vp, _vp]
         L.dmmo_relax.restype = c_int
+        L.dmmo_relax_gates.argtypes = L.dmmo_relax.argtypes + [_vp, _vp]
+        L.dmmo_relax_gates.restype = c_int
         L.dmmo_matching_loss.argtypes = [_f32p, c_int, _f32p, c_int, c_int, _f32p, _vp, _vp]
         L.dmmo_matching_loss.restype = c_float
         L.dmmo_match_forward.argtypes = [_f32p, _f32p, _f32p, _f32p, _f32p, c_int, c_int, c_int, c_int,
@@ -118,8 +120,13 @@ def greedy_init(C):
     return idx
 
 
-def relax(C, max_iter, proj_iter, lr, want_xlist=False):
-    """relax_matching (relax_match.py:36-105).  Returns dict(X, R, cost, iters, xlist, inner)."""
+def relax(C, max_iter, proj_iter, lr, want_xlist=False, gates=None):
+    """relax_matching (relax_match.py:36-105).  Returns dict(X, R, cost, iters, xlist, inner).
+
+    ``gates``: None, or a dict the caller allocated with ``gate_record(n, m, max_iter, proj_iter)`` -- the run then records
+    in it, per projection sweep, which elements of ``X + P0`` passed the relu and which columns had ``col_sum <= 1`` (what
+    the device's tape holds).  Sweep j of outer iteration i is slot ``[i, j]``; slots past ``inner[i]`` / ``iters`` are
+    not written.  The results are the same bits with or without it."""
     C = _c(C)
     n, m = C.shape
     X = np.zeros((n, m), np.float32)
@@ -127,10 +134,21 @@ def relax(C, max_iter, proj_iter, lr, want_xlist=False):
     cost = np.zeros(max_iter + 1, np.float32)
     xl = np.zeros((max_iter + 1, n, m), np.float32) if want_xlist else None
     inner = np.zeros(max(max_iter, 1), np.int32)
-    iters = lib().dmmo_relax(C, n, m, int(max_iter), int(proj_iter), float(lr),
-                             _ptr(X), _ptr(R), _ptr(cost), _ptr(xl), _ptr(inner))
+    args = (C, n, m, int(max_iter), int(proj_iter), float(lr), _ptr(X), _ptr(R), _ptr(cost), _ptr(xl), _ptr(inner))
+    if gates is None:
+        iters = lib().dmmo_relax(*args)
+    else:
+        relu, col = gates["relu"], gates["col"]
+        assert relu.dtype == np.uint8 and relu.flags.c_contiguous and relu.shape == (max_iter, proj_iter, n, m), relu.shape
+        assert col.dtype == np.uint8 and col.flags.c_contiguous and col.shape == (max_iter, proj_iter, m), col.shape
+        iters = lib().dmmo_relax_gates(*args, _ptr(relu), _ptr(col))
     return dict(X=X, R=R, cost=cost[:iters + 1], iters=iters,
                 xlist=None if xl is None else xl[:iters + 1], inner=inner[:iters])
+
+
+def gate_record(n, m, max_iter, proj_iter):
+    """Room for ``relax(..., gates=)``: relu [max_iter, proj_iter, n, m] and col [max_iter, proj_iter, m], uint8."""
+    return dict(relu=np.zeros((max_iter, proj_iter, n, m), np.uint8), col=np.zeros((max_iter, proj_iter, m), np.uint8))
 
 
 def matching_loss(prop_mask, targets, feature_sim):

@@ -263,10 +263,18 @@ DMMO_API void dmmo_greedy_init(const float *C, int n, int m, int32_t *idx) {
  * cost_out [max_iter+1] (cost[0] = 0); xlist_out [(max_iter+1)*n*m];
  * inner_sweeps_out [max_iter] sweeps executed per outer iteration.
  * Returns the number of executed outer iterations (= len(X_list) - 1).
+ *
+ * dmmo_relax_gates additionally records the gates of every projection sweep it ran -- what
+ * the device's tape holds ("Training call"): slot s = it * proj_iter + j of
+ * relu_gate_out [max_iter*proj_iter][n*m] is 1 where X + P0 > 0 (the relu passes), of
+ * col_gate_out [max_iter*proj_iter][m] is 1 where col_sum <= 1 (the column is left alone).
+ * Slots of sweeps that did not run are not written.  Either may be NULL; the arithmetic does
+ * not depend on them.
  * ---------------------------------------------------------------------------------- */
-DMMO_API int dmmo_relax(const float *C, int n, int m, int max_iter, int proj_iter, float lr,
-                        float *X_out, float *R_mean_out, float *cost_out, float *xlist_out,
-                        int32_t *inner_sweeps_out) {
+DMMO_API int dmmo_relax_gates(const float *C, int n, int m, int max_iter, int proj_iter, float lr,
+                              float *X_out, float *R_mean_out, float *cost_out, float *xlist_out,
+                              int32_t *inner_sweeps_out, uint8_t *relu_gate_out,
+                              uint8_t *col_gate_out) {
     const int cnt = n * m;
     float *buf = (float *)calloc((size_t)cnt * 8 + m, sizeof(float));
     float *X = buf, *Y = buf + cnt, *P0 = buf + 2 * cnt, *P1 = buf + 3 * cnt, *P2 = buf + 4 * cnt,
@@ -303,11 +311,13 @@ DMMO_API int dmmo_relax(const float *C, int n, int m, int max_iter, int proj_ite
                 float y = x > 0.0f ? x : 0.0f;
                 P0[i] = x - y;
                 Y[i] = y;
+                if (relu_gate_out) relu_gate_out[((size_t)it * proj_iter + j) * cnt + i] = x > 0.0f;
             }
             /* column set (:78-80, project_col :21-34) */
             for (int i = 0; i < cnt; ++i) X[i] = Y[i] + P1[i];
             t_outer_sum(X, n, m, m, cs);
             for (int c = 0; c < m; ++c) {
+                if (col_gate_out) col_gate_out[((size_t)it * proj_iter + j) * m + c] = cs[c] <= 1.0f;
                 if (cs[c] <= 1.0f) {
                     for (int r = 0; r < n; ++r) Y[r * m + c] = X[r * m + c];
                 } else {
@@ -338,6 +348,13 @@ DMMO_API int dmmo_relax(const float *C, int n, int m, int max_iter, int proj_ite
         for (int i = 0; i < cnt; ++i) R_mean_out[i] = acc[i] / (float)len;
     free(buf);
     return len - 1;
+}
+
+DMMO_API int dmmo_relax(const float *C, int n, int m, int max_iter, int proj_iter, float lr,
+                        float *X_out, float *R_mean_out, float *cost_out, float *xlist_out,
+                        int32_t *inner_sweeps_out) {
+    return dmmo_relax_gates(C, n, m, max_iter, proj_iter, lr, X_out, R_mean_out, cost_out, xlist_out,
+                            inner_sweeps_out, NULL, NULL);
 }
 
 /* ------------------------------------------------------------------------------------
