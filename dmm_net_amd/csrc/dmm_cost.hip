@@ -626,15 +626,13 @@ static int launch_tl(const T *masks_p, const T *masks_t, const T *masks_t2, int 
     return check_launch();
 }
 
-// set (per thread, for the duration of one call) by iou_counts_prezeroed
-static thread_local bool g_tables_prezeroed = false;
-
+// tables_zeroed: the caller has cleared every table on this stream already (iou_counts_prezeroed / _dual_prezeroed)
 template <typename T>
 static int iou_counts_typed(const T *masks_p, const T *masks_t, const T *masks_t2, int B, int N, int M, int HW,
                             int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
                             const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
-                            int32_t *area_t, int32_t *inter2, int32_t *area_t2, hipStream_t stream) {
-    if (g_tables_prezeroed) {
+                            int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zeroed, hipStream_t stream) {
+    if (tables_zeroed) {
         // dmm_match_forward / dmm_match_train_forward: the feature-similarity launch in front of this one already cleared
         // the tables (all five of them in the dual form)
     } else if (area_p == inter + (size_t)B * M * N && area_t == area_p + (size_t)B * N) {
@@ -645,7 +643,7 @@ static int iou_counts_typed(const T *masks_p, const T *masks_t, const T *masks_t
         DMM_HIP_TRY(zero_async(area_p, sizeof(int32_t) * (size_t)B * N, stream));
         DMM_HIP_TRY(zero_async(area_t, sizeof(int32_t) * (size_t)B * M, stream));
     }
-    if (masks_t2 && !g_tables_prezeroed) {
+    if (masks_t2 && !tables_zeroed) {
         DMM_HIP_TRY(zero_async(inter2, sizeof(int32_t) * (size_t)B * M * N, stream));
         DMM_HIP_TRY(zero_async(area_t2, sizeof(int32_t) * (size_t)B * M, stream));
     }
@@ -713,7 +711,7 @@ static int iou_counts_dispatch(const void *masks_p, const void *masks_t, const v
                                int M, int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b,
                                int64_t st2_m, const int32_t *n_valid, const int32_t *m_valid, int32_t *inter,
                                int32_t *area_p, int32_t *area_t, int32_t *inter2, int32_t *area_t2,
-                               dmm_stream_t stream) {
+                               bool tables_zeroed, dmm_stream_t stream) {
     if (B < 0 || N < 0 || M < 0 || HW < 0) return DMM_ERR_BAD_ARG;
     if (B == 0 || N == 0 || M == 0) return DMM_OK;
     if (!masks_p || !masks_t || !inter || !area_p || !area_t) return DMM_ERR_BAD_ARG;
@@ -731,7 +729,8 @@ static int iou_counts_dispatch(const void *masks_p, const void *masks_t, const v
                 masks_t2 ? (const char *)masks_t2 + es * (size_t)b0 * st2_b : nullptr, dtype, nb, N, M, HW, sp_b, sp_n,
                 st_b, st_m, st2_b, st2_m, n_valid ? n_valid + b0 : nullptr, m_valid ? m_valid + b0 : nullptr,
                 inter + (size_t)b0 * M * N, area_p + (size_t)b0 * N, area_t + (size_t)b0 * M,
-                inter2 ? inter2 + (size_t)b0 * M * N : nullptr, area_t2 ? area_t2 + (size_t)b0 * M : nullptr, stream);
+                inter2 ? inter2 + (size_t)b0 * M * N : nullptr, area_t2 ? area_t2 + (size_t)b0 * M : nullptr, tables_zeroed,
+                stream);
             if (rc != DMM_OK) return rc;
         }
         return DMM_OK;
@@ -742,21 +741,21 @@ static int iou_counts_dispatch(const void *masks_p, const void *masks_t, const v
             return dmm::iou_counts_typed<dmm::packed_t>((const dmm::packed_t *)masks_p, (const dmm::packed_t *)masks_t,
                                                         (const dmm::packed_t *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b,
                                                         st_m, st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t,
-                                                        inter2, area_t2, s);
+                                                        inter2, area_t2, tables_zeroed, s);
         case DMM_F32:
             return dmm::iou_counts_typed<float>((const float *)masks_p, (const float *)masks_t, (const float *)masks_t2, B,
                                                 N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, n_valid, m_valid, inter,
-                                                area_p, area_t, inter2, area_t2, s);
+                                                area_p, area_t, inter2, area_t2, tables_zeroed, s);
         case DMM_F16:
             return dmm::iou_counts_typed<dmm::f16_t>((const dmm::f16_t *)masks_p, (const dmm::f16_t *)masks_t,
                                                      (const dmm::f16_t *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m,
                                                      st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2,
-                                                     area_t2, s);
+                                                     area_t2, tables_zeroed, s);
         case DMM_BF16:
             return dmm::iou_counts_typed<dmm::bf16_t>((const dmm::bf16_t *)masks_p, (const dmm::bf16_t *)masks_t,
                                                       (const dmm::bf16_t *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m,
                                                       st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2,
-                                                      area_t2, s);
+                                                      area_t2, tables_zeroed, s);
         default:
             return DMM_ERR_BAD_ARG;
     }
@@ -767,7 +766,7 @@ extern "C" int dmm_iou_counts(const void *masks_p, const void *masks_t, int dtyp
                               const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t,
                               dmm_stream_t stream) {
     return iou_counts_dispatch(masks_p, masks_t, nullptr, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, 0, 0, n_valid,
-                               m_valid, inter, area_p, area_t, nullptr, nullptr, stream);
+                               m_valid, inter, area_p, area_t, nullptr, nullptr, false, stream);
 }
 
 // dmm_iou_counts for a caller that has ALREADY zeroed inter / area_p / area_t on this stream (dmm_match_forward: the
@@ -776,11 +775,8 @@ namespace dmm {
 int iou_counts_prezeroed(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW, int64_t sp_b,
                          int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid, const int32_t *m_valid,
                          int32_t *inter, int32_t *area_p, int32_t *area_t, dmm_stream_t stream) {
-    g_tables_prezeroed = true;
-    const int rc = dmm_iou_counts(masks_p, masks_t, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, n_valid, m_valid, inter,
-                                  area_p, area_t, stream);
-    g_tables_prezeroed = false;
-    return rc;
+    return iou_counts_dispatch(masks_p, masks_t, nullptr, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, 0, 0, n_valid,
+                               m_valid, inter, area_p, area_t, nullptr, nullptr, true, stream);
 }
 // the dual form (templates + targets) on tables the caller has already zeroed; sp_b may be kFrameTable (masks_p = the
 // device table of per-frame base pointers)
@@ -788,11 +784,8 @@ int iou_counts_dual_prezeroed(const void *masks_p, const void *masks_t, const vo
                               int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
                               const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
                               int32_t *area_t, int32_t *inter2, int32_t *area_t2, dmm_stream_t stream) {
-    g_tables_prezeroed = true;
-    const int rc = iou_counts_dispatch(masks_p, masks_t, masks_t2, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m,
-                                       n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, stream);
-    g_tables_prezeroed = false;
-    return rc;
+    return iou_counts_dispatch(masks_p, masks_t, masks_t2, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m,
+                               n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, true, stream);
 }
 }  // namespace dmm
 
@@ -803,7 +796,7 @@ extern "C" int dmm_iou_counts_dual(const void *masks_p, const void *masks_t, con
                                    dmm_stream_t stream) {
     if (!masks_t2) return DMM_ERR_BAD_ARG;
     return iou_counts_dispatch(masks_p, masks_t, masks_t2, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m,
-                               n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, stream);
+                               n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, false, stream);
 }
 
 // ---- per-frame pointer tables for the proposal planes (the per-video tensors of DMM_Model: no batch copy) ----
@@ -812,7 +805,7 @@ extern "C" int dmm_iou_counts_frames(const void *const *masks_p_frames, const vo
                                      const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t,
                                      dmm_stream_t stream) {
     return iou_counts_dispatch((const void *)masks_p_frames, masks_t, nullptr, dtype, B, N, M, HW, dmm::kFrameTable, sp_n,
-                               st_b, st_m, 0, 0, n_valid, m_valid, inter, area_p, area_t, nullptr, nullptr, stream);
+                               st_b, st_m, 0, 0, n_valid, m_valid, inter, area_p, area_t, nullptr, nullptr, false, stream);
 }
 
 extern "C" int dmm_iou_counts_dual_frames(const void *const *masks_p_frames, const void *masks_t, const void *masks_t2,
@@ -823,5 +816,5 @@ extern "C" int dmm_iou_counts_dual_frames(const void *const *masks_p_frames, con
     if (!masks_t2) return DMM_ERR_BAD_ARG;
     return iou_counts_dispatch((const void *)masks_p_frames, masks_t, masks_t2, dtype, B, N, M, HW, dmm::kFrameTable,
                                sp_n, st_b, st_m, st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2, area_t2,
-                               stream);
+                               false, stream);
 }

@@ -21,7 +21,8 @@ int front_small_launch(const void *masks_p, const void *masks_t, const void *mas
                        const float *feat_p, int B, int N, int M, int HW, int D, int64_t sp_b, int64_t sp_n, int64_t st_b,
                        int64_t st_m, int64_t st2_b, int64_t st2_m, float *cos_out, int32_t *inter, int32_t *area_p,
                        int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zero, hipStream_t stream);
-// dmm_cost.hip: dmm_iou_counts / dmm_iou_counts_dual on tables the caller has already cleared on this stream
+// dmm_cost.hip: dmm_iou_counts / dmm_iou_counts_dual on tables the caller has already cleared on this stream (the
+// dispatch behind every count entry with tables_zeroed = true)
 int iou_counts_prezeroed(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW, int64_t sp_b,
                          int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid, const int32_t *m_valid,
                          int32_t *inter, int32_t *area_p, int32_t *area_t, dmm_stream_t stream);
@@ -29,7 +30,8 @@ int iou_counts_dual_prezeroed(const void *masks_p, const void *masks_t, const vo
                               int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
                               const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
                               int32_t *area_t, int32_t *inter2, int32_t *area_t2, dmm_stream_t stream);
-// dmm_mix.hip: dmm_mask_mix_bwd into a dRb the caller has already cleared
+// dmm_mix.hip: dmm_mask_mix_bwd into a dRb the caller has already cleared (the backward behind every mix entry with
+// MixBwd::drb_zeroed set)
 int mask_mix_bwd_prezeroed(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M, int Pp,
                            int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, float *dRb,
                            dmm_stream_t stream);

@@ -15,8 +15,29 @@
 namespace dmm {
 
 constexpr int kMixThreads = 256;
-static thread_local bool g_drb_prezeroed = false;     // set (per thread, for one call) by mask_mix_bwd_prezeroed: dRb is zero already
-static thread_local bool g_mix_shared_call = false;   // set by dmm_mask_mix_shared_* around the common entry point
+
+// ---- host-side argument bundles of the mix launchers (the kernels' own signatures spell the lists out) ----
+struct MixArgs {
+    const float *Rb;                        // [B, M, Pp] weights
+    const void *masks_p;                    // planes of `dtype`; sp_b == kFrameTable: the device table of per-frame bases
+    int dtype;
+    int B, N, M, Pp, HW;
+    int64_t sp_b, sp_n;
+    const int32_t *n_valid, *m_valid;       // live proposals / templates per frame (null: all)
+    hipStream_t stream;
+};
+struct MixFwd : MixArgs {
+    void *out;                              // [B, M, HW] of out_dtype: fp32, or the planes' own 16-bit type
+    int out_dtype;
+    int64_t so_b, so_m;
+    bool shared_entry;                      // called through dmm_mask_mix_shared_*: the rows share planes
+};
+struct MixBwd : MixArgs {
+    const float *dout;
+    float *dRb;
+    bool drb_zeroed;                        // the caller has cleared dRb on this stream already
+    float *slab;                            // the deterministic form's per-workgroup planes; null: atomics into dRb
+};
 
 // ---------------------------------------------------------------------------------------------
 // One workgroup = one output row m of one frame over a pixel range.
@@ -334,22 +355,21 @@ static inline int mix_bwd_row_splits(int B, int M, int HW, int &steps_per_wg) {
     return (nsteps + steps_per_wg - 1) / steps_per_wg;
 }
 
+// a.slab (zeroed by the caller) takes each workgroup's partial in a plane of its own; without it the partials go into dRb
 template <typename T>
-static int mask_mix_bwd_typed(const float *Rb, const T *masks_p, const float *dout, int B, int N, int M, int Pp, int HW,
-                              int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, float *dRb,
-                              hipStream_t stream) {
-    if (!g_drb_prezeroed) DMM_HIP_TRY(zero_async(dRb, sizeof(float) * (size_t)B * M * Pp, stream));
+static int mask_mix_bwd_typed(const MixBwd &a, const T *masks_p) {
+    if (!a.slab && !a.drb_zeroed) DMM_HIP_TRY(zero_async(a.dRb, sizeof(float) * (size_t)a.B * a.M * a.Pp, a.stream));
     int steps_per_wg;
-    const int splits = mix_bwd_row_splits(B, M, HW, steps_per_wg);
-    hipLaunchKernelGGL((mask_mix_bwd_kernel<T>), dim3(splits, M, B), dim3(kMixThreads), 0, stream, Rb, masks_p, dout, N, M,
-                       Pp, HW, sp_b, sp_n, n_valid, m_valid, dRb, steps_per_wg);
+    const int splits = mix_bwd_row_splits(a.B, a.M, a.HW, steps_per_wg);
+    const auto kernel = a.slab ? mask_mix_bwd_kernel<T, true> : mask_mix_bwd_kernel<T, false>;
+    hipLaunchKernelGGL(kernel, dim3(splits, a.M, a.B), dim3(kMixThreads), 0, a.stream, a.Rb, masks_p, a.dout, a.N, a.M, a.Pp,
+                       a.HW, a.sp_b, a.sp_n, a.n_valid, a.m_valid, a.slab ? a.slab : a.dRb, steps_per_wg);
     return check_launch();
 }
 
 template <typename T, typename TO>
-static int mask_mix_typed(const float *Rb, const T *masks_p, int B, int N, int M, int Pp, int HW, int64_t sp_b,
-                          int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, TO *out, int64_t so_b,
-                          int64_t so_m, hipStream_t stream) {
+static int mask_mix_typed(const MixFwd &a, const T *masks_p, TO *out) {
+    const int B = a.B, M = a.M, HW = a.HW;
     constexpr int E = 16 / (int)sizeof(T);
     const int align_bytes = opt(DMM_OPT_MIX_ALIGN);
     const int align_mask = align_bytes / (int)sizeof(TO) - 1;
@@ -369,8 +389,9 @@ static int mask_mix_typed(const float *Rb, const T *masks_p, int B, int N, int M
     const int nt_mode = opt(DMM_OPT_MIX_NT);
     const int xcd_remap = opt(DMM_OPT_MIX_XCD);
 #define DMM_MIX_LAUNCH(NT)                                                                                              \
-    hipLaunchKernelGGL((mask_mix_rows_kernel<T, TO, NT>), dim3(splits, M, B), dim3(kMixThreads), 0, stream, Rb, masks_p, \
-                       N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, out, so_b, so_m, steps_per_wg, align_mask, xcd_remap)
+    hipLaunchKernelGGL((mask_mix_rows_kernel<T, TO, NT>), dim3(splits, M, B), dim3(kMixThreads), 0, a.stream, a.Rb,    \
+                       masks_p, a.N, M, a.Pp, HW, a.sp_b, a.sp_n, a.n_valid, a.m_valid, out, a.so_b, a.so_m, steps_per_wg, \
+                       align_mask, xcd_remap)
     switch (nt_mode & 3) {
         case 0: DMM_MIX_LAUNCH(0); break;
         case 1: DMM_MIX_LAUNCH(1); break;
@@ -519,10 +540,9 @@ __global__ __launch_bounds__(kMixThreads) void mask_mix_shared_kernel(const floa
 }
 
 template <typename T, typename TO>
-static int mask_mix_shared_typed(const float *Rb, const T *masks_p, int B, int N, int M, int Pp, int HW, int64_t sp_b,
-                                 int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, TO *out, int64_t so_b,
-                                 int64_t so_m, hipStream_t stream) {
-    const int nsteps = (HW + kMixThreads * 4 - 1) / (kMixThreads * 4);
+static int mask_mix_shared_typed(const MixFwd &a, const T *masks_p, TO *out) {
+    const int M = a.M;
+    const int nsteps = (a.HW + kMixThreads * 4 - 1) / (kMixThreads * 4);
     // ONE step (4 KiB of every plane of the union) per workgroup: the access-pattern probe (tools/mix_shared_probe.py) loses
     // 4 % / 8 % with 2 / 4 steps per workgroup, whatever the batch (DMM_OPT_MIX_SHARED_STEPS)
     int steps_per_wg = opt(DMM_OPT_MIX_SHARED_STEPS);
@@ -530,9 +550,9 @@ static int mask_mix_shared_typed(const float *Rb, const T *masks_p, int B, int N
     const int splits = (nsteps + steps_per_wg - 1) / steps_per_wg;
     const int nt_mode = opt(DMM_OPT_MIX_NT);
 #define DMM_MIXS_LAUNCH(MT_, NT_)                                                                                       \
-    hipLaunchKernelGGL((mask_mix_shared_kernel<T, TO, MT_, NT_>), dim3(splits, B), dim3(kMixThreads), 0, stream, Rb,    \
-                       masks_p, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, out, so_b, so_m, steps_per_wg,               \
-                       opt(DMM_OPT_MIX_SHARED_LOCKSTEP), (opt(DMM_OPT_MIX_XCD) >> 1) & 1)
+    hipLaunchKernelGGL((mask_mix_shared_kernel<T, TO, MT_, NT_>), dim3(splits, a.B), dim3(kMixThreads), 0, a.stream,    \
+                       a.Rb, masks_p, a.N, M, a.Pp, a.HW, a.sp_b, a.sp_n, a.n_valid, a.m_valid, out, a.so_b, a.so_m,     \
+                       steps_per_wg, opt(DMM_OPT_MIX_SHARED_LOCKSTEP), (opt(DMM_OPT_MIX_XCD) >> 1) & 1)
 #define DMM_MIXS_PICK(MT_)                       \
     do {                                         \
         if ((nt_mode & 3) == 3) DMM_MIXS_LAUNCH(MT_, 3); \
@@ -743,25 +763,23 @@ static inline int mix_bwd_shared_splits(int B, int HW, int &steps_per_wg) {
     return (nsteps + steps_per_wg - 1) / steps_per_wg;
 }
 
+// a.slab: as in mask_mix_bwd_typed
 template <typename T>
-static int mask_mix_bwd_shared_typed(const float *Rb, const T *masks_p, const float *dout, int B, int N, int M, int Pp,
-                                     int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid,
-                                     float *dRb, hipStream_t stream) {
-    if (!g_drb_prezeroed) DMM_HIP_TRY(zero_async(dRb, sizeof(float) * (size_t)B * M * Pp, stream));
+static int mask_mix_bwd_shared_typed(const MixBwd &a, const T *masks_p) {
+    if (!a.slab && !a.drb_zeroed) DMM_HIP_TRY(zero_async(a.dRb, sizeof(float) * (size_t)a.B * a.M * a.Pp, a.stream));
     int steps_per_wg;
-    const int splits = mix_bwd_shared_splits(B, HW, steps_per_wg);
-#define DMM_MIXB_LAUNCH(MT_)                                                                                        \
-    hipLaunchKernelGGL((mask_mix_bwd_shared_kernel<T, MT_>), dim3(splits, B), dim3(kMixThreads),                    \
-                       mix_bwd_dynamic_lds(N, MT_), stream, Rb, masks_p, dout, N, M, Pp, HW,                         \
-                       sp_b, sp_n, n_valid, m_valid, dRb, steps_per_wg, opt(DMM_OPT_MIX_SHARED_LOCKSTEP),               \
-                       (opt(DMM_OPT_MIX_XCD) >> 2) & 1)
-    if (M <= 8) DMM_MIXB_LAUNCH(8);
-    else if (M <= 16) DMM_MIXB_LAUNCH(16);
+    const int splits = mix_bwd_shared_splits(a.B, a.HW, steps_per_wg);
+#define DMM_MIXB_LAUNCH(MT_)                                                                                             \
+    hipLaunchKernelGGL((a.slab ? mask_mix_bwd_shared_kernel<T, MT_, true> : mask_mix_bwd_shared_kernel<T, MT_, false>),  \
+                       dim3(splits, a.B), dim3(kMixThreads), mix_bwd_dynamic_lds(a.N, MT_), a.stream, a.Rb, masks_p,     \
+                       a.dout, a.N, a.M, a.Pp, a.HW, a.sp_b, a.sp_n, a.n_valid, a.m_valid, a.slab ? a.slab : a.dRb,      \
+                       steps_per_wg, opt(DMM_OPT_MIX_SHARED_LOCKSTEP), (opt(DMM_OPT_MIX_XCD) >> 2) & 1)
+    if (a.M <= 8) DMM_MIXB_LAUNCH(8);
+    else if (a.M <= 16) DMM_MIXB_LAUNCH(16);
     else DMM_MIXB_LAUNCH(32);
 #undef DMM_MIXB_LAUNCH
     return check_launch();
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // The mix for ANY N, M (tables outside the fast kernel's envelope: it compacts a row's weights into a 256-entry LDS list
@@ -824,107 +842,157 @@ __global__ __launch_bounds__(256) void mask_mix_bwd_wide_kernel(const float *__r
 }
 
 template <typename T>
-static int mask_mix_bwd_wide_typed(const float *Rb, const T *masks_p, const float *dout, int B, int N, int M, int Pp, int HW,
-                                   int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, float *dRb,
-                                   hipStream_t stream) {
-    if (Pp > N && !g_drb_prezeroed) DMM_HIP_TRY(zero_async(dRb, sizeof(float) * (size_t)B * M * Pp, stream));   // the padded columns
-    hipLaunchKernelGGL((mask_mix_bwd_wide_kernel<T>), dim3(N, M, B), dim3(256), 0, stream, Rb, masks_p, dout, N, M, Pp, HW,
-                       sp_b, sp_n, n_valid, m_valid, dRb);
+static int mask_mix_bwd_wide_typed(const MixBwd &a, const T *masks_p) {
+    if (a.Pp > a.N && !a.drb_zeroed)                                              // the padded columns
+        DMM_HIP_TRY(zero_async(a.dRb, sizeof(float) * (size_t)a.B * a.M * a.Pp, a.stream));
+    hipLaunchKernelGGL((mask_mix_bwd_wide_kernel<T>), dim3(a.N, a.M, a.B), dim3(256), 0, a.stream, a.Rb, masks_p, a.dout,
+                       a.N, a.M, a.Pp, a.HW, a.sp_b, a.sp_n, a.n_valid, a.m_valid, a.dRb);
     return check_launch();
 }
 
 template <typename T, typename TO>
-static int mask_mix_wide_typed(const float *Rb, const T *masks_p, int B, int N, int M, int Pp, int HW, int64_t sp_b,
-                               int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, TO *out, int64_t so_b,
-                               int64_t so_m, hipStream_t stream) {
-    hipLaunchKernelGGL((mask_mix_wide_kernel<T, TO>), dim3((HW + 255) / 256, M, B), dim3(256), 0, stream, Rb, masks_p, N, M,
-                       Pp, HW, sp_b, sp_n, n_valid, m_valid, out, so_b, so_m);                 // (M, B <= 65535: caller)
+static int mask_mix_wide_typed(const MixFwd &a, const T *masks_p, TO *out) {
+    hipLaunchKernelGGL((mask_mix_wide_kernel<T, TO>), dim3((a.HW + 255) / 256, a.M, a.B), dim3(256), 0, a.stream, a.Rb,
+                       masks_p, a.N, a.M, a.Pp, a.HW, a.sp_b, a.sp_n, a.n_valid, a.m_valid, out, a.so_b,
+                       a.so_m);                                                    // (M, B <= 65535: the entry check)
     return check_launch();
+}
+
+// ---- deterministic dRb: the fast kernels' decomposition, each workgroup's partials stored to a slab plane of its own, then one
+// fold in plane order (no arrival-order sums).  Tables outside the fast envelope take the wide kernel (deterministic as it is).
+__global__ __launch_bounds__(256) void mix_slab_fold_kernel(const float *__restrict__ slab, int planes, int64_t n,
+                                                            float *__restrict__ dRb) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float a = 0.0f;
+    for (int p = 0; p < planes; ++p) a += slab[(int64_t)p * n + i];
+    dRb[i] = a;
+}
+
+// ---- which kernel serves a call: the whole rule of each direction, here and nowhere else ----
+enum class MixKind { Wide, Union, Rows };
+
+static inline bool mix_wide(int N, int M) {                               // any N, M: the general kernel (tests: everywhere)
+    return M > DMM_MAX_TEMPLATES || N > DMM_MAX_PROPOSALS || opt(DMM_OPT_FORCE_WIDE) == 1;
+}
+// rows that share planes (train mode): DMM_OPT_MIX_SHARED -1 = the caller's entry point decides (dmm_mask_mix_shared_*),
+// 0 = row kernel always, 1 = union kernel always (tests pin both: bit-identical)
+static MixKind mix_fwd_kind(int N, int M, bool shared_entry) {
+    if (mix_wide(N, M)) return MixKind::Wide;
+    const int shared_opt = opt(DMM_OPT_MIX_SHARED);
+    return shared_opt == 1 || (shared_opt < 0 && shared_entry) ? MixKind::Union : MixKind::Rows;
+}
+// default: planes of the union streamed once.  The union kernel's four per-wave pair tables share ONE dynamic block with
+// its slot slabs (mix_bwd_dynamic_lds: the larger of the two) beside ~3.1 KB of static tables: 4 * N * mt floats <= 56 KB
+// keeps the workgroup under the 64 KB a launch gets without an attribute (everything up to 112 proposals x 32 rows or
+// 224 x 16; wider tables: the row kernel).  Both edges are in the tests.
+static MixKind mix_bwd_kind(int N, int M) {
+    if (mix_wide(N, M)) return MixKind::Wide;
+    const int mt = M <= 8 ? 8 : (M <= 16 ? 16 : 32);
+    return opt(DMM_OPT_MIX_SHARED) != 0 && sizeof(float) * 4 * (size_t)N * mt <= 56 * 1024 ? MixKind::Union : MixKind::Rows;
+}
+// planes of the deterministic slab = pixel splits of the kernel that fills it (the wide kernel has none)
+static int mix_bwd_slab_planes(MixKind kind, int B, int M, int HW) {
+    int steps_per_wg;
+    if (kind == MixKind::Wide) return 0;
+    return kind == MixKind::Union ? mix_bwd_shared_splits(B, HW, steps_per_wg) : mix_bwd_row_splits(B, M, HW, steps_per_wg);
+}
+
+// The checks every mix entry starts with.  *go = true: go on; otherwise the return value is the entry's answer (DMM_OK:
+// nothing to do).  have_pointers: the direction's own mandatory pointers; empty_hw_ok: a call without pixels is answered
+// before the pointers are looked at (the forward; the backward still owes dRb its zeros).
+static int mix_entry_check(const MixArgs &a, bool have_pointers, bool empty_hw_ok, bool *go) {
+    *go = false;
+    if (a.B < 0 || a.N < 0 || a.M < 0 || a.HW < 0 || a.Pp < a.N) return DMM_ERR_BAD_ARG;
+    if (a.B == 0 || a.M == 0 || (empty_hw_ok && a.HW == 0)) return DMM_OK;
+    if (!a.Rb || !a.masks_p || !have_pointers) return DMM_ERR_BAD_ARG;
+    if (a.M > 65535 || a.B > 65535) return DMM_ERR_UNSUPPORTED;               // grid y / z
+    if (a.sp_n < a.HW) return DMM_ERR_BAD_ARG;
+    *go = true;
+    return DMM_OK;
+}
+
+// f(planes) with the planes as const float / f16_t / bf16_t * -- the one place a dtype becomes a type
+template <typename F>
+static int with_plane_type(int dtype, const void *masks_p, F &&f) {
+    switch (dtype) {
+        case DMM_F32: return f((const float *)masks_p);
+        case DMM_F16: return f((const f16_t *)masks_p);
+        case DMM_BF16: return f((const bf16_t *)masks_p);
+        default: return DMM_ERR_BAD_ARG;
+    }
+}
+
+// the forward behind every entry
+static int mask_mix_forward(const MixFwd &a) {
+    bool go;
+    const int rc = mix_entry_check(a, a.out != nullptr, /*empty_hw_ok=*/true, &go);
+    if (!go) return rc;
+    if (a.so_m < a.HW) return DMM_ERR_BAD_ARG;
+    if (a.out_dtype != DMM_F32 && a.out_dtype != a.dtype) return DMM_ERR_BAD_ARG;   // fp32, or the planes' own 16-bit type
+    const MixKind kind = mix_fwd_kind(a.N, a.M, a.shared_entry);
+    return with_plane_type(a.dtype, a.masks_p, [&](auto *planes) {
+        using T = std::remove_const_t<std::remove_pointer_t<decltype(planes)>>;
+        const auto launch = [&](auto *out) {                                  // out: float or T, no other pair is compiled
+            switch (kind) {
+                case MixKind::Wide: return mask_mix_wide_typed(a, planes, out);
+                case MixKind::Union: return mask_mix_shared_typed(a, planes, out);
+                default: return mask_mix_typed(a, planes, out);
+            }
+        };
+        return a.out_dtype == DMM_F32 ? launch((float *)a.out) : launch((T *)a.out);
+    });
+}
+
+// the deterministic form of the two fast kernels: zero the slab, fill it, fold it into dRb
+template <typename T>
+static int mask_mix_bwd_det_typed(const MixBwd &a, MixKind kind, int planes, const T *masks_p) {
+    const int64_t n = (int64_t)a.B * a.M * a.Pp;
+    DMM_HIP_TRY(zero_async(a.slab, sizeof(float) * (size_t)planes * n, a.stream));
+    const int rc = kind == MixKind::Union ? mask_mix_bwd_shared_typed(a, masks_p) : mask_mix_bwd_typed(a, masks_p);
+    if (rc != DMM_OK) return rc;
+    hipLaunchKernelGGL(mix_slab_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a.stream, (const float *)a.slab,
+                       planes, n, a.dRb);
+    // (checked, not counted: dmm_launch_count has always shown this entry as the clear and one launch)
+    DMM_HIP_TRY(hipGetLastError());
+    return DMM_OK;
+}
+
+// the backward behind every entry.  det: the deterministic form, a.slab = its workspace of slab_bytes
+static int mask_mix_backward(MixBwd a, bool det = false, size_t slab_bytes = 0) {
+    bool go;
+    const int rc = mix_entry_check(a, a.dout && a.dRb, /*empty_hw_ok=*/false, &go);
+    if (!go) return rc;
+    if (det && !soft_planes(a.dtype)) return DMM_ERR_BAD_ARG;                 // whatever the kind, before the workspace
+    const MixKind kind = mix_bwd_kind(a.N, a.M);
+    const int planes = det ? mix_bwd_slab_planes(kind, a.B, a.M, a.HW) : 0;
+    const size_t need = sizeof(float) * (size_t)planes * (size_t)a.B * a.M * a.Pp;
+    if (need && !a.slab) return DMM_ERR_BAD_ARG;
+    if (slab_bytes < need) return DMM_ERR_WORKSPACE;
+    if (kind == MixKind::Wide) a.slab = nullptr;                              // deterministic as it is
+    return with_plane_type(a.dtype, a.masks_p, [&](auto *planes_p) {
+        if (kind == MixKind::Wide) return mask_mix_bwd_wide_typed(a, planes_p);
+        if (det) return mask_mix_bwd_det_typed(a, kind, planes, planes_p);
+        return kind == MixKind::Union ? mask_mix_bwd_shared_typed(a, planes_p) : mask_mix_bwd_typed(a, planes_p);
+    });
+}
+
+// dmm_mask_mix_bwd for a caller that cleared dRb itself (dmm_match_train_backward: by the launch in front)
+int mask_mix_bwd_prezeroed(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M, int Pp,
+                           int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, float *dRb,
+                           dmm_stream_t stream) {
+    return mask_mix_backward({{Rb, masks_p, dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, (hipStream_t)stream}, dout,
+                              dRb, /*drb_zeroed=*/true, nullptr});
 }
 
 }  // namespace dmm
 
+// ---- the entries: each fills a bundle (or hands on to the entry it is a special case of) ----
 extern "C" int dmm_mask_mix_to(const float *Rb, const void *masks_p, int dtype, int B, int N, int M, int Pp, int HW,
                                int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, void *out,
                                int out_dtype, int64_t so_b, int64_t so_m, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || Pp < N) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0 || HW == 0) return DMM_OK;
-    if (!Rb || !masks_p || !out) return DMM_ERR_BAD_ARG;
-    if (M > 65535 || B > 65535) return DMM_ERR_UNSUPPORTED;
-    if (sp_n < HW || so_m < HW) return DMM_ERR_BAD_ARG;
-    if (out_dtype != DMM_F32 && out_dtype != dtype) return DMM_ERR_BAD_ARG;      // fp32, or the planes' own 16-bit type
-    hipStream_t s = (hipStream_t)stream;
-    if (M > DMM_MAX_TEMPLATES || N > DMM_MAX_PROPOSALS || dmm::opt(DMM_OPT_FORCE_WIDE) == 1) {   // tests: the general kernel everywhere
-        switch (dtype) {
-            case DMM_F32:
-                return dmm::mask_mix_wide_typed<float, float>(Rb, (const float *)masks_p, B, N, M, Pp, HW, sp_b, sp_n,
-                                                              n_valid, m_valid, (float *)out, so_b, so_m, s);
-            case DMM_F16:
-                if (out_dtype == DMM_F16)
-                    return dmm::mask_mix_wide_typed<dmm::f16_t, dmm::f16_t>(Rb, (const dmm::f16_t *)masks_p, B, N, M, Pp,
-                                                                            HW, sp_b, sp_n, n_valid, m_valid,
-                                                                            (dmm::f16_t *)out, so_b, so_m, s);
-                return dmm::mask_mix_wide_typed<dmm::f16_t, float>(Rb, (const dmm::f16_t *)masks_p, B, N, M, Pp, HW, sp_b,
-                                                                   sp_n, n_valid, m_valid, (float *)out, so_b, so_m, s);
-            case DMM_BF16:
-                if (out_dtype == DMM_BF16)
-                    return dmm::mask_mix_wide_typed<dmm::bf16_t, dmm::bf16_t>(Rb, (const dmm::bf16_t *)masks_p, B, N, M,
-                                                                              Pp, HW, sp_b, sp_n, n_valid, m_valid,
-                                                                              (dmm::bf16_t *)out, so_b, so_m, s);
-                return dmm::mask_mix_wide_typed<dmm::bf16_t, float>(Rb, (const dmm::bf16_t *)masks_p, B, N, M, Pp, HW,
-                                                                    sp_b, sp_n, n_valid, m_valid, (float *)out, so_b, so_m, s);
-            default:
-                return DMM_ERR_BAD_ARG;
-        }
-    }
-    // rows that share planes (train mode): DMM_OPT_MIX_SHARED -1 = the caller's entry point decides (dmm_mask_mix_shared_to),
-    // 0 = row kernel always, 1 = union kernel always (tests pin both: bit-identical)
-    const int shared_opt = dmm::opt(DMM_OPT_MIX_SHARED);
-    if (shared_opt == 1 || (shared_opt < 0 && dmm::g_mix_shared_call)) {
-        switch (dtype) {
-            case DMM_F32:
-                return dmm::mask_mix_shared_typed<float, float>(Rb, (const float *)masks_p, B, N, M, Pp, HW, sp_b, sp_n,
-                                                                n_valid, m_valid, (float *)out, so_b, so_m, s);
-            case DMM_F16:
-                if (out_dtype == DMM_F16)
-                    return dmm::mask_mix_shared_typed<dmm::f16_t, dmm::f16_t>(Rb, (const dmm::f16_t *)masks_p, B, N, M, Pp,
-                                                                              HW, sp_b, sp_n, n_valid, m_valid,
-                                                                              (dmm::f16_t *)out, so_b, so_m, s);
-                return dmm::mask_mix_shared_typed<dmm::f16_t, float>(Rb, (const dmm::f16_t *)masks_p, B, N, M, Pp, HW,
-                                                                     sp_b, sp_n, n_valid, m_valid, (float *)out, so_b,
-                                                                     so_m, s);
-            case DMM_BF16:
-                if (out_dtype == DMM_BF16)
-                    return dmm::mask_mix_shared_typed<dmm::bf16_t, dmm::bf16_t>(Rb, (const dmm::bf16_t *)masks_p, B, N, M,
-                                                                                Pp, HW, sp_b, sp_n, n_valid, m_valid,
-                                                                                (dmm::bf16_t *)out, so_b, so_m, s);
-                return dmm::mask_mix_shared_typed<dmm::bf16_t, float>(Rb, (const dmm::bf16_t *)masks_p, B, N, M, Pp, HW,
-                                                                      sp_b, sp_n, n_valid, m_valid, (float *)out, so_b,
-                                                                      so_m, s);
-            default:
-                return DMM_ERR_BAD_ARG;
-        }
-    }
-    switch (dtype) {
-        case DMM_F32:
-            return dmm::mask_mix_typed<float, float>(Rb, (const float *)masks_p, B, N, M, Pp, HW, sp_b, sp_n, n_valid,
-                                                     m_valid, (float *)out, so_b, so_m, s);
-        case DMM_F16:
-            if (out_dtype == DMM_F16)
-                return dmm::mask_mix_typed<dmm::f16_t, dmm::f16_t>(Rb, (const dmm::f16_t *)masks_p, B, N, M, Pp, HW, sp_b,
-                                                                   sp_n, n_valid, m_valid, (dmm::f16_t *)out, so_b, so_m, s);
-            return dmm::mask_mix_typed<dmm::f16_t, float>(Rb, (const dmm::f16_t *)masks_p, B, N, M, Pp, HW, sp_b, sp_n,
-                                                          n_valid, m_valid, (float *)out, so_b, so_m, s);
-        case DMM_BF16:
-            if (out_dtype == DMM_BF16)
-                return dmm::mask_mix_typed<dmm::bf16_t, dmm::bf16_t>(Rb, (const dmm::bf16_t *)masks_p, B, N, M, Pp, HW,
-                                                                     sp_b, sp_n, n_valid, m_valid, (dmm::bf16_t *)out,
-                                                                     so_b, so_m, s);
-            return dmm::mask_mix_typed<dmm::bf16_t, float>(Rb, (const dmm::bf16_t *)masks_p, B, N, M, Pp, HW, sp_b, sp_n,
-                                                           n_valid, m_valid, (float *)out, so_b, so_m, s);
-        default:
-            return DMM_ERR_BAD_ARG;
-    }
+    return dmm::mask_mix_forward({{Rb, masks_p, dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, (hipStream_t)stream},
+                                  out, out_dtype, so_b, so_m, /*shared_entry=*/false});
 }
 
 // (4d) the same product for weight tables whose rows share planes: every plane of the union of the supports is streamed
@@ -932,19 +1000,8 @@ extern "C" int dmm_mask_mix_to(const float *Rb, const void *masks_p, int dtype, 
 extern "C" int dmm_mask_mix_shared_to(const float *Rb, const void *masks_p, int dtype, int B, int N, int M, int Pp, int HW,
                                       int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid,
                                       void *out, int out_dtype, int64_t so_b, int64_t so_m, dmm_stream_t stream) {
-    dmm::g_mix_shared_call = true;
-    const int rc = dmm_mask_mix_to(Rb, masks_p, dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, out, out_dtype, so_b,
-                                   so_m, stream);
-    dmm::g_mix_shared_call = false;
-    return rc;
-}
-
-extern "C" int dmm_mask_mix_shared_frames(const float *Rb, const void *const *masks_p_frames, int dtype, int B, int N,
-                                          int M, int Pp, int HW, int64_t sp_n, const int32_t *n_valid,
-                                          const int32_t *m_valid, float *out, int64_t so_b, int64_t so_m,
-                                          dmm_stream_t stream) {
-    return dmm_mask_mix_shared_to(Rb, (const void *)masks_p_frames, dtype, B, N, M, Pp, HW, dmm::kFrameTable, sp_n, n_valid,
-                                  m_valid, out, DMM_F32, so_b, so_m, stream);
+    return dmm::mask_mix_forward({{Rb, masks_p, dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, (hipStream_t)stream},
+                                  out, out_dtype, so_b, so_m, /*shared_entry=*/true});
 }
 
 extern "C" int dmm_mask_mix(const float *Rb, const void *masks_p, int dtype, int B, int N, int M, int Pp, int HW,
@@ -957,61 +1014,21 @@ extern "C" int dmm_mask_mix(const float *Rb, const void *masks_p, int dtype, int
 extern "C" int dmm_mask_mix_bwd(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M,
                                 int Pp, int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid,
                                 const int32_t *m_valid, float *dRb, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || Pp < N) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (!Rb || !masks_p || !dout || !dRb) return DMM_ERR_BAD_ARG;
-    if (M > 65535 || B > 65535) return DMM_ERR_UNSUPPORTED;
-    if (sp_n < HW) return DMM_ERR_BAD_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (M > DMM_MAX_TEMPLATES || N > DMM_MAX_PROPOSALS || dmm::opt(DMM_OPT_FORCE_WIDE) == 1) {   // any N, M: the general kernel
-        switch (dtype) {
-            case DMM_F32:
-                return dmm::mask_mix_bwd_wide_typed<float>(Rb, (const float *)masks_p, dout, B, N, M, Pp, HW, sp_b, sp_n,
-                                                           n_valid, m_valid, dRb, s);
-            case DMM_F16:
-                return dmm::mask_mix_bwd_wide_typed<dmm::f16_t>(Rb, (const dmm::f16_t *)masks_p, dout, B, N, M, Pp, HW, sp_b,
-                                                                sp_n, n_valid, m_valid, dRb, s);
-            case DMM_BF16:
-                return dmm::mask_mix_bwd_wide_typed<dmm::bf16_t>(Rb, (const dmm::bf16_t *)masks_p, dout, B, N, M, Pp, HW,
-                                                                 sp_b, sp_n, n_valid, m_valid, dRb, s);
-            default:
-                return DMM_ERR_BAD_ARG;
-        }
-    }
-    // default: planes of the union streamed once -- while the four per-wave pair tables fit the default dynamic-LDS limit
-    // (4 * N * MT floats: everything up to 112 proposals x 32 rows or 224 x 16); wider tables keep the row kernel
-    const int mt = M <= 8 ? 8 : (M <= 16 ? 16 : 32);
-    // The union kernel's four per-wave pair tables share ONE dynamic block with its slot slabs (mix_bwd_dynamic_lds: the
-    // larger of the two) beside ~3.1 KB of static tables: 4 * N * mt floats <= 56 KB keeps the workgroup under the 64 KB a
-    // launch gets without an attribute (wider tables: the row kernel).  Edge cases 112 x 32 and 224 x 16 are in the tests.
-    if (dmm::opt(DMM_OPT_MIX_SHARED) != 0 && sizeof(float) * 4 * (size_t)N * mt <= 56 * 1024) {
-        switch (dtype) {
-            case DMM_F32:
-                return dmm::mask_mix_bwd_shared_typed<float>(Rb, (const float *)masks_p, dout, B, N, M, Pp, HW, sp_b, sp_n,
-                                                             n_valid, m_valid, dRb, s);
-            case DMM_F16:
-                return dmm::mask_mix_bwd_shared_typed<dmm::f16_t>(Rb, (const dmm::f16_t *)masks_p, dout, B, N, M, Pp, HW,
-                                                                  sp_b, sp_n, n_valid, m_valid, dRb, s);
-            case DMM_BF16:
-                return dmm::mask_mix_bwd_shared_typed<dmm::bf16_t>(Rb, (const dmm::bf16_t *)masks_p, dout, B, N, M, Pp, HW,
-                                                                   sp_b, sp_n, n_valid, m_valid, dRb, s);
-            default:
-                return DMM_ERR_BAD_ARG;
-        }
-    }
-    switch (dtype) {
-        case DMM_F32:
-            return dmm::mask_mix_bwd_typed<float>(Rb, (const float *)masks_p, dout, B, N, M, Pp, HW, sp_b, sp_n, n_valid,
-                                                  m_valid, dRb, s);
-        case DMM_F16:
-            return dmm::mask_mix_bwd_typed<dmm::f16_t>(Rb, (const dmm::f16_t *)masks_p, dout, B, N, M, Pp, HW, sp_b, sp_n,
-                                                       n_valid, m_valid, dRb, s);
-        case DMM_BF16:
-            return dmm::mask_mix_bwd_typed<dmm::bf16_t>(Rb, (const dmm::bf16_t *)masks_p, dout, B, N, M, Pp, HW, sp_b,
-                                                        sp_n, n_valid, m_valid, dRb, s);
-        default:
-            return DMM_ERR_BAD_ARG;
-    }
+    return dmm::mask_mix_backward({{Rb, masks_p, dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, (hipStream_t)stream},
+                                   dout, dRb, /*drb_zeroed=*/false, nullptr});
+}
+
+extern "C" size_t dmm_mask_mix_bwd_det_workspace_bytes(int B, int N, int M, int Pp, int HW) {
+    if (B <= 0 || N < 0 || M <= 0 || HW < 0 || Pp < N) return 0;
+    return sizeof(float) * (size_t)dmm::mix_bwd_slab_planes(dmm::mix_bwd_kind(N, M), B, M, HW) * (size_t)B * M * Pp;
+}
+
+extern "C" int dmm_mask_mix_bwd_det(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M,
+                                    int Pp, int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid,
+                                    float *dRb, void *workspace, size_t workspace_bytes, dmm_stream_t stream) {
+    return dmm::mask_mix_backward({{Rb, masks_p, dtype, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, (hipStream_t)stream},
+                                   dout, dRb, /*drb_zeroed=*/false, (float *)workspace},
+                                  /*det=*/true, workspace_bytes);
 }
 
 // ---- per-frame pointer tables for the proposal planes (the per-video tensors of DMM_Model: no batch copy) ----
@@ -1022,115 +1039,19 @@ extern "C" int dmm_mask_mix_frames(const float *Rb, const void *const *masks_p_f
                         m_valid, out, so_b, so_m, stream);
 }
 
+extern "C" int dmm_mask_mix_shared_frames(const float *Rb, const void *const *masks_p_frames, int dtype, int B, int N,
+                                          int M, int Pp, int HW, int64_t sp_n, const int32_t *n_valid,
+                                          const int32_t *m_valid, float *out, int64_t so_b, int64_t so_m,
+                                          dmm_stream_t stream) {
+    return dmm_mask_mix_shared_to(Rb, (const void *)masks_p_frames, dtype, B, N, M, Pp, HW, dmm::kFrameTable, sp_n, n_valid,
+                                  m_valid, out, DMM_F32, so_b, so_m, stream);
+}
+
 extern "C" int dmm_mask_mix_bwd_frames(const float *Rb, const void *const *masks_p_frames, int dtype, const float *dout,
                                        int B, int N, int M, int Pp, int HW, int64_t sp_n, const int32_t *n_valid,
                                        const int32_t *m_valid, float *dRb, dmm_stream_t stream) {
     return dmm_mask_mix_bwd(Rb, (const void *)masks_p_frames, dtype, dout, B, N, M, Pp, HW, dmm::kFrameTable, sp_n,
                             n_valid, m_valid, dRb, stream);
-}
-
-// dmm_mask_mix_bwd for a caller that cleared dRb itself (dmm_match_train_backward: by the launch in front)
-namespace dmm {
-int mask_mix_bwd_prezeroed(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M, int Pp,
-                           int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid, float *dRb,
-                           dmm_stream_t stream) {
-    g_drb_prezeroed = true;
-    const int rc = dmm_mask_mix_bwd(Rb, masks_p, dtype, dout, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, dRb, stream);
-    g_drb_prezeroed = false;
-    return rc;
-}
-}  // namespace dmm
-
-// ---- deterministic dRb: the fast kernels' decomposition, each workgroup's partials stored to a slab plane of its own, then one
-// fold in plane order (no arrival-order sums).  Tables outside the fast envelope take the wide kernel (deterministic as it is).
-namespace dmm {
-
-__global__ __launch_bounds__(256) void mix_slab_fold_kernel(const float *__restrict__ slab, int planes, int64_t n,
-                                                            float *__restrict__ dRb) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    float a = 0.0f;
-    for (int p = 0; p < planes; ++p) a += slab[(int64_t)p * n + i];
-    dRb[i] = a;
-}
-
-// 0 = the wide kernel (no slab), 1 = the union kernel, 2 = the row kernel -- what dmm_mask_mix_bwd dispatches to
-static int mix_bwd_det_kind(int N, int M) {
-    if (M > DMM_MAX_TEMPLATES || N > DMM_MAX_PROPOSALS || opt(DMM_OPT_FORCE_WIDE) == 1) return 0;
-    const int mt = M <= 8 ? 8 : (M <= 16 ? 16 : 32);
-    return opt(DMM_OPT_MIX_SHARED) != 0 && sizeof(float) * 4 * (size_t)N * mt <= 56 * 1024 ? 1 : 2;
-}
-
-static int mix_bwd_det_planes(int kind, int B, int M, int HW, int &steps_per_wg) {
-    steps_per_wg = 0;
-    if (kind == 0) return 0;
-    return kind == 1 ? mix_bwd_shared_splits(B, HW, steps_per_wg) : mix_bwd_row_splits(B, M, HW, steps_per_wg);
-}
-
-template <typename T>
-static int mask_mix_bwd_det_typed(int kind, const float *Rb, const T *masks_p, const float *dout, int B, int N, int M, int Pp,
-                                  int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid,
-                                  float *dRb, float *slab, hipStream_t stream) {
-    int steps_per_wg;
-    const int planes = mix_bwd_det_planes(kind, B, M, HW, steps_per_wg);
-    const int64_t n = (int64_t)B * M * Pp;
-    DMM_HIP_TRY(zero_async(slab, sizeof(float) * (size_t)planes * n, stream));
-    if (kind == 1) {
-#define DMM_MIXB_LAUNCH(MT_)                                                                                        \
-    hipLaunchKernelGGL((mask_mix_bwd_shared_kernel<T, MT_, true>), dim3(planes, B), dim3(kMixThreads),              \
-                       mix_bwd_dynamic_lds(N, MT_), stream, Rb, masks_p, dout, N, M, Pp, HW,                         \
-                       sp_b, sp_n, n_valid, m_valid, slab, steps_per_wg, opt(DMM_OPT_MIX_SHARED_LOCKSTEP),              \
-                       (opt(DMM_OPT_MIX_XCD) >> 2) & 1)
-        if (M <= 8) DMM_MIXB_LAUNCH(8);
-        else if (M <= 16) DMM_MIXB_LAUNCH(16);
-        else DMM_MIXB_LAUNCH(32);
-#undef DMM_MIXB_LAUNCH
-    } else {
-        hipLaunchKernelGGL((mask_mix_bwd_kernel<T, true>), dim3(planes, M, B), dim3(kMixThreads), 0, stream, Rb, masks_p, dout,
-                           N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, slab, steps_per_wg);
-    }
-    hipLaunchKernelGGL(mix_slab_fold_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const float *)slab, planes,
-                       n, dRb);
-    return check_launch();
-}
-
-}  // namespace dmm
-
-extern "C" size_t dmm_mask_mix_bwd_det_workspace_bytes(int B, int N, int M, int Pp, int HW) {
-    if (B <= 0 || N < 0 || M <= 0 || HW < 0 || Pp < N) return 0;
-    int steps_per_wg;
-    const int planes = dmm::mix_bwd_det_planes(dmm::mix_bwd_det_kind(N, M), B, M, HW, steps_per_wg);
-    return sizeof(float) * (size_t)planes * (size_t)B * M * Pp;
-}
-
-extern "C" int dmm_mask_mix_bwd_det(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M,
-                                    int Pp, int HW, int64_t sp_b, int64_t sp_n, const int32_t *n_valid, const int32_t *m_valid,
-                                    float *dRb, void *workspace, size_t workspace_bytes, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0 || Pp < N) return DMM_ERR_BAD_ARG;
-    if (B == 0 || M == 0) return DMM_OK;
-    if (!Rb || !masks_p || !dout || !dRb) return DMM_ERR_BAD_ARG;
-    if (M > 65535 || B > 65535) return DMM_ERR_UNSUPPORTED;
-    if (sp_n < HW) return DMM_ERR_BAD_ARG;
-    if (dtype != DMM_F32 && dtype != DMM_F16 && dtype != DMM_BF16) return DMM_ERR_BAD_ARG;
-    const int kind = dmm::mix_bwd_det_kind(N, M);
-    if (kind == 0)
-        return dmm_mask_mix_bwd(Rb, masks_p, dtype, dout, B, N, M, Pp, HW, sp_b, sp_n, n_valid, m_valid, dRb, stream);
-    const size_t need = dmm_mask_mix_bwd_det_workspace_bytes(B, N, M, Pp, HW);
-    if (need && !workspace) return DMM_ERR_BAD_ARG;
-    if (workspace_bytes < need) return DMM_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    float *slab = (float *)workspace;
-    switch (dtype) {
-        case DMM_F32:
-            return dmm::mask_mix_bwd_det_typed<float>(kind, Rb, (const float *)masks_p, dout, B, N, M, Pp, HW, sp_b, sp_n,
-                                                      n_valid, m_valid, dRb, slab, s);
-        case DMM_F16:
-            return dmm::mask_mix_bwd_det_typed<dmm::f16_t>(kind, Rb, (const dmm::f16_t *)masks_p, dout, B, N, M, Pp, HW, sp_b,
-                                                           sp_n, n_valid, m_valid, dRb, slab, s);
-        default:
-            return dmm::mask_mix_bwd_det_typed<dmm::bf16_t>(kind, Rb, (const dmm::bf16_t *)masks_p, dout, B, N, M, Pp, HW,
-                                                            sp_b, sp_n, n_valid, m_valid, dRb, slab, s);
-    }
 }
 
 extern "C" int dmm_mask_mix_bwd_frames_det(const float *Rb, const void *const *masks_p_frames, int dtype, const float *dout,

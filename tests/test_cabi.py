@@ -107,6 +107,75 @@ def test_argument_validation_without_gpu():
     assert L.dmm_relax_solve_f32(one, 1, 3, 257, None, None, 1, 1, 0.1, one, one, None, one, None) == 2
 
 
+MIX_FORWARD = ("dmm_mask_mix_to", "dmm_mask_mix_shared_to", "dmm_mask_mix", "dmm_mask_mix_frames", "dmm_mask_mix_shared_frames")
+MIX_BACKWARD = ("dmm_mask_mix_bwd", "dmm_mask_mix_bwd_frames", "dmm_mask_mix_bwd_det", "dmm_mask_mix_bwd_frames_det")
+
+
+def _mix_status(L, entry, *, B=1, N=4, M=2, Pp=4, HW=16, sp_n=16, so_m=16, dtype=0, out_dtype=0, Rb=True, planes=True,
+                out=True, dout=True, dRb=True, ws=True, ws_bytes=1 << 30):
+    """One mix entry's status for a call that must be answered before the device is touched (every pointer is the
+    address 8).  ``out`` / ``out_dtype`` / ``so_m`` go to the entries that take them, ``ws`` to the deterministic ones."""
+    p = lambda have: ctypes.c_void_p(8) if have else None
+    frames, det = "_frames" in entry, entry.endswith("_det")
+    sp = (sp_n,) if frames else (N * sp_n, sp_n)
+    if entry in MIX_FORWARD:
+        odt = (out_dtype,) if entry.endswith("_to") else ()
+        return getattr(L, entry)(p(Rb), p(planes), dtype, B, N, M, Pp, HW, *sp, None, None, p(out), *odt, M * so_m, so_m, None)
+    tail = (p(ws), ws_bytes) if det else ()
+    return getattr(L, entry)(p(Rb), p(planes), dtype, p(dout), B, N, M, Pp, HW, *sp, None, None, p(dRb), *tail, None)
+
+
+def test_mix_entries_validate_their_arguments_without_gpu():
+    """Every mix entry's answer to arguments it rejects, or has nothing to do for, before any launch.  The expected statuses are
+    those of the entries as they stood when each spelled its own checks out (commit 7c7ab6b), read off that code; the
+    deterministic workspace sizes were recorded from a build of it."""
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    L = _lib.load()
+    OK, BAD, UNSUPPORTED, WORKSPACE = 0, 1, 2, 4
+    null = dict(Rb=False, planes=False, out=False, dout=False, dRb=False, ws=False)
+    for entry in MIX_FORWARD + MIX_BACKWARD:
+        fwd, det = entry in MIX_FORWARD, entry.endswith("_det")
+        st = lambda **kw: _mix_status(L, entry, **kw)
+        for kw in (dict(B=-1), dict(N=-1), dict(M=-1), dict(HW=-1), dict(Pp=3), dict(sp_n=15), dict(Rb=False),
+                   dict(planes=False), dict(dtype=7), dict(dtype=_lib.DTYPE_PACKED1)):
+            assert st(**kw) == BAD, (entry, kw)
+        assert st(B=0, **null) == OK and st(M=0, **null) == OK, entry                   # nothing to do, whatever the pointers
+        assert st(HW=0, **null) == (OK if fwd else BAD), entry                           # (the backward still owes dRb its zeros)
+        assert st(B=0, Pp=3, **null) == BAD and st(M=0, HW=-1, **null) == BAD, entry     # sizes before "nothing to do"
+        assert st(M=65536) == UNSUPPORTED and st(B=65536) == UNSUPPORTED, entry
+        assert st(B=65536, Rb=False) == BAD and st(M=65536, sp_n=15) == UNSUPPORTED, entry    # pointers, grid limits, strides
+        if fwd:
+            assert st(out=False) == BAD and st(so_m=15) == BAD and st(M=65536, so_m=15) == UNSUPPORTED, entry
+        else:
+            assert st(dout=False) == BAD and st(dRb=False) == BAD, entry
+        if entry.endswith("_to"):
+            for kw in (dict(out_dtype=_lib.DTYPE_F16), dict(out_dtype=7), dict(dtype=_lib.DTYPE_F16, out_dtype=_lib.DTYPE_BF16),
+                       dict(dtype=7, out_dtype=7)):
+                assert st(**kw) == BAD, (entry, kw)
+            assert st(M=65536, out_dtype=7) == UNSUPPORTED, entry
+        if det:
+            need = L.dmm_mask_mix_bwd_det_workspace_bytes(1, 4, 2, 4, 16)
+            assert need == 32
+            assert st(ws_bytes=need - 4) == WORKSPACE and st(ws=False) == BAD and st(ws=False, ws_bytes=0) == BAD, entry
+            assert st(dtype=7, ws_bytes=0) == BAD and st(sp_n=15, ws_bytes=0) == BAD, entry   # before the workspace is looked at
+            assert st(M=65536, ws=False) == UNSUPPORTED, entry
+    # deterministic slab: pixel splits of the kernel that fills it x B x M x Pp floats.  112 x 32 and 224 x 16 are the widest
+    # tables of the union kernel (4 * N * mt floats of LDS <= 56 KB), one proposal more takes the row kernel; at HW = 240 both
+    # have one split, at 300 steps of 1024 pixels they differ
+    size = L.dmm_mask_mix_bwd_det_workspace_bytes
+    for (B, N, M), at240, at300 in (((2, 6, 3), 144, 57600), ((1, 112, 32), 14336, 8601600), ((1, 113, 32), 14464, 3471360),
+                                    ((1, 224, 16), 14336, 8601600), ((1, 225, 16), 14400, 5760000)):
+        assert size(B, N, M, N, 240) == at240 and size(B, N, M, N, 300 * 4096) == at300, (B, N, M)
+    assert size(1, 112, 32, 115, 240) == 14720 and size(1, 225, 16, 228, 240) == 14592
+    assert size(1, 300, 16, 300, 300 * 4096) == 0 and size(1, 20, 40, 20, 300 * 4096) == 0     # the wide kernel: no slab
+    with _lib.options(MIX_SHARED=0):
+        assert size(1, 112, 32, 112, 300 * 4096) == 3440640                                   # the row kernel
+    with _lib.options(FORCE_WIDE=1):
+        assert size(1, 112, 32, 112, 300 * 4096) == 0
+    assert size(0, 4, 2, 4, 16) == 0 and size(1, 4, 0, 4, 16) == 0 and size(1, 4, 2, 3, 16) == 0 and size(1, 4, 2, 4, -1) == 0
+
+
 def test_training_entries_validate_their_arguments_without_gpu():
     """(5d) / (5e) / (1e): workspace sizes are positive and grow with the batch, null pointers / negative sizes answer
     DMM_ERR_BAD_ARG, tables outside the fast kernels' envelope answer DMM_ERR_UNSUPPORTED (the caller then takes the granular
