@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../../include/dmm_match.h"
 
 namespace dmm {
@@ -300,6 +302,25 @@ inline int check_launch() {
             return DMM_ERR_LAUNCH;                         \
         }                                                  \
     } while (0)
+
+// f(planes) with the planes as const float / f16_t / bf16_t * -- the one place a dtype becomes a type.  `otherwise`: the
+// caller's answer to 1-bit or unknown planes.
+template <typename F>
+static int with_plane_type(int dtype, const void *planes, int otherwise, F &&f) {
+    switch (dtype) {
+        case DMM_F32: return f((const float *)planes);
+        case DMM_F16: return f((const f16_t *)planes);
+        case DMM_BF16: return f((const bf16_t *)planes);
+        default: return otherwise;
+    }
+}
+// ... and for the counts, which read DMM_PACKED1 words as well
+template <typename F>
+static int with_count_plane_type(int dtype, const void *planes, F &&f) {
+    return dtype == DMM_PACKED1 ? f((const packed_t *)planes) : with_plane_type(dtype, planes, DMM_ERR_BAD_ARG, f);
+}
+template <typename P>
+using plane_type_of = typename std::remove_const<typename std::remove_pointer<P>::type>::type;   // P: what f was handed
 
 // ---- XCD-aware workgroup -> (frame, range) mapping -------------------------------------------
 // Workgroups are dispatched round-robin over the 8 XCDs by linear id.  With the plain (range = blockIdx.x, frame =

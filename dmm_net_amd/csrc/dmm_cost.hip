@@ -21,6 +21,12 @@
 // VALU work is ~10 % of the HBM time of a chunk; the kernel is a pure stream.
 // DMM_PACKED1 input (1 bit per pixel, see dmm_pack.hip) skips the threshold/ballot step: lane p loads the 16 words
 // of its plane's chunk straight into the tile.
+//
+// Host side: every caller fills one CountArgs (dmm_launchers.h) -- the four dmm_iou_counts* entries at the end of this file,
+// the one-call entries through their Front, which derives from it.  iou_counts_launch checks the bundle, slices a batch of
+// more than 65535 frames (count_slice), turns the dtype into a type once (with_count_plane_type) and tiles the table
+// (iou_counts_typed -> launch_tile / launch_tl); front_small_launch is the fused small-batch form.  The typed functions take
+// the bundle and plain tile coordinates; only the kernels and their launches spell the arguments out.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -291,7 +297,7 @@ __global__ __launch_bounds__(kCostThreads) void iou_counts_kernel(
 // features) and the counts ~450 workgroups for ~13 us (16 MB of planes); as two launches they queue behind each other.
 // Here the first cos_parts workgroups of every frame run cosine_lanes_body, the rest iou_counts_body in its small-batch
 // shape (one 16-byte lane load per plane and chunk, sub-tiles of proposals) -- neither depends on the other, both feed the
-// solver.  The count tables must be zero on entry (dmm_front_small clears them with one launch in front).
+// solver.  The count tables must be zero on entry (launch_front_small clears them with one launch in front).
 // grid = (cos_parts + splits * sub_count, B), block = 256, dynamic LDS = lanes_geom<LPC>().lds.
 // ---------------------------------------------------------------------------------------------
 template <int LPC, typename T, int MT>
@@ -318,11 +324,30 @@ __global__ __launch_bounds__(kCostThreads) void front_small_kernel(
                                         (int)gridDim.x - cos_parts, gridDim.y);
 }
 
+// Sub-tiles of proposals: a tile of `ntile` proposals cut into sub_count sub-tiles of n_sub, one workgroup each.
+struct SubTiles { int sub_count, n_sub; };
+// as even as `sub_count` pieces get (pieces that would be empty are dropped)
+static SubTiles even_sub_tiles(int ntile, int sub_count) {
+    const int n_sub = (ntile + sub_count - 1) / sub_count;
+    return {(ntile + n_sub - 1) / n_sub, n_sub};
+}
+// THE rule of every register-tile launch: one that has `wgs` workgroups, fewer than COST_SMALL_WGS, is split further into
+// sub-tiles of >= 8 proposals until about that many exist (a tile of <= 8 stays whole, as does every larger launch: one
+// "sub-tile" of the tile's `capacity`).  Every sub-tile re-reads the frame's template planes, so the target must not be
+// higher than it takes to fill the chip: measured per call (cosine + counts + solver + mix) at B = 1 / 4 / 8 / 64 frames
+// of 50 x 10, 255 x 255: 1024 -> 0.109 / 0.124 / 0.137 / 0.473 ms, 512 -> 0.109 / 0.117 / 0.134 / 0.345,
+// 256 -> 0.106 / 0.121 / 0.135 / 0.346, 2048 -> 0.109 / 0.133 / 0.142 / 0.474
+static SubTiles sub_tiles(int ntile, int capacity, int64_t wgs) {
+    const int small_wgs = opt(DMM_OPT_COST_SMALL_WGS);
+    if (wgs >= small_wgs || ntile <= 8) return {1, capacity};
+    const int64_t want = (small_wgs + wgs - 1) / wgs, max_sub = (ntile + 7) / 8;
+    return even_sub_tiles(ntile, (int)(want < max_sub ? want : max_sub));
+}
+
 template <typename T, int MT>
-static int launch_front_small(const float *feat_t, const float *feat_p, float *cos_out, const T *masks_p, const T *masks_t,
-                              const T *masks_t2, int B, int N, int M, int HW, int64_t sp_b, int64_t sp_n, int64_t st_b,
-                              int64_t st_m, int64_t st2_b, int64_t st2_m, int32_t *inter, int32_t *area_p, int32_t *area_t,
-                              int32_t *inter2, int32_t *area_t2, bool tables_zero, hipStream_t stream) {
+static int launch_front_small(const Front &f, hipStream_t stream) {
+    const T *masks_p = (const T *)f.masks_p, *masks_t = (const T *)f.masks_t, *masks_t2 = (const T *)f.masks_t2;
+    const int B = f.B, N = f.N, M = f.M;
     constexpr int LPC = 32;                                          // D = 512, the model's ROI feature width
     // similarity workgroups: 2 of the 4 waves take steps (every workgroup of the launch carries their LDS; with 4 wave
     // buffers only 2 workgroups fit a CU, with 2 three do)
@@ -334,29 +359,18 @@ static int launch_front_small(const float *feat_t, const float *feat_p, float *c
     g.lds = sizeof(float) * ((size_t)M * G::PITCH + 32 + (size_t)g.nw * G::WAVE_FLOATS);
     // the small-batch shape of launch_tile below
     constexpr int CHS = 64 * MaskIO<T>::kVec;
-    const int small_wgs = opt(DMM_OPT_COST_SMALL_WGS);
-    const int nch = (HW + CHS - 1) / CHS;
+    const int nch = (f.HW + CHS - 1) / CHS;
     const int splits_s = (nch + kCostThreads / kWave - 1) / (kCostThreads / kWave);
-    int sub_count = 1, n_sub = kWave;
-    if ((int64_t)B * splits_s < small_wgs && N > 8) {
-        sub_count = (int)((small_wgs + (int64_t)B * splits_s - 1) / ((int64_t)B * splits_s));
-        const int max_sub = (N + 7) / 8;
-        if (sub_count > max_sub) sub_count = max_sub;
-        n_sub = (N + sub_count - 1) / sub_count;
-        sub_count = (N + n_sub - 1) / n_sub;
-    }
+    const int64_t wgs = (int64_t)B * splits_s;
+    SubTiles st = sub_tiles(N, kWave, wgs);
     // every workgroup of the launch carries the similarity's LDS, so only a few fit a CU; the launch must stay ONE
     // resident wave of workgroups (a second wave would queue the counts behind the similarity's 10 us):
     // fewer sub-tiles of proposals if that does it, the separate launches otherwise
     {
         const int64_t per_cu = (int64_t)(160 * 1024) / (int64_t)(g.lds + 8 * 1024);
         const int64_t slots = 256 * (per_cu < 1 ? 1 : per_cu) - (int64_t)B * g.parts;
-        while (sub_count > 1 && (int64_t)B * splits_s * sub_count > slots) {
-            --sub_count;
-            n_sub = (N + sub_count - 1) / sub_count;
-            sub_count = (N + n_sub - 1) / n_sub;
-        }
-        if ((int64_t)B * splits_s * sub_count > slots) return DMM_ERR_UNSUPPORTED;
+        while (st.sub_count > 1 && wgs * st.sub_count > slots) st = even_sub_tiles(N, st.sub_count - 1);
+        if (wgs * st.sub_count > slots) return DMM_ERR_UNSUPPORTED;
     }
     if (g.lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute((const void *)front_small_kernel<LPC, T, MT>,
@@ -364,61 +378,45 @@ static int launch_front_small(const float *feat_t, const float *feat_p, float *c
         if (e != hipSuccess) { set_last_hip_error((int)e); return DMM_ERR_LAUNCH; }
     }
     // (training: the targets' tables inter2 | area_t2 follow the three tables in the caller's block -- one clearing launch)
-    if (!tables_zero)
-        DMM_HIP_TRY(zero_async(inter, sizeof(int32_t) * (((size_t)B * M * N + (size_t)B * M) * (masks_t2 ? 2 : 1) + (size_t)B * N),
+    if (!f.tables_zero)
+        DMM_HIP_TRY(zero_async(f.inter, sizeof(int32_t) * (((size_t)B * M * N + (size_t)B * M) * (masks_t2 ? 2 : 1) + (size_t)B * N),
                                stream));
-    hipLaunchKernelGGL((front_small_kernel<LPC, T, MT>), dim3(g.parts + splits_s * sub_count, B), dim3(kCostThreads), g.lds,
-                       stream, feat_t, feat_p, cos_out, g.parts, g.nw, masks_p, masks_t, masks_t2, N, M, HW, sp_b, sp_n,
-                       st_b, st_m, st2_b, st2_m, (const int32_t *)nullptr, (const int32_t *)nullptr, inter, area_p,
-                       area_t, inter2, area_t2, 0, 0, kCostThreads / kWave, 1, 1, 0, sub_count, n_sub);
+    hipLaunchKernelGGL((front_small_kernel<LPC, T, MT>), dim3(g.parts + splits_s * st.sub_count, B), dim3(kCostThreads), g.lds,
+                       stream, f.feat_t, f.feat_p, f.cos, g.parts, g.nw, masks_p, masks_t, masks_t2, N, M, f.HW, f.sp_b,
+                       f.sp_n, f.st_b, f.st_m, f.st2_b, f.st2_m, (const int32_t *)nullptr, (const int32_t *)nullptr, f.inter,
+                       f.area_p, f.area_t, f.inter2, f.area_t2, 0, 0, kCostThreads / kWave, 1, 1, 0, st.sub_count, st.n_sub);
     return check_launch();
 }
 
 // DMM_ERR_UNSUPPORTED (nothing launched) outside its envelope: B <= DMM_OPT_COST_TINY_FRAMES dense frames, N <= 64,
 // M <= 16, D = 512, float / half / bfloat16 planes, the three tables contiguous (dmm_match_forward's workspace).
-// tables_zero: the caller vouches that the tables are zero already (dmm_match_forward_ws) -- no clearing launch.
-// masks_t2 (training, dmm_match_train_forward): a second template set -- the targets of compute_matching_loss -- rides in
+// f.tables_zero: the caller vouches that the tables are zero already (dmm_match_forward_ws) -- no clearing launch.
+// f.masks_t2 (training, dmm_match_train_forward): a second template set -- the targets of compute_matching_loss -- rides in
 // the same tile (rows M..2M-1), M <= 8; its tables inter2 | area_t2 must follow area_t in the same block.
-int front_small_launch(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, const float *feat_t,
-                       const float *feat_p, int B, int N, int M, int HW, int D, int64_t sp_b, int64_t sp_n, int64_t st_b,
-                       int64_t st_m, int64_t st2_b, int64_t st2_m, float *cos_out, int32_t *inter, int32_t *area_p,
-                       int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zero, hipStream_t stream) {
-    if (opt(DMM_OPT_SMALL_FUSED) != 1 || B > opt(DMM_OPT_COST_TINY_FRAMES) || opt(DMM_OPT_COST_KERNEL) == 1)
+int front_small_launch(const Front &f, hipStream_t stream) {
+    if (opt(DMM_OPT_SMALL_FUSED) != 1 || f.B > opt(DMM_OPT_COST_TINY_FRAMES) || opt(DMM_OPT_COST_KERNEL) == 1)
         return DMM_ERR_UNSUPPORTED;
-    const int rows = masks_t2 ? 2 * M : M;
-    if (D != 512 || N < 2 || N > 64 || M < 1 || rows > 16 || HW <= 0 || sp_n < HW || st_m < HW) return DMM_ERR_UNSUPPORTED;
-    if (area_p != inter + (size_t)B * M * N || area_t != area_p + (size_t)B * N) return DMM_ERR_UNSUPPORTED;
-    if (masks_t2 && (st2_m < HW || inter2 != area_t + (size_t)B * M || area_t2 != inter2 + (size_t)B * M * N))
+    const int rows = f.masks_t2 ? 2 * f.M : f.M;
+    if (f.D != 512 || f.N < 2 || f.N > 64 || f.M < 1 || rows > 16 || f.HW <= 0 || f.sp_n < f.HW || f.st_m < f.HW)
         return DMM_ERR_UNSUPPORTED;
-#define DMM_FRONT_CASE(T_)                                                                                              \
-    return rows <= 8 ? launch_front_small<T_, 8>(feat_t, feat_p, cos_out, (const T_ *)masks_p, (const T_ *)masks_t,       \
-                                                 (const T_ *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, \
-                                                 inter, area_p, area_t, inter2, area_t2, tables_zero, stream)            \
-                     : launch_front_small<T_, 16>(feat_t, feat_p, cos_out, (const T_ *)masks_p, (const T_ *)masks_t,      \
-                                                  (const T_ *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, \
-                                                  inter, area_p, area_t, inter2, area_t2, tables_zero, stream)
-    switch (dtype) {
-        case DMM_F32: DMM_FRONT_CASE(float);
-        case DMM_F16: DMM_FRONT_CASE(f16_t);
-        case DMM_BF16: DMM_FRONT_CASE(bf16_t);
-        default: return DMM_ERR_UNSUPPORTED;
-    }
-#undef DMM_FRONT_CASE
+    const size_t BMN = (size_t)f.B * f.M * f.N, BN = (size_t)f.B * f.N, BM = (size_t)f.B * f.M;
+    if (f.area_p != f.inter + BMN || f.area_t != f.area_p + BN) return DMM_ERR_UNSUPPORTED;
+    if (f.masks_t2 && (f.st2_m < f.HW || f.inter2 != f.area_t + BM || f.area_t2 != f.inter2 + BMN)) return DMM_ERR_UNSUPPORTED;
+    return with_plane_type(f.dtype, f.masks_p, DMM_ERR_UNSUPPORTED, [&](auto *planes) {       // 1-bit planes: the chain goes on
+        using T = plane_type_of<decltype(planes)>;
+        return rows <= 8 ? launch_front_small<T, 8>(f, stream) : launch_front_small<T, 16>(f, stream);
+    });
 }
 
 template <typename T, int MT, int NG>
-static int launch_tile(const T *masks_p, const T *masks_t, const T *masks_t2, int B, int N, int M, int HW, int64_t sp_b,
-                       int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m, const int32_t *n_valid,
-                       const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t, int32_t *inter2,
-                       int32_t *area_t2, int n0, int m0, int wap, int wat, hipStream_t stream) {
+static int launch_tile(const CountArgs &a, int n0, int m0, int wap, int wat, hipStream_t stream) {
+    const T *masks_p = (const T *)a.masks_p, *masks_t = (const T *)a.masks_t, *masks_t2 = (const T *)a.masks_t2;
+    const int B = a.B, HW = a.HW;
     const int target_wgs = opt(DMM_OPT_COST_WGS);
-    // workgroups below which a launch is split further (one chunk per workgroup, sub-tiles of proposals).  Every sub-tile
-    // re-reads the frame's template planes, so the target must not be higher than it takes to fill the chip: measured per
-    // call (cosine + counts + solver + mix) at B = 1 / 4 / 8 / 64 frames of 50 x 10, 255 x 255: 1024 -> 0.109 / 0.124 / 0.137
-    // / 0.473 ms, 512 -> 0.109 / 0.117 / 0.134 / 0.345, 256 -> 0.106 / 0.121 / 0.135 / 0.346, 2048 -> 0.109 / 0.133 / 0.142 / 0.474
-    const int small_wgs = opt(DMM_OPT_COST_SMALL_WGS);
+    const int small_wgs = opt(DMM_OPT_COST_SMALL_WGS);           // workgroups below which a launch is split further: sub_tiles
     const int tiny_frames = opt(DMM_OPT_COST_TINY_FRAMES);       // default 8: B = 8 0.162 ms per sequence with it, 0.191 without
     const int xcd_remap = opt(DMM_OPT_COST_XCD);
+    const int ntile = (a.N - n0) < NG * kWave ? (a.N - n0) : NG * kWave;
     // A handful of frames (the product's B = 1 / B = 4 calls) is a LATENCY problem: with 1024-pixel chunks one frame
     // has 64 of them, one per workgroup, so three waves of every workgroup idled and the working one went through 9
     // dependent load batches (10 template planes + 8 proposals, 2 planes in flight): 19 us at B = 1.  The same kernel
@@ -429,19 +427,11 @@ static int launch_tile(const T *masks_p, const T *masks_t, const T *masks_t2, in
             constexpr int CHS = 64 * MaskIO<T>::kVec, LBS = 16384;
             const int nch = (HW + CHS - 1) / CHS;
             const int splits_s = (nch + kCostThreads / kWave - 1) / (kCostThreads / kWave);
-            const int ntile_s = (N - n0) < kWave ? (N - n0) : kWave;
-            int sub_count = 1, n_sub = kWave;
-            if ((int64_t)B * splits_s < small_wgs && ntile_s > 8) {
-                sub_count = (int)((small_wgs + (int64_t)B * splits_s - 1) / ((int64_t)B * splits_s));
-                const int max_sub = (ntile_s + 7) / 8;
-                if (sub_count > max_sub) sub_count = max_sub;
-                n_sub = (ntile_s + sub_count - 1) / sub_count;
-                sub_count = (ntile_s + n_sub - 1) / n_sub;
-            }
-            hipLaunchKernelGGL((iou_counts_kernel<T, MT, NG, CHS, LBS>), dim3(splits_s * sub_count, B), dim3(kCostThreads), 0,
-                               stream, masks_p, masks_t, masks_t2, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, n_valid,
-                               m_valid, inter, area_p, area_t, inter2, area_t2, n0, m0, kCostThreads / kWave, wap, wat,
-                               xcd_remap, sub_count, n_sub);
+            const SubTiles st = sub_tiles(ntile, kWave, (int64_t)B * splits_s);
+            hipLaunchKernelGGL((iou_counts_kernel<T, MT, NG, CHS, LBS>), dim3(splits_s * st.sub_count, B), dim3(kCostThreads),
+                               0, stream, masks_p, masks_t, masks_t2, a.N, a.M, HW, a.sp_b, a.sp_n, a.st_b, a.st_m, a.st2_b,
+                               a.st2_m, a.n_valid, a.m_valid, a.inter, a.area_p, a.area_t, a.inter2, a.area_t2, n0, m0,
+                               kCostThreads / kWave, wap, wat, xcd_remap, st.sub_count, st.n_sub);
             return check_launch();
         }
     }
@@ -458,19 +448,11 @@ static int launch_tile(const T *masks_p, const T *masks_t, const T *masks_t2, in
     splits = (nchunks + chunks_per_wg - 1) / chunks_per_wg;
     // ... and sub-tiles of >= 8 proposals until ~small_wgs workgroups exist (B = 1, N = 50: 16 workgroups took 33 us,
     // 448 take 17; B = 4: 53 us with 64)
-    const int ntile = (N - n0) < NG * kWave ? (N - n0) : NG * kWave;
-    int sub_count = 1, n_sub = NG * kWave;
-    if ((int64_t)B * splits < small_wgs && ntile > 8) {
-        sub_count = (int)((small_wgs + (int64_t)B * splits - 1) / ((int64_t)B * splits));
-        const int max_sub = (ntile + 7) / 8;
-        if (sub_count > max_sub) sub_count = max_sub;
-        n_sub = (ntile + sub_count - 1) / sub_count;
-        sub_count = (ntile + n_sub - 1) / n_sub;
-    }
-    dim3 grid(splits * sub_count, B);
-    hipLaunchKernelGGL((iou_counts_kernel<T, MT, NG>), grid, dim3(kCostThreads), 0, stream, masks_p, masks_t, masks_t2, N,
-                       M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2,
-                       area_t2, n0, m0, chunks_per_wg, wap, wat, xcd_remap, sub_count, n_sub);
+    const SubTiles st = sub_tiles(ntile, NG * kWave, (int64_t)B * splits);
+    hipLaunchKernelGGL((iou_counts_kernel<T, MT, NG>), dim3(splits * st.sub_count, B), dim3(kCostThreads), 0, stream, masks_p,
+                       masks_t, masks_t2, a.N, a.M, HW, a.sp_b, a.sp_n, a.st_b, a.st_m, a.st2_b, a.st2_m, a.n_valid,
+                       a.m_valid, a.inter, a.area_p, a.area_t, a.inter2, a.area_t2, n0, m0, chunks_per_wg, wap, wat,
+                       xcd_remap, st.sub_count, st.n_sub);
     return check_launch();
 }
 
@@ -602,16 +584,14 @@ __global__ __launch_bounds__(kCostThreads, DMM_TL_MIN_WAVES) void iou_counts_tl_
 }
 
 template <typename T>
-static int launch_tl(const T *masks_p, const T *masks_t, const T *masks_t2, int B, int N, int M, int HW, int64_t sp_b,
-                     int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m, const int32_t *n_valid,
-                     const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t, int32_t *inter2,
-                     int32_t *area_t2, int n0, int m0, int nt, int mt, int wap, int wat, hipStream_t stream) {
-    const int nchunks = (HW + kChunk - 1) / kChunk;
+static int launch_tl(const CountArgs &a, int n0, int m0, int nt, int mt, int wap, int wat, hipStream_t stream) {
+    const T *masks_p = (const T *)a.masks_p, *masks_t = (const T *)a.masks_t, *masks_t2 = (const T *)a.masks_t2;
+    const int nchunks = (a.HW + kChunk - 1) / kChunk;
     // FEW, long-lived workgroups: every one zeroes and flushes its own [proposal][row] table (4200 entries at config 5),
     // and this kernel's rate does not follow its occupancy (2 waves per SIMD stream as fast as 4).  Measured at config 5,
     // ms per launch at 512 / 2048 / 8192 workgroups: 512 frames 2.42 / 2.48 / 2.53, 128 frames 0.68 / 0.71 / 0.71.
     const int target_wgs = opt(DMM_OPT_COST_TL_WGS);
-    int splits = (target_wgs + B - 1) / B;
+    int splits = (target_wgs + a.B - 1) / a.B;
     const int max_splits = (nchunks + kCostThreads / kWave - 1) / (kCostThreads / kWave);
     if (splits > max_splits) splits = max_splits;
     if (splits < 1) splits = 1;
@@ -620,34 +600,34 @@ static int launch_tl(const T *masks_p, const T *masks_t, const T *masks_t2, int 
     const int xcd_remap = opt(DMM_OPT_COST_XCD);
     const int RS = (masks_t2 ? 2 * mt : mt) + 1;
     const size_t lds = sizeof(unsigned) * ((size_t)nt * RS + kWave);
-    hipLaunchKernelGGL((iou_counts_tl_kernel<T>), dim3(splits, B), dim3(kCostThreads), lds, stream, masks_p, masks_t,
-                       masks_t2, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t,
-                       inter2, area_t2, n0, m0, nt, mt, chunks_per_wg, wap, wat, RS, xcd_remap);
+    hipLaunchKernelGGL((iou_counts_tl_kernel<T>), dim3(splits, a.B), dim3(kCostThreads), lds, stream, masks_p, masks_t,
+                       masks_t2, a.N, a.M, a.HW, a.sp_b, a.sp_n, a.st_b, a.st_m, a.st2_b, a.st2_m, a.n_valid, a.m_valid,
+                       a.inter, a.area_p, a.area_t, a.inter2, a.area_t2, n0, m0, nt, mt, chunks_per_wg, wap, wat, RS,
+                       xcd_remap);
     return check_launch();
 }
 
-// tables_zeroed: the caller has cleared every table on this stream already (iou_counts_prezeroed / _dual_prezeroed)
+// the counts of at most 65535 frames (grid.y) on planes of type T
 template <typename T>
-static int iou_counts_typed(const T *masks_p, const T *masks_t, const T *masks_t2, int B, int N, int M, int HW,
-                            int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
-                            const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
-                            int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zeroed, hipStream_t stream) {
+static int iou_counts_typed(const CountArgs &a, bool tables_zeroed, hipStream_t stream) {
+    const int N = a.N, M = a.M;
+    const size_t BMN = (size_t)a.B * M * N, BN = (size_t)a.B * N, BM = (size_t)a.B * M;
     if (tables_zeroed) {
         // dmm_match_forward / dmm_match_train_forward: the feature-similarity launch in front of this one already cleared
         // the tables (all five of them in the dual form)
-    } else if (area_p == inter + (size_t)B * M * N && area_t == area_p + (size_t)B * N) {
-        // the three tables are one contiguous block (dmm_match_forward's workspace): one memset node
-        DMM_HIP_TRY(zero_async(inter, sizeof(int32_t) * ((size_t)B * M * N + (size_t)B * N + (size_t)B * M), stream));
+    } else if (a.area_p == a.inter + BMN && a.area_t == a.area_p + BN) {
+        // the three tables are one contiguous block (dmm_match_forward's workspace): one clearing launch
+        DMM_HIP_TRY(zero_async(a.inter, sizeof(int32_t) * (BMN + BN + BM), stream));
     } else {
-        DMM_HIP_TRY(zero_async(inter, sizeof(int32_t) * (size_t)B * M * N, stream));
-        DMM_HIP_TRY(zero_async(area_p, sizeof(int32_t) * (size_t)B * N, stream));
-        DMM_HIP_TRY(zero_async(area_t, sizeof(int32_t) * (size_t)B * M, stream));
+        DMM_HIP_TRY(zero_async(a.inter, sizeof(int32_t) * BMN, stream));
+        DMM_HIP_TRY(zero_async(a.area_p, sizeof(int32_t) * BN, stream));
+        DMM_HIP_TRY(zero_async(a.area_t, sizeof(int32_t) * BM, stream));
     }
-    if (masks_t2 && !tables_zeroed) {
-        DMM_HIP_TRY(zero_async(inter2, sizeof(int32_t) * (size_t)B * M * N, stream));
-        DMM_HIP_TRY(zero_async(area_t2, sizeof(int32_t) * (size_t)B * M, stream));
+    if (a.masks_t2 && !tables_zeroed) {
+        DMM_HIP_TRY(zero_async(a.inter2, sizeof(int32_t) * BMN, stream));
+        DMM_HIP_TRY(zero_async(a.area_t2, sizeof(int32_t) * BM, stream));
     }
-    if (HW == 0) return DMM_OK;
+    if (a.HW == 0) return DMM_OK;
     // Tile the (N, M) table over the compiled envelopes: <= 32 template rows per launch (<= 16 when a second
     // template set rides along: both sets share the tile) x <= 256 proposals.  Register budget decides the
     // proposal tile: accumulators are MT x NG per lane, and at MT > 16 a 4-group tile drops to 1 wave/SIMD
@@ -655,139 +635,99 @@ static int iou_counts_typed(const T *masks_p, const T *masks_t, const T *masks_t
     // per tile: +9 % bytes at N=200, M=20).
     // kernel choice: DMM_OPT_COST_KERNEL = 0 (register tiles) / 1 (template lanes) / -1 = by shape (the IoU tests pin both)
     const int kernel_mode = opt(DMM_OPT_COST_KERNEL);
+    const int mstep = a.masks_t2 ? 16 : 32;
     if constexpr (!std::is_same<T, packed_t>::value) {
-        const int rows = masks_t2 ? 2 * M : M;
+        const int rows = a.masks_t2 ? 2 * M : M;
         const bool use_tl = kernel_mode == 1 || (kernel_mode < 0 && (rows > 16 || N > 128));
         if (use_tl) {
-            const int mstep_tl = masks_t2 ? 16 : 32;
-            for (int m0 = 0; m0 < M; m0 += mstep_tl) {
-                const int mt = M - m0 < mstep_tl ? M - m0 : mstep_tl;
+            for (int m0 = 0; m0 < M; m0 += mstep) {
+                const int mt = M - m0 < mstep ? M - m0 : mstep;
                 for (int n0 = 0; n0 < N; n0 += 256) {
                     const int nt = N - n0 < 256 ? N - n0 : 256;
-                    const int rc = launch_tl<T>(masks_p, masks_t, masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b,
-                                                st2_m, n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, n0, m0,
-                                                nt, mt, m0 == 0, n0 == 0, stream);
+                    const int rc = launch_tl<T>(a, n0, m0, nt, mt, m0 == 0, n0 == 0, stream);
                     if (rc != DMM_OK) return rc;
                 }
             }
             return DMM_OK;
         }
     }
-    const int mstep = masks_t2 ? 16 : 32;
     for (int m0 = 0; m0 < M; m0 += mstep) {
-        const int mt = (M - m0 < mstep ? M - m0 : mstep) * (masks_t2 ? 2 : 1);
+        const int mt = (M - m0 < mstep ? M - m0 : mstep) * (a.masks_t2 ? 2 : 1);
         const int nstep = mt > 16 ? 128 : 256;
         for (int n0 = 0; n0 < N; n0 += nstep) {
             const int nt = N - n0 < nstep ? N - n0 : nstep;
             const int wap = (m0 == 0), wat = (n0 == 0);
             int rc;
-#define DMM_COST_CASE(MT_, NG_)                                                                                       \
-    rc = launch_tile<T, MT_, NG_>(masks_p, masks_t, masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, n_valid, \
-                                  m_valid, inter, area_p, area_t, inter2, area_t2, n0, m0, wap, wat, stream)
             if (nt <= 64) {
-                if (mt <= 8) DMM_COST_CASE(8, 1);
-                else if (mt <= 16) DMM_COST_CASE(16, 1);
-                else if (mt <= 24) DMM_COST_CASE(24, 1);
-                else DMM_COST_CASE(32, 1);
+                if (mt <= 8) rc = launch_tile<T, 8, 1>(a, n0, m0, wap, wat, stream);
+                else if (mt <= 16) rc = launch_tile<T, 16, 1>(a, n0, m0, wap, wat, stream);
+                else if (mt <= 24) rc = launch_tile<T, 24, 1>(a, n0, m0, wap, wat, stream);
+                else rc = launch_tile<T, 32, 1>(a, n0, m0, wap, wat, stream);
             } else if (nt <= 128) {
-                if (mt <= 8) DMM_COST_CASE(8, 2);
-                else if (mt <= 16) DMM_COST_CASE(16, 2);
-                else if (mt <= 24) DMM_COST_CASE(24, 2);
-                else DMM_COST_CASE(32, 2);
+                if (mt <= 8) rc = launch_tile<T, 8, 2>(a, n0, m0, wap, wat, stream);
+                else if (mt <= 16) rc = launch_tile<T, 16, 2>(a, n0, m0, wap, wat, stream);
+                else if (mt <= 24) rc = launch_tile<T, 24, 2>(a, n0, m0, wap, wat, stream);
+                else rc = launch_tile<T, 32, 2>(a, n0, m0, wap, wat, stream);
             } else {
-                if (mt <= 8) DMM_COST_CASE(8, 4);
-                else DMM_COST_CASE(16, 4);
+                if (mt <= 8) rc = launch_tile<T, 8, 4>(a, n0, m0, wap, wat, stream);
+                else rc = launch_tile<T, 16, 4>(a, n0, m0, wap, wat, stream);
             }
-#undef DMM_COST_CASE
             if (rc != DMM_OK) return rc;
         }
     }
     return DMM_OK;
 }
 
-}  // namespace dmm
-
-static int iou_counts_dispatch(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, int B, int N,
-                               int M, int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b,
-                               int64_t st2_m, const int32_t *n_valid, const int32_t *m_valid, int32_t *inter,
-                               int32_t *area_p, int32_t *area_t, int32_t *inter2, int32_t *area_t2,
-                               bool tables_zeroed, dmm_stream_t stream) {
-    if (B < 0 || N < 0 || M < 0 || HW < 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || N == 0 || M == 0) return DMM_OK;
-    if (!masks_p || !masks_t || !inter || !area_p || !area_t) return DMM_ERR_BAD_ARG;
-    if (masks_t2 && (!inter2 || !area_t2)) return DMM_ERR_BAD_ARG;
-    const int64_t min_stride = dtype == DMM_PACKED1 ? 4 * ((int64_t)(HW + 255) / 256) : HW;
-    if (sp_n < min_stride || st_m < min_stride || (masks_t2 && st2_m < min_stride)) return DMM_ERR_BAD_ARG;
-    if (B > 65535) {   // grid.y limit: run in batch slices
-        const size_t es = dtype == DMM_F32 ? 4 : (dtype == DMM_PACKED1 ? 8 : 2);
-        for (int b0 = 0; b0 < B; b0 += 65535) {
-            const int nb = B - b0 < 65535 ? B - b0 : 65535;
-            const int rc = iou_counts_dispatch(
-                sp_b == dmm::kFrameTable ? (const char *)masks_p + sizeof(void *) * (size_t)b0
-                                         : (const char *)masks_p + es * (size_t)b0 * sp_b,
-                (const char *)masks_t + es * (size_t)b0 * st_b,
-                masks_t2 ? (const char *)masks_t2 + es * (size_t)b0 * st2_b : nullptr, dtype, nb, N, M, HW, sp_b, sp_n,
-                st_b, st_m, st2_b, st2_m, n_valid ? n_valid + b0 : nullptr, m_valid ? m_valid + b0 : nullptr,
-                inter + (size_t)b0 * M * N, area_p + (size_t)b0 * N, area_t + (size_t)b0 * M,
-                inter2 ? inter2 + (size_t)b0 * M * N : nullptr, area_t2 ? area_t2 + (size_t)b0 * M : nullptr, tables_zeroed,
-                stream);
-            if (rc != DMM_OK) return rc;
-        }
-        return DMM_OK;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    switch (dtype) {
-        case DMM_PACKED1:
-            return dmm::iou_counts_typed<dmm::packed_t>((const dmm::packed_t *)masks_p, (const dmm::packed_t *)masks_t,
-                                                        (const dmm::packed_t *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b,
-                                                        st_m, st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t,
-                                                        inter2, area_t2, tables_zeroed, s);
-        case DMM_F32:
-            return dmm::iou_counts_typed<float>((const float *)masks_p, (const float *)masks_t, (const float *)masks_t2, B,
-                                                N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m, n_valid, m_valid, inter,
-                                                area_p, area_t, inter2, area_t2, tables_zeroed, s);
-        case DMM_F16:
-            return dmm::iou_counts_typed<dmm::f16_t>((const dmm::f16_t *)masks_p, (const dmm::f16_t *)masks_t,
-                                                     (const dmm::f16_t *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m,
-                                                     st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2,
-                                                     area_t2, tables_zeroed, s);
-        case DMM_BF16:
-            return dmm::iou_counts_typed<dmm::bf16_t>((const dmm::bf16_t *)masks_p, (const dmm::bf16_t *)masks_t,
-                                                      (const dmm::bf16_t *)masks_t2, B, N, M, HW, sp_b, sp_n, st_b, st_m,
-                                                      st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2,
-                                                      area_t2, tables_zeroed, s);
-        default:
-            return DMM_ERR_BAD_ARG;
-    }
+// the bundle advanced to frames [b0, b0 + nb): whatever has one entry, row or table per frame moves b0 frames on
+static CountArgs count_slice(const CountArgs &a, int b0, int nb) {
+    const size_t es = a.dtype == DMM_F32 ? 4 : (a.dtype == DMM_PACKED1 ? 8 : 2);
+    const auto planes = [&](const void *p, int64_t stride_b) { return (const void *)((const char *)p + es * (size_t)b0 * stride_b); };
+    const size_t MN = (size_t)a.M * a.N;
+    CountArgs s = a;
+    s.B = nb;
+    s.masks_p = a.sp_b == kFrameTable ? (const char *)a.masks_p + sizeof(void *) * (size_t)b0 : planes(a.masks_p, a.sp_b);
+    s.masks_t = planes(a.masks_t, a.st_b);
+    if (a.masks_t2) s.masks_t2 = planes(a.masks_t2, a.st2_b);
+    if (a.n_valid) s.n_valid = a.n_valid + b0;
+    if (a.m_valid) s.m_valid = a.m_valid + b0;
+    s.inter = a.inter + b0 * MN;
+    s.area_p = a.area_p + (size_t)b0 * a.N;
+    s.area_t = a.area_t + (size_t)b0 * a.M;
+    if (a.inter2) s.inter2 = a.inter2 + b0 * MN;
+    if (a.area_t2) s.area_t2 = a.area_t2 + (size_t)b0 * a.M;
+    return s;
 }
 
+int iou_counts_launch(const CountArgs &a, bool tables_zeroed, hipStream_t stream) {
+    if (a.B < 0 || a.N < 0 || a.M < 0 || a.HW < 0) return DMM_ERR_BAD_ARG;
+    if (a.B == 0 || a.N == 0 || a.M == 0) return DMM_OK;
+    if (!a.masks_p || !a.masks_t || !a.inter || !a.area_p || !a.area_t) return DMM_ERR_BAD_ARG;
+    if (a.masks_t2 && (!a.inter2 || !a.area_t2)) return DMM_ERR_BAD_ARG;
+    const int64_t min_stride = a.dtype == DMM_PACKED1 ? 4 * ((int64_t)(a.HW + 255) / 256) : a.HW;
+    if (a.sp_n < min_stride || a.st_m < min_stride || (a.masks_t2 && a.st2_m < min_stride)) return DMM_ERR_BAD_ARG;
+    constexpr int kMaxFrames = 65535;                            // grid.y: more frames run in batch slices
+    for (int b0 = 0; b0 < a.B; b0 += kMaxFrames) {
+        const CountArgs s = count_slice(a, b0, a.B - b0 < kMaxFrames ? a.B - b0 : kMaxFrames);
+        const int rc = with_count_plane_type(s.dtype, s.masks_p, [&](auto *planes) {
+            return iou_counts_typed<plane_type_of<decltype(planes)>>(s, tables_zeroed, stream);
+        });
+        if (rc != DMM_OK) return rc;
+    }
+    return DMM_OK;
+}
+
+}  // namespace dmm
+
+// ---- the entries: each fills a bundle.  The *_frames forms take a device table of per-frame base pointers for the proposal
+// planes (the per-video tensors of DMM_Model: no batch copy) = the batch form with the stride sentinel kFrameTable; the dual
+// forms count a second template set in the same pass and refuse a call without one before anything else ----
 extern "C" int dmm_iou_counts(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW,
                               int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid,
                               const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t,
                               dmm_stream_t stream) {
-    return iou_counts_dispatch(masks_p, masks_t, nullptr, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, 0, 0, n_valid,
-                               m_valid, inter, area_p, area_t, nullptr, nullptr, false, stream);
+    return dmm::iou_counts_launch({masks_p, masks_t, nullptr, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, 0, 0, n_valid,
+                                   m_valid, inter, area_p, area_t, nullptr, nullptr}, false, (hipStream_t)stream);
 }
-
-// dmm_iou_counts for a caller that has ALREADY zeroed inter / area_p / area_t on this stream (dmm_match_forward: the
-// feature-similarity kernel clears them, one memset node less in front of the solver's dependent chain)
-namespace dmm {
-int iou_counts_prezeroed(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW, int64_t sp_b,
-                         int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid, const int32_t *m_valid,
-                         int32_t *inter, int32_t *area_p, int32_t *area_t, dmm_stream_t stream) {
-    return iou_counts_dispatch(masks_p, masks_t, nullptr, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, 0, 0, n_valid,
-                               m_valid, inter, area_p, area_t, nullptr, nullptr, true, stream);
-}
-// the dual form (templates + targets) on tables the caller has already zeroed; sp_b may be kFrameTable (masks_p = the
-// device table of per-frame base pointers)
-int iou_counts_dual_prezeroed(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, int B, int N, int M,
-                              int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
-                              const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
-                              int32_t *area_t, int32_t *inter2, int32_t *area_t2, dmm_stream_t stream) {
-    return iou_counts_dispatch(masks_p, masks_t, masks_t2, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m,
-                               n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, true, stream);
-}
-}  // namespace dmm
 
 extern "C" int dmm_iou_counts_dual(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, int B,
                                    int N, int M, int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m,
@@ -795,17 +735,17 @@ extern "C" int dmm_iou_counts_dual(const void *masks_p, const void *masks_t, con
                                    int32_t *inter, int32_t *area_p, int32_t *area_t, int32_t *inter2, int32_t *area_t2,
                                    dmm_stream_t stream) {
     if (!masks_t2) return DMM_ERR_BAD_ARG;
-    return iou_counts_dispatch(masks_p, masks_t, masks_t2, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m,
-                               n_valid, m_valid, inter, area_p, area_t, inter2, area_t2, false, stream);
+    return dmm::iou_counts_launch({masks_p, masks_t, masks_t2, dtype, B, N, M, HW, sp_b, sp_n, st_b, st_m, st2_b, st2_m,
+                                   n_valid, m_valid, inter, area_p, area_t, inter2, area_t2}, false, (hipStream_t)stream);
 }
 
-// ---- per-frame pointer tables for the proposal planes (the per-video tensors of DMM_Model: no batch copy) ----
 extern "C" int dmm_iou_counts_frames(const void *const *masks_p_frames, const void *masks_t, int dtype, int B, int N,
                                      int M, int HW, int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid,
                                      const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t,
                                      dmm_stream_t stream) {
-    return iou_counts_dispatch((const void *)masks_p_frames, masks_t, nullptr, dtype, B, N, M, HW, dmm::kFrameTable, sp_n,
-                               st_b, st_m, 0, 0, n_valid, m_valid, inter, area_p, area_t, nullptr, nullptr, false, stream);
+    return dmm::iou_counts_launch({masks_p_frames, masks_t, nullptr, dtype, B, N, M, HW, dmm::kFrameTable, sp_n, st_b, st_m,
+                                   0, 0, n_valid, m_valid, inter, area_p, area_t, nullptr, nullptr}, false,
+                                  (hipStream_t)stream);
 }
 
 extern "C" int dmm_iou_counts_dual_frames(const void *const *masks_p_frames, const void *masks_t, const void *masks_t2,
@@ -814,7 +754,7 @@ extern "C" int dmm_iou_counts_dual_frames(const void *const *masks_p_frames, con
                                           const int32_t *m_valid, int32_t *inter, int32_t *area_p, int32_t *area_t,
                                           int32_t *inter2, int32_t *area_t2, dmm_stream_t stream) {
     if (!masks_t2) return DMM_ERR_BAD_ARG;
-    return iou_counts_dispatch((const void *)masks_p_frames, masks_t, masks_t2, dtype, B, N, M, HW, dmm::kFrameTable,
-                               sp_n, st_b, st_m, st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2, area_t2,
-                               false, stream);
+    return dmm::iou_counts_launch({masks_p_frames, masks_t, masks_t2, dtype, B, N, M, HW, dmm::kFrameTable, sp_n, st_b, st_m,
+                                   st2_b, st2_m, n_valid, m_valid, inter, area_p, area_t, inter2, area_t2}, false,
+                                  (hipStream_t)stream);
 }

@@ -1,18 +1,9 @@
 // dmm_front.hip -- what the one-call entries (dmm_api.hip, dmm_train.hip) share in front of and behind the solver:
-// match_front (feature similarity + IoU counts, with their fallback chain) and match_mix.  See dmm_launchers.h.
+// match_front (feature similarity + IoU counts, with their fallback chain) and match_mix.  See dmm_launchers.h: a Front IS
+// the counts' bundle (CountArgs) plus the similarity's arguments, so the count launchers take it as it stands.
 #include "dmm_launchers.h"
 
 namespace dmm {
-
-// the counts of the front on tables that are zero: templates alone, or templates and targets in one pass
-static int front_counts(const Front &f, hipStream_t stream) {
-    if (f.targets)
-        return iou_counts_dual_prezeroed(f.masks_p, f.masks_t, f.targets, f.dtype, f.B, f.N, f.M, f.HW, f.sp_b, f.sp_n,
-                                         f.st_b, f.st_m, f.sg_b, f.sg_m, f.n_valid, f.m_valid, f.inter, f.area_p, f.area_t,
-                                         f.inter2, f.area_t2, stream);
-    return iou_counts_prezeroed(f.masks_p, f.masks_t, f.dtype, f.B, f.N, f.M, f.HW, f.sp_b, f.sp_n, f.st_b, f.st_m,
-                                f.n_valid, f.m_valid, f.inter, f.area_p, f.area_t, stream);
-}
 
 int match_front(const Front &f, hipStream_t stream, bool *fused) {
     if (fused) *fused = false;
@@ -21,9 +12,7 @@ int match_front(const Front &f, hipStream_t stream, bool *fused) {
     int rc = DMM_ERR_UNSUPPORTED;
     // 1. a handful of dense frames: table clear, then similarity and counts beside each other in ONE launch
     if (dense && lanes) {
-        rc = front_small_launch(f.masks_p, f.masks_t, f.targets, f.dtype, f.feat_t, f.feat_p, f.B, f.N, f.M, f.HW, f.D,
-                                f.sp_b, f.sp_n, f.st_b, f.st_m, f.sg_b, f.sg_m, f.cos, f.inter, f.area_p, f.area_t, f.inter2,
-                                f.area_t2, f.tables_zero, stream);
+        rc = front_small_launch(f, stream);
         if (rc == DMM_OK && fused) *fused = true;
         if (rc != DMM_ERR_UNSUPPORTED) return rc;
     }
@@ -33,11 +22,11 @@ int match_front(const Front &f, hipStream_t stream, bool *fused) {
     if (lanes && (dense || f.ragged_lanes))
         rc = cosine_lanes_launch(f.feat_t, f.feat_p, f.B, f.N, f.M, f.D, f.cos, stream, f.inter, (int64_t)f.table_words,
                                  f.n_valid);
-    if (rc == DMM_OK) return front_counts(f, stream);
+    if (rc == DMM_OK) return iou_counts_launch(f, /*tables_zeroed=*/true, stream);
     if (rc != DMM_ERR_UNSUPPORTED) return rc;
     // 3. a D the lanes kernel does not take (or COSINE_KERNEL = 1): clear, count, then the tile kernel on dense batches
     DMM_HIP_TRY(zero_async(f.inter, sizeof(int32_t) * f.table_words, stream));
-    rc = front_counts(f, stream);
+    rc = iou_counts_launch(f, /*tables_zeroed=*/true, stream);
     if (rc != DMM_OK) return rc;
     if (dense && f.dense_tile) {
         rc = dmm_cosine_features_f32(f.feat_t, f.feat_p, f.B, f.N, f.M, f.D, f.cos, stream);

@@ -1,6 +1,7 @@
 // dmm_launchers.h -- every dmm:: launcher that one .hip defines and another calls, declared ONCE (the solver's are in
 // dmm_solve.h).  The defining file includes this header too, so a definition that drifts from its declaration does not
-// compile; default arguments are given here and nowhere else.
+// compile; default arguments are given here and nowhere else.  The host-side argument bundles that cross files live here
+// too: CountArgs (the IoU counts) and Front (the one-call entries' front), which derives from it.
 #pragma once
 #include "dmm_common.h"
 
@@ -16,20 +17,22 @@ int feature_normalize2_launch(const float *in_a, int64_t rows_a, float *out_a, f
                               int64_t rows_b, float *out_b, float *norms_b, int D, hipStream_t stream,
                               void *zero_ptr = nullptr, size_t zero_bytes = 0);
 
-// dmm_cost.hip: similarity and counts of a handful of dense frames in one launch (DMM_ERR_UNSUPPORTED: nothing launched)
-int front_small_launch(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, const float *feat_t,
-                       const float *feat_p, int B, int N, int M, int HW, int D, int64_t sp_b, int64_t sp_n, int64_t st_b,
-                       int64_t st_m, int64_t st2_b, int64_t st2_m, float *cos_out, int32_t *inter, int32_t *area_p,
-                       int32_t *area_t, int32_t *inter2, int32_t *area_t2, bool tables_zero, hipStream_t stream);
-// dmm_cost.hip: dmm_iou_counts / dmm_iou_counts_dual on tables the caller has already cleared on this stream (the
-// dispatch behind every count entry with tables_zeroed = true)
-int iou_counts_prezeroed(const void *masks_p, const void *masks_t, int dtype, int B, int N, int M, int HW, int64_t sp_b,
-                         int64_t sp_n, int64_t st_b, int64_t st_m, const int32_t *n_valid, const int32_t *m_valid,
-                         int32_t *inter, int32_t *area_p, int32_t *area_t, dmm_stream_t stream);
-int iou_counts_dual_prezeroed(const void *masks_p, const void *masks_t, const void *masks_t2, int dtype, int B, int N, int M,
-                              int HW, int64_t sp_b, int64_t sp_n, int64_t st_b, int64_t st_m, int64_t st2_b, int64_t st2_m,
-                              const int32_t *n_valid, const int32_t *m_valid, int32_t *inter, int32_t *area_p,
-                              int32_t *area_t, int32_t *inter2, int32_t *area_t2, dmm_stream_t stream);
+// The arguments of the IoU counts, for every caller and for dmm_cost.hip itself: the planes, the live counts, the tables.
+struct CountArgs {
+    const void *masks_p, *masks_t;       // the planes the counts read (DMM_PACKED1: words)
+    const void *masks_t2;                // a second template set counted in the same pass (training: the targets); null: none
+    int dtype;
+    int B, N, M, HW;
+    int64_t sp_b, sp_n, st_b, st_m;      // element strides; sp_b = kFrameTable: masks_p is the device table of the frames
+    int64_t st2_b, st2_m;
+    const int32_t *n_valid, *m_valid;
+    int32_t *inter, *area_p, *area_t;    // out [B, M, N], [B, N], [B, M]
+    int32_t *inter2, *area_t2;           // the second set's tables (null without masks_t2)
+};
+// dmm_cost.hip: the dispatch behind every count entry.  tables_zeroed: the caller has already cleared every table on this
+// stream (the front: the launch before this one did) -- otherwise the counts clear them first
+int iou_counts_launch(const CountArgs &a, bool tables_zeroed, hipStream_t stream);
+
 // dmm_mix.hip: dmm_mask_mix_bwd into a dRb the caller has already cleared (the backward behind every mix entry with
 // MixBwd::drb_zeroed set)
 int mask_mix_bwd_prezeroed(const float *Rb, const void *masks_p, int dtype, const float *dout, int B, int N, int M, int Pp,
@@ -58,25 +61,20 @@ static inline bool soft_planes(int dtype) { return dtype == DMM_F32 || dtype == 
 //   3. a clearing launch, the counts, then the dense tile similarity (dmm_cosine_features_f32)
 //   4. ... or both feature sets normalised and dmm_cosine_f32
 // COSINE_KERNEL = 1 skips 1 and 2.  The last four fields are where the entries differ on purpose.
-struct Front {
-    const void *masks_p, *masks_t;       // the planes the counts read (DMM_PACKED1: words) and their element strides
-    int dtype;
-    int64_t sp_b, sp_n, st_b, st_m;
-    const void *targets;                 // training: a second template set counted in the same pass (null: none)
-    int64_t sg_b, sg_m;
+struct Front : CountArgs {
     const float *feat_p, *feat_t;
-    int B, N, M, HW, D;
-    const int32_t *n_valid, *m_valid;
+    int D;
     float *cos;                          // out [B, M, N]
-    int32_t *inter, *area_p, *area_t;    // out; with inter2 | area_t2 one block of table_words words from `inter`
-    int32_t *inter2, *area_t2;           // the targets' tables (null without targets)
-    size_t table_words;
+    size_t table_words;                  // inter | area_p | area_t (| inter2 | area_t2) are one block of so many words
     float *featn_p, *featn_t;            // room for the normalised rows of link 4
     bool tables_zero;                    // the caller vouches the tables are zero already (link 1 skips its clear)
     bool ragged_lanes;                   // ragged batches take link 2 (dmm_match_forward_ws keeps them on link 4)
     bool dense_tile;                     // dense batches may take link 3's tile kernel (the packed entries go on to 4)
     bool split_norm;                     // link 4 normalises with two launches (dmm_match_forward_ws), not one
 };
+// dmm_cost.hip: link 1 -- similarity and counts of a handful of dense frames in one launch (DMM_ERR_UNSUPPORTED: nothing
+// launched)
+int front_small_launch(const Front &f, hipStream_t stream);
 // *fused (may be null): link 1 ran -- its tables are the ones the solver may be asked to leave zero
 int match_front(const Front &f, hipStream_t stream, bool *fused = nullptr);
 // full_outmask [B, M, HW] from Rb: train mode keeps every R > 0.01, so the rows share planes and the union of their

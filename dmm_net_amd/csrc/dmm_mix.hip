@@ -912,17 +912,6 @@ static int mix_entry_check(const MixArgs &a, bool have_pointers, bool empty_hw_o
     return DMM_OK;
 }
 
-// f(planes) with the planes as const float / f16_t / bf16_t * -- the one place a dtype becomes a type
-template <typename F>
-static int with_plane_type(int dtype, const void *masks_p, F &&f) {
-    switch (dtype) {
-        case DMM_F32: return f((const float *)masks_p);
-        case DMM_F16: return f((const f16_t *)masks_p);
-        case DMM_BF16: return f((const bf16_t *)masks_p);
-        default: return DMM_ERR_BAD_ARG;
-    }
-}
-
 // the forward behind every entry
 static int mask_mix_forward(const MixFwd &a) {
     bool go;
@@ -931,8 +920,8 @@ static int mask_mix_forward(const MixFwd &a) {
     if (a.so_m < a.HW) return DMM_ERR_BAD_ARG;
     if (a.out_dtype != DMM_F32 && a.out_dtype != a.dtype) return DMM_ERR_BAD_ARG;   // fp32, or the planes' own 16-bit type
     const MixKind kind = mix_fwd_kind(a.N, a.M, a.shared_entry);
-    return with_plane_type(a.dtype, a.masks_p, [&](auto *planes) {
-        using T = std::remove_const_t<std::remove_pointer_t<decltype(planes)>>;
+    return with_plane_type(a.dtype, a.masks_p, DMM_ERR_BAD_ARG, [&](auto *planes) {
+        using T = plane_type_of<decltype(planes)>;
         const auto launch = [&](auto *out) {                                  // out: float or T, no other pair is compiled
             switch (kind) {
                 case MixKind::Wide: return mask_mix_wide_typed(a, planes, out);
@@ -970,7 +959,7 @@ static int mask_mix_backward(MixBwd a, bool det = false, size_t slab_bytes = 0) 
     if (need && !a.slab) return DMM_ERR_BAD_ARG;
     if (slab_bytes < need) return DMM_ERR_WORKSPACE;
     if (kind == MixKind::Wide) a.slab = nullptr;                              // deterministic as it is
-    return with_plane_type(a.dtype, a.masks_p, [&](auto *planes_p) {
+    return with_plane_type(a.dtype, a.masks_p, DMM_ERR_BAD_ARG, [&](auto *planes_p) {
         if (kind == MixKind::Wide) return mask_mix_bwd_wide_typed(a, planes_p);
         if (det) return mask_mix_bwd_det_typed(a, kind, planes, planes_p);
         return kind == MixKind::Union ? mask_mix_bwd_shared_typed(a, planes_p) : mask_mix_bwd_typed(a, planes_p);

@@ -227,7 +227,7 @@ extern "C" int dmm_match_train_forward(const void *masks_p, const void *masks_t,
     dmm::Front f{};
     f.masks_p = masks_p; f.masks_t = masks_t; f.dtype = mask_dtype;
     f.sp_b = sp_b; f.sp_n = sp_n; f.st_b = st_b; f.st_m = st_m;
-    if (dual) { f.targets = targets; f.sg_b = sg_b; f.sg_m = sg_m; f.inter2 = w.inter2; f.area_t2 = w.area_t2; }
+    if (dual) { f.masks_t2 = targets; f.st2_b = sg_b; f.st2_m = sg_m; f.inter2 = w.inter2; f.area_t2 = w.area_t2; }
     f.feat_p = feat_p; f.feat_t = feat_t;
     f.B = B; f.N = N; f.M = M; f.HW = HW; f.D = D;
     f.n_valid = n_valid; f.m_valid = m_valid;

@@ -176,6 +176,50 @@ def test_mix_entries_validate_their_arguments_without_gpu():
     assert size(0, 4, 2, 4, 16) == 0 and size(1, 4, 0, 4, 16) == 0 and size(1, 4, 2, 3, 16) == 0 and size(1, 4, 2, 4, -1) == 0
 
 
+COUNT_ENTRIES = ("dmm_iou_counts", "dmm_iou_counts_dual", "dmm_iou_counts_frames", "dmm_iou_counts_dual_frames")
+
+
+def _count_status(L, entry, *, B=1, N=4, M=2, HW=16, sp_n=16, st_m=16, st2_m=16, dtype=0, planes_p=True, planes_t=True,
+                  planes_t2=True, inter=True, area_p=True, area_t=True, inter2=True, area_t2=True):
+    """One count entry's status for a call that must be answered before the device is touched (every pointer is the
+    address 8).  ``planes_t2`` / ``st2_m`` / ``inter2`` / ``area_t2`` go to the dual entries only."""
+    p = lambda have: ctypes.c_void_p(8) if have else None
+    dual, frames = "_dual" in entry, "_frames" in entry
+    args = (p(planes_p), p(planes_t)) + ((p(planes_t2),) if dual else ()) + (dtype, B, N, M, HW)
+    args += (() if frames else (N * sp_n,)) + (sp_n, M * st_m, st_m) + ((M * st2_m, st2_m) if dual else ())
+    args += (None, None, p(inter), p(area_p), p(area_t)) + ((p(inter2), p(area_t2)) if dual else ())
+    return getattr(L, entry)(*args, None)
+
+
+def test_count_entries_validate_their_arguments_without_gpu():
+    """Every count entry's answer to arguments it rejects, or has nothing to do for, before any launch.  The expected statuses
+    are those of the one dispatch behind the four entries as it stood when it took every argument by name (commit ebfc1cf),
+    read off that code and confirmed against a build of it."""
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    L = _lib.load()
+    OK, BAD = 0, 1
+    null = dict(planes_p=False, planes_t=False, inter=False, area_p=False, area_t=False, inter2=False, area_t2=False)
+    for entry in COUNT_ENTRIES:
+        dual = "_dual" in entry
+        st = lambda **kw: _count_status(L, entry, **kw)
+        for kw in (dict(B=-1), dict(N=-1), dict(M=-1), dict(HW=-1), dict(planes_p=False), dict(planes_t=False), dict(inter=False),
+                   dict(area_p=False), dict(area_t=False), dict(sp_n=15), dict(st_m=15), dict(dtype=7), dict(dtype=-1),
+                   dict(dtype=_lib.DTYPE_PACKED1, sp_n=3), dict(dtype=_lib.DTYPE_PACKED1, st_m=3),
+                   dict(dtype=_lib.DTYPE_PACKED1, HW=257, sp_n=7)):                  # 1-bit planes: 4 * ceil(HW / 256) words
+            assert st(**kw) == BAD, (entry, kw)
+        for kw in (dict(B=0), dict(N=0), dict(M=0)):                                 # nothing to do, whatever the pointers
+            assert st(**kw) == OK and st(**kw, **null) == OK and st(**kw, dtype=7, sp_n=0) == OK, (entry, kw)
+        for kw in (dict(B=0, HW=-1), dict(N=0, M=-1), dict(M=0, B=-1)):              # sizes before "nothing to do"
+            assert st(**kw, **null) == BAD, (entry, kw)
+        if dual:
+            for kw in (dict(inter2=False), dict(area_t2=False), dict(st2_m=15), dict(dtype=_lib.DTYPE_PACKED1, st2_m=3)):
+                assert st(**kw) == BAD, (entry, kw)
+            # a second template set is what the entry is for: asked before anything else
+            for kw in (dict(), dict(B=0), dict(N=0), dict(M=0), dict(B=0, **null)):
+                assert st(planes_t2=False, **kw) == BAD, (entry, kw)
+
+
 def test_training_entries_validate_their_arguments_without_gpu():
     """(5d) / (5e) / (1e): workspace sizes are positive and grow with the batch, null pointers / negative sizes answer
     DMM_ERR_BAD_ARG, tables outside the fast kernels' envelope answer DMM_ERR_UNSUPPORTED (the caller then takes the granular
