@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import ctypes
 import threading
+from collections import namedtuple
 from typing import Optional, Tuple
 
 import torch
@@ -32,13 +33,50 @@ def _need_gpu(*ts):
             raise _lib.DmmError("dmm_net_amd ops need tensors on an MI355X device (no CPU fallback)")
 
 
+def _plane_rows(t: torch.Tensor) -> torch.Tensor:
+    """[..., K, H, W] as the C ABI reads planes: the H*W elements of a plane contiguous, the plane stride at least H*W.  A
+    tensor that is laid out so (``alloc_planes`` strides, slices along the batch or plane axis) and an empty one are passed as
+    they are; any other is copied.  (Strides and shape are read once each: the one-frame calls are host bound.)"""
+    s, n = t.stride(), t.shape
+    if (s[-1] == 1 and s[-2] == n[-1] and s[-3] >= n[-2] * n[-1]) or t.numel() == 0:
+        return t
+    return t.contiguous()
+
+
 def _planes(t: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
     """[B,K,H,W] with contiguous H*W planes -> (tensor, frame stride, plane stride) in elements."""
     assert t.dim() == 4, t.shape
-    H, W = t.shape[2], t.shape[3]
-    if t.shape[0] * t.shape[1] * H * W and not (t.stride(3) == 1 and t.stride(2) == W and t.stride(1) >= H * W):
-        t = t.contiguous()
+    t = _plane_rows(t)
     return t, t.stride(0), t.stride(1)
+
+
+def _planes3(t: torch.Tensor):
+    """[K,H,W] with contiguous H*W planes -> (tensor, plane stride in elements)."""
+    assert t.dim() == 3, t.shape
+    t = _plane_rows(t)
+    return t, t.stride(0)
+
+
+def _batch_planes(t: torch.Tensor, one_frame: bool = False):
+    """[B,K,H,W] planes, or with ``one_frame`` the [K,H,W] planes of a batch of one -> (tensor, K, frame stride, plane stride)."""
+    t = _plane_rows(t)
+    s = t.stride()
+    if one_frame:
+        assert len(s) == 3, t.shape
+        return t, t.shape[0], t.shape[0] * s[0], s[0]
+    assert len(s) == 4, t.shape
+    return t, t.shape[1], s[0], s[1]
+
+
+def _cf(t):
+    return None if t is None else t.contiguous().float()
+
+
+def _count_tables(B, N, M, dev, dual=False):
+    """inter [B,M,N], area_p [B,N], area_t [B,M] int32 (``dual``: + inter2, area_t2 of the second template set)."""
+    i32 = dict(dtype=torch.int32, device=dev)
+    one = (torch.empty((B, M, N), **i32), torch.empty((B, N), **i32), torch.empty((B, M), **i32))
+    return one + (torch.empty((B, M, N), **i32), torch.empty((B, M), **i32)) if dual else one
 
 
 def alloc_planes(B: int, K: int, H: int, W: int, dtype, device, align_bytes: int = 128, fill=None) -> torch.Tensor:
@@ -74,9 +112,7 @@ class FramePlanes:
         for t in planes:
             _need_gpu(t)
             assert t.dim() == 3 and tuple(t.shape[-2:]) == (H, W) and t.dtype == self.dtype and t.device == self.device
-            if t.shape[0] and not (t.stride(2) == 1 and t.stride(1) == W and t.stride(0) >= H * W):
-                t = t.contiguous()
-            fixed.append(t)
+            fixed.append(_plane_rows(t))
         strides = {int(t.stride(0)) for t in fixed if t.shape[0] > 1}
         if len(strides) > 1:                         # mixed plane strides: densify the odd ones
             fixed = [t if (t.shape[0] <= 1 or t.stride(0) == H * W) else t.contiguous() for t in fixed]
@@ -107,41 +143,42 @@ class FramePlanes:
         return out
 
 
+def _proposal_planes(masks_p, one_frame: bool = False):
+    """The proposal planes of a call, whatever holds them: a [B,N,H,W] tensor, a ``FramePlanes`` or, with ``one_frame``, a
+    [N,H,W] tensor -> (address, torch dtype, B, N, H, W, frame stride, plane stride, device, what keeps the address alive).
+    For a ``FramePlanes`` the address is its pointer table's and the frame stride is ``_lib.FRAME_TABLE``, as the one-call
+    training entries take it; the granular ``*_frames`` entries take the plane stride alone (``_sp``)."""
+    if isinstance(masks_p, FramePlanes):
+        fp = masks_p
+        return fp.table.data_ptr(), fp.dtype, fp.B, fp.N, fp.H, fp.W, _lib.FRAME_TABLE, fp.plane_stride, fp.device, fp
+    _need_gpu(masks_p)
+    t, N, sp_b, sp_n = _batch_planes(masks_p, one_frame)
+    return t.data_ptr(), t.dtype, 1 if one_frame else t.shape[0], N, t.shape[-2], t.shape[-1], sp_b, sp_n, t.device, t
+
+
+def _sp(sp_b, sp_n):
+    """-> (is a pointer table, the proposal strides of a granular entry: the ``*_frames`` entries have no frame stride)."""
+    return (True, (sp_n,)) if sp_b == _lib.FRAME_TABLE else (False, (sp_b, sp_n))
+
+
 def padded_width(N: int, M: int) -> int:
     """Pp = solver width after the reference's zero padding (match_model.py:109-113)."""
     return N if N > M else M + 1
 
 
-def iou_counts(masks_p: torch.Tensor, masks_t: torch.Tensor, n_valid=None, m_valid=None):
-    """-> inter [B,M,N] i32, area_p [B,N] i32, area_t [B,M] i32 (match_helper.py:9-28 on all pairs)."""
-    if isinstance(masks_p, FramePlanes):
-        fp = masks_p
-        _need_gpu(masks_t)
-        assert fp.dtype == masks_t.dtype and n_valid is not None
-        masks_t, st_b, st_m = _planes(masks_t)
-        B, N, H, W, M = fp.B, fp.N, fp.H, fp.W, masks_t.shape[1]
-        assert masks_t.shape[0] == B and tuple(masks_t.shape[2:]) == (H, W)
-        dev = fp.device
-        inter = torch.empty((B, M, N), dtype=torch.int32, device=dev)
-        ap = torch.empty((B, N), dtype=torch.int32, device=dev)
-        at = torch.empty((B, M), dtype=torch.int32, device=dev)
-        _lib.call("dmm_iou_counts_frames", dev, _ptr(fp.table), _ptr(masks_t), _DT[fp.dtype], B, N, M, H * W,
-                  fp.plane_stride, st_b, st_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
-                  _stream(masks_t))
-        return inter, ap, at
-    _need_gpu(masks_p, masks_t)
-    assert masks_p.dtype == masks_t.dtype and masks_p.dtype in _DT
-    masks_p, sp_b, sp_n = _planes(masks_p)
+def iou_counts(masks_p, masks_t: torch.Tensor, n_valid=None, m_valid=None):
+    """-> inter [B,M,N] i32, area_p [B,N] i32, area_t [B,M] i32 (match_helper.py:9-28 on all pairs).  masks_p: [B,N,H,W]
+    tensor or ``FramePlanes`` (then with ``n_valid``)."""
+    p, dt, B, N, H, W, sp_b, sp_n, dev, _keep = _proposal_planes(masks_p)
+    frames, sp = _sp(sp_b, sp_n)
+    _need_gpu(masks_t)
+    assert dt == masks_t.dtype and dt in _DT and (n_valid is not None or not frames)
     masks_t, st_b, st_m = _planes(masks_t)
-    B, N, H, W = masks_p.shape
     M = masks_t.shape[1]
-    assert masks_t.shape[0] == B and masks_t.shape[2:] == masks_p.shape[2:]
-    dev = masks_p.device
-    inter = torch.empty((B, M, N), dtype=torch.int32, device=dev)
-    ap = torch.empty((B, N), dtype=torch.int32, device=dev)
-    at = torch.empty((B, M), dtype=torch.int32, device=dev)
-    _lib.call("dmm_iou_counts", dev, _ptr(masks_p), _ptr(masks_t), _DT[masks_p.dtype], B, N, M, H * W, sp_b, sp_n, st_b,
-              st_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), _stream(masks_p))
+    assert masks_t.shape[0] == B and tuple(masks_t.shape[2:]) == (H, W)
+    inter, ap, at = _count_tables(B, N, M, dev)
+    _lib.call("dmm_iou_counts_frames" if frames else "dmm_iou_counts", dev, p, _ptr(masks_t), _DT[dt], B, N, M, H * W, *sp,
+              st_b, st_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), _stream(masks_t))
     return inter, ap, at
 
 
@@ -205,46 +242,27 @@ def iou_counts_packed(packed_p: torch.Tensor, packed_t: torch.Tensor, HW: int, n
     M = packed_t.shape[1]
     assert wd == pack_words(HW) and packed_t.shape[2] == wd
     dev = packed_p.device
-    inter = torch.empty((B, M, N), dtype=torch.int32, device=dev)
-    ap = torch.empty((B, N), dtype=torch.int32, device=dev)
-    at = torch.empty((B, M), dtype=torch.int32, device=dev)
+    inter, ap, at = _count_tables(B, N, M, dev)
     _lib.call("dmm_iou_counts", dev, _ptr(packed_p), _ptr(packed_t), _lib.DTYPE_PACKED1, B, N, M, HW, N * wd, wd, M * wd,
               wd, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), _stream(packed_p))
     return inter, ap, at
 
 
-def iou_counts_dual(masks_p: torch.Tensor, masks_t: torch.Tensor, masks_t2: torch.Tensor, n_valid=None, m_valid=None):
-    """One pass over the proposal planes against TWO template sets (templates + training targets).
-    -> (inter, area_p, area_t), (inter2, area_t2)."""
-    if isinstance(masks_p, FramePlanes):
-        fp = masks_p
-        _need_gpu(masks_t, masks_t2)
-        assert fp.dtype == masks_t.dtype == masks_t2.dtype and masks_t.shape == masks_t2.shape and n_valid is not None
-        masks_t, st_b, st_m = _planes(masks_t)
-        masks_t2, st2_b, st2_m = _planes(masks_t2)
-        B, N, H, W, M = fp.B, fp.N, fp.H, fp.W, masks_t.shape[1]
-        i32 = dict(dtype=torch.int32, device=fp.device)
-        inter, inter2 = torch.empty((B, M, N), **i32), torch.empty((B, M, N), **i32)
-        ap, at, at2 = torch.empty((B, N), **i32), torch.empty((B, M), **i32), torch.empty((B, M), **i32)
-        _lib.call("dmm_iou_counts_dual_frames", fp.device, _ptr(fp.table), _ptr(masks_t), _ptr(masks_t2), _DT[fp.dtype],
-                  B, N, M, H * W, fp.plane_stride, st_b, st_m, st2_b, st2_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter),
-                  _ptr(ap), _ptr(at), _ptr(inter2), _ptr(at2), _stream(masks_t))
-        return (inter, ap, at), (inter2, at2)
-    _need_gpu(masks_p, masks_t, masks_t2)
-    assert masks_p.dtype == masks_t.dtype == masks_t2.dtype and masks_p.dtype in _DT
+def iou_counts_dual(masks_p, masks_t: torch.Tensor, masks_t2: torch.Tensor, n_valid=None, m_valid=None):
+    """One pass over the proposal planes (tensor or ``FramePlanes``) against TWO template sets (templates + training
+    targets).  -> (inter, area_p, area_t), (inter2, area_t2)."""
+    p, dt, B, N, H, W, sp_b, sp_n, dev, _keep = _proposal_planes(masks_p)
+    frames, sp = _sp(sp_b, sp_n)
+    _need_gpu(masks_t, masks_t2)
+    assert dt == masks_t.dtype == masks_t2.dtype and dt in _DT and (n_valid is not None or not frames)
     assert masks_t.shape == masks_t2.shape
-    masks_p, sp_b, sp_n = _planes(masks_p)
     masks_t, st_b, st_m = _planes(masks_t)
     masks_t2, st2_b, st2_m = _planes(masks_t2)
-    B, N, H, W = masks_p.shape
     M = masks_t.shape[1]
-    dev = masks_p.device
-    i32 = dict(dtype=torch.int32, device=dev)
-    inter, inter2 = torch.empty((B, M, N), **i32), torch.empty((B, M, N), **i32)
-    ap, at, at2 = torch.empty((B, N), **i32), torch.empty((B, M), **i32), torch.empty((B, M), **i32)
-    _lib.call("dmm_iou_counts_dual", dev, _ptr(masks_p), _ptr(masks_t), _ptr(masks_t2), _DT[masks_p.dtype], B, N, M, H * W,
-              sp_b, sp_n, st_b, st_m, st2_b, st2_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at),
-              _ptr(inter2), _ptr(at2), _stream(masks_p))
+    inter, ap, at, inter2, at2 = _count_tables(B, N, M, dev, dual=True)
+    _lib.call("dmm_iou_counts_dual_frames" if frames else "dmm_iou_counts_dual", dev, p, _ptr(masks_t), _ptr(masks_t2),
+              _DT[dt], B, N, M, H * W, *sp, st_b, st_m, st2_b, st2_m, _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap),
+              _ptr(at), _ptr(inter2), _ptr(at2), _stream(masks_t))
     return (inter, ap, at), (inter2, at2)
 
 
@@ -288,6 +306,17 @@ def cosine_features(feat_t: torch.Tensor, feat_p: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _solver_out(B, N, M, dev, per_frame: str):
+    """The result dict of the solver wrappers: sim [B,M,N], R and Rb [B,M,Pp], match_score and det_score [B,M] fp32, and
+    the int32 [B] tensor named ``per_frame`` (iters / status)."""
+    Pp = padded_width(N, M)
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = dict(sim=torch.empty((B, M, N), **f32), R=torch.empty((B, M, Pp), **f32), Rb=torch.empty((B, M, Pp), **f32),
+               match_score=torch.empty((B, M), **f32), det_score=torch.empty((B, M), **f32))
+    out[per_frame] = torch.empty((B,), dtype=torch.int32, device=dev)
+    return out
+
+
 def relax_match(cos, inter, area_p, area_t, score_p, *, score_weight, max_iter, proj_iter, lr, is_test,
                 n_valid=None, m_valid=None, want_x=False, state="f32"):
     """Similarity mix + relaxed assignment + scores for B frames.  cos [B,M,N] = feature_sim.
@@ -299,12 +328,9 @@ def relax_match(cos, inter, area_p, area_t, score_p, *, score_weight, max_iter, 
     B, M, N = cos.shape
     Pp = padded_width(N, M)
     dev = cos.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = dict(sim=torch.empty((B, M, N), **f32), R=torch.empty((B, M, Pp), **f32), Rb=torch.empty((B, M, Pp), **f32),
-               match_score=torch.empty((B, M), **f32), det_score=torch.empty((B, M), **f32),
-               iters=torch.empty((B,), dtype=torch.int32, device=dev),
-               X=torch.empty((B, M, Pp), **f32) if want_x else None)
-    cos, score_p = cos.contiguous().float(), score_p.contiguous().float()
+    out = _solver_out(B, N, M, dev, "iters")
+    out["X"] = torch.empty((B, M, Pp), dtype=torch.float32, device=dev) if want_x else None
+    cos, score_p = _cf(cos), _cf(score_p)
     assert state in ("f32", "f16")
     args = (_ptr(cos), _ptr(inter), _ptr(area_p), _ptr(area_t), _ptr(score_p), B, N, M, _ptr(n_valid), _ptr(m_valid),
             float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(out["sim"]),
@@ -326,8 +352,7 @@ def relax_match_bwd(sim, score_p, dRb, d_match_score, d_det_score, *, max_iter, 
     sim = sim.contiguous().float()
     B, M, N = sim.shape
     dev = sim.device
-    cf = lambda t: None if t is None else t.contiguous().float()
-    dRb, d_match_score, d_det_score, score_p = cf(dRb), cf(d_match_score), cf(d_det_score), cf(score_p)
+    dRb, d_match_score, d_det_score, score_p = _cf(dRb), _cf(d_match_score), _cf(d_det_score), _cf(score_p)
     L = _lib.load()
     nbytes = int(L.dmm_relax_bwd_workspace_bytes(B, N, M, int(max_iter), int(proj_iter)))
     ws = torch.empty((max(nbytes, 8),), dtype=torch.uint8, device=dev)
@@ -343,10 +368,9 @@ def feature_sim_bwd(dsim, cos, gt, d_loss, score_weight, feat_t, feat_p, featn_t
     """-> (g_feat_t [B,M,D], g_feat_p [B,N,D]): backward of cosine + (1 - w) mix + matching-loss mse in one launch
     (``dmm_feature_sim_bwd_f32``).  gt / d_loss None = no matching loss."""
     _need_gpu(dsim, feat_t, feat_p)
-    cf = lambda t: None if t is None else t.contiguous().float()
-    dsim, cos, gt, d_loss = cf(dsim), cf(cos), cf(gt), cf(d_loss)
-    feat_t, feat_p, featn_t, featn_p = cf(feat_t), cf(feat_p), cf(featn_t), cf(featn_p)
-    norm_t, norm_p = cf(norm_t), cf(norm_p)
+    dsim, cos, gt, d_loss = _cf(dsim), _cf(cos), _cf(gt), _cf(d_loss)
+    feat_t, feat_p, featn_t, featn_p = _cf(feat_t), _cf(feat_p), _cf(featn_t), _cf(featn_p)
+    norm_t, norm_p = _cf(norm_t), _cf(norm_p)
     B, M, N = dsim.shape
     D = feat_p.shape[-1]
     g_t, g_p = torch.empty_like(feat_t), torch.empty_like(feat_p)
@@ -487,13 +511,9 @@ def hungarian_match(cos, inter, area_p, area_t, score_p, *, score_weight, is_tes
     while a stream capture is in progress).  M <= 32 and Pp <= 256 only (DmmError otherwise)."""
     _need_gpu(cos, inter)
     B, M, N = cos.shape
-    Pp = padded_width(N, M)
     dev = cos.device
-    f32 = dict(dtype=torch.float32, device=dev)
-    out = dict(sim=torch.empty((B, M, N), **f32), R=torch.empty((B, M, Pp), **f32), Rb=torch.empty((B, M, Pp), **f32),
-               match_score=torch.empty((B, M), **f32), det_score=torch.empty((B, M), **f32),
-               status=torch.empty((B,), dtype=torch.int32, device=dev))
-    cos, score_p = cos.contiguous().float(), score_p.contiguous().float()
+    out = _solver_out(B, N, M, dev, "status")
+    cos, score_p = _cf(cos), _cf(score_p)
     _lib.call("dmm_hungarian_match_f32", dev, _ptr(cos), _ptr(inter), _ptr(area_p), _ptr(area_t), _ptr(score_p), B, N, M,
               _ptr(n_valid), _ptr(m_valid), float(score_weight), int(is_test), _ptr(out["sim"]), _ptr(out["R"]),
               _ptr(out["Rb"]), _ptr(out["match_score"]), _ptr(out["det_score"]), _ptr(out["status"]), _stream(cos))
@@ -502,76 +522,51 @@ def hungarian_match(cos, inter, area_p, area_t, score_p, *, score_weight, is_tes
     return out
 
 
-def mask_mix(Rb: torch.Tensor, masks_p: torch.Tensor, n_valid=None, m_valid=None, out_dtype=None,
-             shared: bool = False) -> torch.Tensor:
-    """full_outmask [B,M,H,W] = Rb [B,M,Pp] @ masks_p [B,N,H*W] (zero planes for the padded columns).
+def mask_mix(Rb: torch.Tensor, masks_p, n_valid=None, m_valid=None, out_dtype=None, shared: bool = False) -> torch.Tensor:
+    """full_outmask [B,M,H,W] = Rb [B,M,Pp] @ masks_p [B,N,H*W] (zero planes for the padded columns); masks_p: tensor or
+    ``FramePlanes`` (fp32 output only; ``n_valid`` defaults to the frames' own counts).
     ``shared``: the rows of Rb share planes (train mode keeps every R > 0.01): every plane of the union of the rows'
     supports is streamed once (``dmm_mask_mix_shared_*``); same result bit for bit."""
-    if isinstance(masks_p, FramePlanes):
-        fp = masks_p
-        _need_gpu(Rb)
-        B, N, H, W = fp.B, fp.N, fp.H, fp.W
-        M, Pp = Rb.shape[1], Rb.shape[2]
-        Rb = Rb.contiguous().float()
-        if n_valid is None:                          # frames are ragged by construction: never read past a short one
-            n_valid = fp.n_valid()
-        if out_dtype not in (None, torch.float32):
-            raise ValueError("mask_mix on per-frame plane tables writes fp32 (dmm_mask_mix_frames)")
-        out = torch.empty((B, M, H, W), dtype=torch.float32, device=Rb.device)
-        _lib.call("dmm_mask_mix_shared_frames" if shared else "dmm_mask_mix_frames", Rb.device, _ptr(Rb), _ptr(fp.table),
-                  _DT[fp.dtype], B, N, M, Pp, H * W, fp.plane_stride, _ptr(n_valid), _ptr(m_valid), _ptr(out), M * H * W,
-                  H * W, _stream(Rb))
-        return out
-    _need_gpu(Rb, masks_p)
-    masks_p, sp_b, sp_n = _planes(masks_p)
-    B, N, H, W = masks_p.shape
+    p, dt, B, N, H, W, sp_b, sp_n, _dev, _keep = _proposal_planes(masks_p)
+    frames, sp = _sp(sp_b, sp_n)
+    _need_gpu(Rb)
     M, Pp = Rb.shape[1], Rb.shape[2]
-    Rb = Rb.contiguous().float()
+    Rb = _cf(Rb)
     out_dtype = out_dtype or torch.float32
+    if frames:
+        if n_valid is None:                          # frames are ragged by construction: never read past a short one
+            n_valid = masks_p.n_valid()
+        if out_dtype != torch.float32:
+            raise ValueError("mask_mix on per-frame plane tables writes fp32 (dmm_mask_mix_frames)")
     out = torch.empty((B, M, H, W), dtype=out_dtype, device=Rb.device)
-    _lib.call("dmm_mask_mix_shared_to" if shared else "dmm_mask_mix_to", Rb.device, _ptr(Rb), _ptr(masks_p),
-              _DT[masks_p.dtype], B, N, M, Pp, H * W, sp_b, sp_n, _ptr(n_valid), _ptr(m_valid), _ptr(out), _DT[out_dtype],
-              M * H * W, H * W, _stream(Rb))
+    _lib.call(("dmm_mask_mix_shared" if shared else "dmm_mask_mix") + ("_frames" if frames else "_to"), Rb.device, _ptr(Rb),
+              p, _DT[dt], B, N, M, Pp, H * W, *sp, _ptr(n_valid), _ptr(m_valid), _ptr(out),
+              *(() if frames else (_DT[out_dtype],)), M * H * W, H * W, _stream(Rb))
     return out
 
 
-def mask_mix_bwd(Rb: torch.Tensor, masks_p: torch.Tensor, dout: torch.Tensor, n_valid=None, m_valid=None, det=None):
-    """dRb [B,M,Pp] = dout [B,M,H,W] . masks_p [B,N,H,W] on the support of Rb (zeros elsewhere).  ``det``: the deterministic
-    entry (None: the mode as it resolves now; autograd callers pass the decision of their forward)."""
+def mask_mix_bwd(Rb: torch.Tensor, masks_p, dout: torch.Tensor, n_valid=None, m_valid=None, det=None):
+    """dRb [B,M,Pp] = dout [B,M,H,W] . masks_p [B,N,H,W] on the support of Rb (zeros elsewhere); masks_p: tensor or
+    ``FramePlanes``.  ``det``: the deterministic entry (None: the mode as it resolves now; autograd callers pass the decision
+    of their forward)."""
     if det is None:
         det = is_deterministic()
-    if isinstance(masks_p, FramePlanes):
-        fp = masks_p
-        _need_gpu(Rb, dout)
-        B, N, H, W = fp.B, fp.N, fp.H, fp.W
-        M, Pp = Rb.shape[1], Rb.shape[2]
-        Rb = Rb.contiguous().float()
-        if n_valid is None:
-            n_valid = fp.n_valid()
-        dout = dout.contiguous().float().view(B, M, H * W)
-        dRb = torch.empty((B, M, Pp), dtype=torch.float32, device=Rb.device)
-        args = (_ptr(Rb), _ptr(fp.table), _DT[fp.dtype], _ptr(dout), B, N, M, Pp, H * W, fp.plane_stride, _ptr(n_valid),
-                _ptr(m_valid), _ptr(dRb))
-        if det:
-            ws = _det_mix_ws(B, N, M, Pp, H * W, Rb.device)
-            _lib.call("dmm_mask_mix_bwd_frames_det", Rb.device, *args, _ptr(ws), ws.numel(), _stream(Rb))
-        else:
-            _lib.call("dmm_mask_mix_bwd_frames", Rb.device, *args, _stream(Rb))
-        return dRb
-    _need_gpu(Rb, masks_p, dout)
-    masks_p, sp_b, sp_n = _planes(masks_p)
-    B, N, H, W = masks_p.shape
+    p, dt, B, N, H, W, sp_b, sp_n, _dev, _keep = _proposal_planes(masks_p)
+    frames, sp = _sp(sp_b, sp_n)
+    _need_gpu(Rb, dout)
     M, Pp = Rb.shape[1], Rb.shape[2]
-    Rb = Rb.contiguous().float()
-    dout = dout.contiguous().float().view(B, M, H * W)
+    Rb = _cf(Rb)
+    if frames and n_valid is None:
+        n_valid = masks_p.n_valid()
+    dout = _cf(dout).view(B, M, H * W)
     dRb = torch.empty((B, M, Pp), dtype=torch.float32, device=Rb.device)
-    args = (_ptr(Rb), _ptr(masks_p), _DT[masks_p.dtype], _ptr(dout), B, N, M, Pp, H * W, sp_b, sp_n, _ptr(n_valid),
-            _ptr(m_valid), _ptr(dRb))
+    entry = "dmm_mask_mix_bwd_frames" if frames else "dmm_mask_mix_bwd"
+    args = (_ptr(Rb), p, _DT[dt], _ptr(dout), B, N, M, Pp, H * W, *sp, _ptr(n_valid), _ptr(m_valid), _ptr(dRb))
     if det:
         ws = _det_mix_ws(B, N, M, Pp, H * W, Rb.device)
-        _lib.call("dmm_mask_mix_bwd_det", Rb.device, *args, _ptr(ws), ws.numel(), _stream(Rb))
+        _lib.call(entry + "_det", Rb.device, *args, _ptr(ws), ws.numel(), _stream(Rb))
     else:
-        _lib.call("dmm_mask_mix_bwd", Rb.device, *args, _stream(Rb))
+        _lib.call(entry, Rb.device, *args, _stream(Rb))
     return dRb
 
 
@@ -586,6 +581,42 @@ _WS_STATE = {}                       # (device, stream) -> ((B, N, M, D), ctypes
 # HIP stream capture is process-global by default: a second host thread that touches the runtime while one captures
 # aborts the process.  Captures are serialised and run in thread-local capture mode (nn.DataParallel-style callers).
 _CAPTURE_LOCK = threading.Lock()
+_WS_NEED = {}                        # (B, N, M, D) [+ solver setting] -> workspace bytes (a C call saved per layer call)
+
+
+def _need_cached(key, size_fn, *args) -> int:
+    """``size_fn(*args)`` bytes, asked once per ``key`` (the host-bound one-frame and training calls)."""
+    need = _WS_NEED.get(key)
+    if need is None:
+        need = _WS_NEED[key] = int(size_fn(*args))
+    return need
+
+
+def _cached_ws(key, need, dev):
+    """The workspace cached under ``key`` = (device index, stream[, tag]), at least ``need`` bytes: grown, never shrunk.
+    A new buffer holds nothing the library knows about: the note kept for the old one goes with it."""
+    ws = _WORKSPACES.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _WORKSPACES[key] = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
+        _WS_STATE.pop(key, None)
+    return ws
+
+
+def _forward_ws(dev, stream, shape, need):
+    """``dmm_match_forward_ws``'s workspace of (device, stream) and the library's note about what the previous call left in
+    THIS workspace, ``need`` bytes for tables of ``shape`` = (B, N, M, D) -> (workspace, byref(note) | None).  The note only
+    holds for the same table layout, so another shape starts from "unknown".  A call recorded into a graph is replayed
+    behind our back, on this workspace: a capturing stream ends note keeping for its workspace for good."""
+    key = (dev.index, stream)
+    ws = _cached_ws(key, need, dev)
+    if torch.cuda.is_current_stream_capturing() or _WS_STATE.get(key) == "captured":
+        _WS_STATE[key] = "captured"
+        return ws, None
+    noted, note = _WS_STATE.get(key, (None, None))
+    if noted != shape:
+        note = ctypes.c_int(0)
+        _WS_STATE[key] = (shape, note)
+    return ws, ctypes.byref(note)
 
 
 def match_forward(masks_p, masks_t, feat_p, feat_t, score_p, *, score_weight, max_iter, proj_iter, lr, is_test,
@@ -602,27 +633,10 @@ def match_forward(masks_p, masks_t, feat_p, feat_t, score_p, *, score_weight, ma
     masks_t, st_b, st_m = _planes(masks_t)
     B, N, H, W = masks_p.shape
     M, D = masks_t.shape[1], feat_p.shape[-1]
-    feat_p, feat_t, score_p = feat_p.contiguous().float(), feat_t.contiguous().float(), score_p.contiguous().float()
+    feat_p, feat_t, score_p = _cf(feat_p), _cf(feat_t), _cf(score_p)
     dev = masks_p.device
-    L = _lib.load()
     stream = _stream(masks_p)
-    need = int(L.dmm_workspace_bytes(B, N, M, D))
-    key = (dev.index, stream)
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACES[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _WS_STATE.pop(key, None)
-    # dmm_match_forward_ws: the library's note about what the previous call left in THIS workspace; it only holds for the
-    # same table layout (B, N, M, D), so another shape starts from "unknown"
-    # (a call recorded into a graph is replayed behind our back, on this workspace: from then on no note is kept for it)
-    note = None
-    if torch.cuda.is_current_stream_capturing() or _WS_STATE.get(key) == "captured":
-        _WS_STATE[key] = "captured"
-    else:
-        shape, note = _WS_STATE.get(key, (None, None))
-        if shape != (B, N, M, D):
-            note = ctypes.c_int(0)
-            _WS_STATE[key] = ((B, N, M, D), note)
+    ws, note = _forward_ws(dev, stream, (B, N, M, D), int(_lib.load().dmm_workspace_bytes(B, N, M, D)))
     f32 = dict(dtype=torch.float32, device=dev)
     full = torch.empty((B, M, H, W), **f32)
     ms, ds = torch.empty((B, M), **f32), torch.empty((B, M), **f32)
@@ -636,7 +650,7 @@ def match_forward(masks_p, masks_t, feat_p, feat_t, score_p, *, score_weight, ma
     _lib.call("dmm_match_forward_ws", dev, _ptr(masks_p), _ptr(masks_t), _DT[masks_p.dtype], _ptr(feat_p), _ptr(feat_t),
               _ptr(score_p), B, N, M, H * W, D, sp_b, sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight),
               int(max_iter), int(proj_iter), float(lr), int(is_test), _ptr(full), _ptr(ms), _ptr(ds), tp("sim"), tp("R"),
-              tp("Rb"), _ptr(iters), _ptr(ws), ws.numel(), None if note is None else ctypes.byref(note), stream)
+              tp("Rb"), _ptr(iters), _ptr(ws), ws.numel(), note, stream)
     if return_tables:
         return full, ms, ds, iters, tables
     return full, ms, ds, iters
@@ -651,59 +665,22 @@ def match_forward_frame(proposed_mask, mask_last, feat_p, feat_t, score_p, *, sc
     _need_gpu(proposed_mask, mask_last, feat_p, feat_t, score_p)
     pm, tm = proposed_mask, mask_last
     assert pm.dtype == tm.dtype and pm.dtype in _DT and pm.dim() == 3 and tm.dim() == 3
+    pm, tm = _plane_rows(pm), _plane_rows(tm)
     N, H, W = pm.shape
     M, D = tm.shape[0], feat_p.shape[-1]
-    if N * H * W and not (pm.stride(2) == 1 and pm.stride(1) == W and pm.stride(0) >= H * W):
-        pm = pm.contiguous()
-    if M * H * W and not (tm.stride(2) == 1 and tm.stride(1) == W and tm.stride(0) >= H * W):
-        tm = tm.contiguous()
     feat_p, feat_t, score_p = feat_p.contiguous().float(), feat_t.contiguous().float(), score_p.contiguous().float()
     dev = pm.device
-    L = _lib.load()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    key = (dev.index, stream)
-    ws = _WORKSPACES.get(key)
-    need = _WS_NEED.get((1, N, M, D))
-    if need is None:
-        need = _WS_NEED[(1, N, M, D)] = int(L.dmm_workspace_bytes(1, N, M, D))
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACES[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
-        _WS_STATE.pop(key, None)
-    note = None
-    if torch.cuda.is_current_stream_capturing() or _WS_STATE.get(key) == "captured":
-        _WS_STATE[key] = "captured"
-    else:
-        shape, note = _WS_STATE.get(key, (None, None))
-        if shape != (1, N, M, D):
-            note = ctypes.c_int(0)
-            _WS_STATE[key] = ((1, N, M, D), note)
+    shape = (1, N, M, D)
+    ws, note = _forward_ws(dev, stream, shape, _need_cached(shape, _lib.load().dmm_workspace_bytes, *shape))
     full = torch.empty((M, H, W), dtype=torch.float32, device=dev)
     ms = torch.empty((M,), dtype=torch.float32, device=dev)
     ds = torch.empty((M,), dtype=torch.float32, device=dev)
     _lib.call("dmm_match_forward_ws", dev, pm.data_ptr(), tm.data_ptr(), _DT[pm.dtype], feat_p.data_ptr(),
               feat_t.data_ptr(), score_p.data_ptr(), 1, N, M, H * W, D, N * pm.stride(0) if N else 0, pm.stride(0),
               M * tm.stride(0) if M else 0, tm.stride(0), None, None, score_weight, max_iter, proj_iter, lr, is_test,
-              full.data_ptr(), ms.data_ptr(), ds.data_ptr(), None, None, None, None, ws.data_ptr(), ws.numel(),
-              None if note is None else ctypes.byref(note), stream)
+              full.data_ptr(), ms.data_ptr(), ds.data_ptr(), None, None, None, None, ws.data_ptr(), ws.numel(), note, stream)
     return full, ms, ds
-
-
-_WS_NEED = {}                        # (B, N, M, D) [+ solver setting] -> workspace bytes (a C call saved per layer call)
-
-
-def _cached_ws(key, need, dev):
-    ws = _WORKSPACES.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _WORKSPACES[key] = torch.empty((max(need, 256),), dtype=torch.uint8, device=dev)
-    return ws
-
-
-def _planes3(t: torch.Tensor):
-    """[K,H,W] with contiguous H*W planes -> (tensor, plane stride in elements)."""
-    K, H, W = t.shape
-    if K * H * W and not (t.stride(2) == 1 and t.stride(1) == W and t.stride(0) >= H * W):
-        t = t.contiguous()
-    return t, t.stride(0)
 
 
 def match_train_forward(masks_p, masks_t, targets, feat_p, feat_t, score_p, n_valid, m_valid, *, score_weight, max_iter,
@@ -718,25 +695,8 @@ def match_train_forward(masks_p, masks_t, targets, feat_p, feat_t, score_p, n_va
     flat fp32 block cos | sim | Rb | gt (| the solver's tape, 256-byte aligned) that ``match_train_backward`` reads and
     ``taped`` = whether the forward's solver kernel kept its tape there (tables of <= 64 solver columns: the backward then
     does not re-run the solver).  ``want_tape=False`` (no gradient will be asked for): the untaped solver kernels."""
-    fp = masks_p if isinstance(masks_p, FramePlanes) else None
-    if one_frame:
-        masks_p, sp_n = _planes3(masks_p)
-        B, (N, H, W) = 1, masks_p.shape
-        sp_b = N * sp_n
-        dt, p_ptr, dev = masks_p.dtype, masks_p.data_ptr(), masks_p.device
-        masks_t, st_m = _planes3(masks_t)
-        M = masks_t.shape[0]
-        st_b = M * st_m
-    else:
-        if fp is not None:
-            B, N, H, W, dt = fp.B, fp.N, fp.H, fp.W, fp.dtype
-            sp_b, sp_n, p_ptr, dev = _lib.FRAME_TABLE, fp.plane_stride, fp.table.data_ptr(), fp.device
-        else:
-            masks_p, sp_b, sp_n = _planes(masks_p)
-            B, N, H, W = masks_p.shape
-            dt, p_ptr, dev = masks_p.dtype, masks_p.data_ptr(), masks_p.device
-        masks_t, st_b, st_m = _planes(masks_t)
-        M = masks_t.shape[1]
+    p_ptr, dt, B, N, H, W, sp_b, sp_n, dev, _keep = _proposal_planes(masks_p, one_frame)
+    masks_t, M, st_b, st_m = _batch_planes(masks_t, one_frame)
     D = feat_p.shape[-1]
     Pp = padded_width(N, M)
     if M > _lib.MAX_TEMPLATES or Pp > _lib.MAX_PROPOSALS or B > 65535 or N == 0 or M == 0 or B == 0 or dt not in _DT \
@@ -747,17 +707,11 @@ def match_train_forward(masks_p, masks_t, targets, feat_p, feat_t, score_p, n_va
     if targets is not None:
         if targets.dtype != dt:
             targets = targets.to(dt)
-        if one_frame:
-            targets, sg_m = _planes3(targets)
-            sg_b = M * sg_m
-        else:
-            targets, sg_b, sg_m = _planes(targets)
+        targets, _, sg_b, sg_m = _batch_planes(targets, one_frame)
         g_ptr = targets.data_ptr()
     L = _lib.load()
     stream = torch.cuda.current_stream(dev).cuda_stream
-    need = _WS_NEED.get(("tf", B, N, M, D))
-    if need is None:
-        need = _WS_NEED[("tf", B, N, M, D)] = int(L.dmm_match_train_forward_workspace_bytes(B, N, M, D))
+    need = _need_cached(("tf", B, N, M, D), L.dmm_match_train_forward_workspace_bytes, B, N, M, D)
     ws = _cached_ws((dev.index, stream, "train_fwd"), need, dev)
     f32 = dict(dtype=torch.float32, device=dev)
     lead = () if one_frame else (B,)
@@ -808,19 +762,7 @@ def match_train_backward(masks_p, feat_p, feat_t, score_p, saved, has_loss, d_fu
     feature-similarity backward.  ``saved`` is the forward's block; d_* may be None.  ``one_frame``: as in the forward.
     ``iters`` / ``taped``: the forward's iteration counts and its ``taped`` flag -- with them the solver's backward walks the
     tape inside ``saved`` instead of re-running the solver."""
-    fp = masks_p if isinstance(masks_p, FramePlanes) else None
-    if one_frame:
-        masks_p, sp_n = _planes3(masks_p)
-        B, (N, H, W) = 1, masks_p.shape
-        sp_b = N * sp_n
-        dt, p_ptr, dev = masks_p.dtype, masks_p.data_ptr(), masks_p.device
-    elif fp is not None:
-        B, N, H, W, dt = fp.B, fp.N, fp.H, fp.W, fp.dtype
-        sp_b, sp_n, p_ptr, dev = _lib.FRAME_TABLE, fp.plane_stride, fp.table.data_ptr(), fp.device
-    else:
-        masks_p, sp_b, sp_n = _planes(masks_p)
-        B, N, H, W = masks_p.shape
-        dt, p_ptr, dev = masks_p.dtype, masks_p.data_ptr(), masks_p.device
+    p_ptr, dt, B, N, H, W, sp_b, sp_n, dev, _keep = _proposal_planes(masks_p, one_frame)
     D = feat_p.shape[-1]
     Pp = padded_width(N, M)
     n_cs, n_rb = B * M * N, B * M * Pp
@@ -831,13 +773,10 @@ def match_train_backward(masks_p, feat_p, feat_t, score_p, saved, has_loss, d_fu
     if det:                               # (its slab depends on the dispatch options too: sized per call, a host function)
         need = int(L.dmm_match_train_backward_det_workspace_bytes(B, N, M, D, max_iter, proj_iter, H * W))
     else:
-        k = ("tb", B, N, M, D, max_iter, proj_iter)
-        need = _WS_NEED.get(k)
-        if need is None:
-            need = _WS_NEED[k] = int(L.dmm_match_train_backward_workspace_bytes(B, N, M, D, max_iter, proj_iter))
+        need = _need_cached(("tb", B, N, M, D, max_iter, proj_iter), L.dmm_match_train_backward_workspace_bytes, B, N, M, D,
+                            max_iter, proj_iter)
     ws = _cached_ws((dev.index, stream, "train_bwd"), need, dev)
-    cf = lambda t: None if t is None else t.contiguous().float()
-    d_full, d_ms, d_ds, d_loss = cf(d_full), cf(d_ms), cf(d_ds), cf(d_loss)
+    d_full, d_ms, d_ds, d_loss = _cf(d_full), _cf(d_ms), _cf(d_ds), _cf(d_loss)
     use_loss = has_loss and d_loss is not None
     g_t, g_p = torch.empty_like(feat_t), torch.empty_like(feat_p)
     sp = saved.data_ptr()
@@ -871,10 +810,7 @@ def match_forward_packed(masks_p, packed_p, masks_t, feat_p, feat_t, score_p, n_
     L = _lib.load()
     need = int(L.dmm_workspace_bytes_packed(B, N, M, D, H * W))
     if workspace is None:
-        key = (dev.index, _stream(masks_p), "packed")
-        workspace = _WORKSPACES.get(key)
-        if workspace is None or workspace.numel() < need:
-            workspace = _WORKSPACES[key] = torch.empty((need,), dtype=torch.uint8, device=dev)
+        workspace = _cached_ws((dev.index, _stream(masks_p), "packed"), need, dev)
     assert workspace.numel() >= need
     if out is None:
         f32 = dict(dtype=torch.float32, device=dev)
@@ -928,6 +864,11 @@ def match_solve_packed_hun(packed_p, packed_t, feat_p, feat_t, score_p, n_valid,
               _ptr(Rb), _ptr(ms), _ptr(ds), None, None, _ptr(status), _ptr(workspace), workspace.numel(),
               _stream(packed_p))
     return out
+
+
+# what one ``ForwardPlan.run`` hands to its launches: the checked inputs, the planes' dtype code and strides, and
+# cfg = (score_weight, max_iter, proj_iter, lr, is_test) as the C ABI takes them
+_PlanRun = namedtuple("_PlanRun", "masks_p masks_t feat_p feat_t score_p dt sp_b sp_n st_b st_m n_valid m_valid cfg")
 
 
 class ForwardPlan:
@@ -1057,38 +998,55 @@ class ForwardPlan:
                 else "HIP graph replay (feature similarity + IoU counts [one launch at <= 8 dense frames] -> solver -> mix, one chain)"
         return "single stream"
 
-    def _launch_forked(self, masks_p, masks_t, feat_p, feat_t, score_p, dt, strides, n_valid, m_valid, cfg):
+    def _launch_forked(self, r):
         """Granular launches, the form that is captured into the HIP graph (``graph_fork``: feature branch on the side
         stream, fork / join by stream waits)."""
-        B, N, M, D, Pp, HW = self.B, self.N, self.M, self.D, self.Pp, self.H * self.W
-        sp_b, sp_n, st_b, st_m = strides
-        score_weight, max_iter, proj_iter, lr, is_test = cfg
         main = torch.cuda.current_stream(self.device)
+        ms = main.cuda_stream
         if not self.graph_fork:
             # one chain: the fused C call (its feature-similarity launch also clears the count tables: no memset node)
-            _lib.call("dmm_match_forward_ws", None,
-                      _ptr(masks_p), _ptr(masks_t), dt, _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, HW, D, sp_b,
-                      sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
-                      float(lr), int(is_test), _ptr(self.full_outmask), _ptr(self.match_score), _ptr(self.det_score),
-                      _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace), self.ws_bytes,
-                      ctypes.byref(self._ws_state), main.cuda_stream)
+            self._fused(r, None, ms)
             return
         side = self.side
-        inter, ap, at = self._tables(0)
-        if self.graph_fork:
-            side.wait_stream(main)
-        ss, ms = side.cuda_stream, main.cuda_stream
-        self._feature_sim(feat_p, feat_t, n_valid, m_valid, ss)
-        _lib.call("dmm_iou_counts", None, _ptr(masks_p), _ptr(masks_t), dt, B, N, M, HW, sp_b, sp_n, st_b, st_m,
-                  _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), ms)
-        if self.graph_fork:
-            main.wait_stream(side)
-        _lib.call(self.solver_entry, None, _ptr(self.cos), _ptr(inter), _ptr(ap), _ptr(at), _ptr(score_p), B, N, M,
-                  _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test),
-                  _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.match_score), _ptr(self.det_score),
-                  _ptr(self.iters), None, ms)
-        _lib.call("dmm_mask_mix_to", None, _ptr(self.Rb), _ptr(masks_p), dt, B, N, M, Pp, HW, sp_b, sp_n, _ptr(n_valid),
-                  _ptr(m_valid), _ptr(self.full_outmask), _DT[self.out_dtype], self.so_b, self.so_m, ms)
+        side.wait_stream(main)
+        self._feature_sim(r.feat_p, r.feat_t, r.n_valid, r.m_valid, side.cuda_stream)
+        self._counts(r, 0, self.B, ms)
+        main.wait_stream(side)
+        self._solve(r, 0, self.B, ms)
+        self._mix(r, 0, self.B, ms)
+
+    # ---- the launches: one method each, on the frames [b, e) of the batch (the whole batch is (0, B): every offset zero) ----
+    @staticmethod
+    def _at(t, b, per_frame):
+        """Address of frame ``b`` in ``t``, ``per_frame`` elements a frame (None stays None)."""
+        return None if t is None else t.data_ptr() + t.element_size() * b * per_frame
+
+    def _counts(self, r, b, e, stream):
+        inter, ap, at = self._tables(b, e)
+        _lib.call("dmm_iou_counts", None, self._at(r.masks_p, b, r.sp_b), self._at(r.masks_t, b, r.st_b), r.dt, e - b, self.N,
+                  self.M, self.H * self.W, r.sp_b, r.sp_n, r.st_b, r.st_m, self._at(r.n_valid, b, 1), self._at(r.m_valid, b, 1),
+                  _ptr(inter), _ptr(ap), _ptr(at), stream)
+
+    def _solve(self, r, b, e, stream):
+        N, M, Pp, at_ = self.N, self.M, self.Pp, self._at
+        inter, ap, at = self._tables(b, e)
+        _lib.call(self.solver_entry, None, at_(self.cos, b, M * N), _ptr(inter), _ptr(ap), _ptr(at), at_(r.score_p, b, N), e - b,
+                  N, M, at_(r.n_valid, b, 1), at_(r.m_valid, b, 1), *r.cfg, at_(self.sim, b, M * N), at_(self.R, b, M * Pp),
+                  at_(self.Rb, b, M * Pp), at_(self.match_score, b, M), at_(self.det_score, b, M), at_(self.iters, b, 1), None,
+                  stream)
+
+    def _mix(self, r, b, e, stream):
+        _lib.call("dmm_mask_mix_to", None, self._at(self.Rb, b, self.M * self.Pp), self._at(r.masks_p, b, r.sp_b), r.dt, e - b,
+                  self.N, self.M, self.Pp, self.H * self.W, r.sp_b, r.sp_n, self._at(r.n_valid, b, 1), self._at(r.m_valid, b, 1),
+                  self._at(self.full_outmask, b, self.so_b), _DT[self.out_dtype], self.so_b, self.so_m, stream)
+
+    def _fused(self, r, guard, stream):
+        """The whole batch as one ``dmm_match_forward_ws`` call on the plan's workspace (``guard``: the device to call under)."""
+        _lib.call("dmm_match_forward_ws", guard, _ptr(r.masks_p), _ptr(r.masks_t), r.dt, _ptr(r.feat_p), _ptr(r.feat_t),
+                  _ptr(r.score_p), self.B, self.N, self.M, self.H * self.W, self.D, r.sp_b, r.sp_n, r.st_b, r.st_m,
+                  _ptr(r.n_valid), _ptr(r.m_valid), *r.cfg, _ptr(self.full_outmask), _ptr(self.match_score),
+                  _ptr(self.det_score), _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace),
+                  self.ws_bytes, ctypes.byref(self._ws_state), stream)
 
     def _mark(self, name, stream, begin):
         """HIP event on ``stream`` before / after a kernel launch when bench.py asked for kernel timing."""
@@ -1114,10 +1072,10 @@ class ForwardPlan:
         _lib.call("dmm_cosine_f32", None, _ptr(self.tn), _ptr(self.pn), B, N, M, D, _ptr(n_valid), _ptr(m_valid),
                   _ptr(self.cos), stream)
 
-    def _tables(self, h):
-        (b, e) = self.halves[h]
+    def _tables(self, b, e):
+        """inter | area_p | area_t of the slice [b, e) (one of ``self.halves``)."""
         nb, M, N = e - b, self.M, self.N
-        c = self.counts[h]
+        c = self.counts[self.halves.index((b, e))]
         return c[:nb * M * N], c[nb * M * N:nb * (M * N + N)], c[nb * (M * N + N):]
 
     def run(self, masks_p, masks_t, feat_p, feat_t, score_p, *, score_weight=0.3, max_iter=20, proj_iter=5, lr=0.1,
@@ -1125,15 +1083,14 @@ class ForwardPlan:
         _need_gpu(masks_p, masks_t, feat_p, feat_t, score_p)
         masks_p, sp_b, sp_n = _planes(masks_p)
         masks_t, st_b, st_m = _planes(masks_t)
-        B, N, M, H, W, D, Pp = self.B, self.N, self.M, self.H, self.W, self.D, self.Pp
-        HW = H * W
+        B, N, M, H, W = self.B, self.N, self.M, self.H, self.W
         assert masks_p.shape == (B, N, H, W) and masks_t.shape == (B, M, H, W)
         assert masks_p.dtype == self.mask_dtype and masks_t.dtype == self.mask_dtype
         assert feat_p.is_contiguous() and feat_t.is_contiguous() and score_p.is_contiguous()
         assert feat_p.dtype == torch.float32 and feat_t.dtype == torch.float32 and score_p.dtype == torch.float32
-        dt = _DT[self.mask_dtype]
+        cfg = (float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test))
+        r = _PlanRun(masks_p, masks_t, feat_p, feat_t, score_p, _DT[self.mask_dtype], sp_b, sp_n, st_b, st_m, n_valid, m_valid, cfg)
         if self.graph_mode and not torch.cuda.is_current_stream_capturing():
-            cfg = (float(score_weight), int(max_iter), int(proj_iter), float(lr), int(is_test))
             key = (masks_p.data_ptr(), masks_t.data_ptr(), feat_p.data_ptr(), feat_t.data_ptr(), score_p.data_ptr(),
                    sp_b, sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), cfg)
             hit = self._graphs.get(key)
@@ -1149,8 +1106,7 @@ class ForwardPlan:
                 with _CAPTURE_LOCK, torch.cuda.device(self.device):
                     g = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        self._launch_forked(masks_p, masks_t, feat_p, feat_t, score_p, dt, (sp_b, sp_n, st_b, st_m),
-                                            n_valid, m_valid, cfg)
+                        self._launch_forked(r)
                 ws_out = self._ws_state.value                       # what a replay leaves (nothing ran during the capture)
                 self._ws_state.value = ws_in
                 # the graph holds raw addresses: keep the tensors alive with it
@@ -1163,35 +1119,21 @@ class ForwardPlan:
             with _lib.device_guard(self.device):
                 main = torch.cuda.current_stream(self.device)
                 ms = main.cuda_stream
-                inter, ap, at = self._tables(0)
                 self._mark("cost", main, True)
-                _lib.call("dmm_iou_counts", None, _ptr(masks_p), _ptr(masks_t), dt, B, N, M, HW, sp_b, sp_n, st_b, st_m,
-                          _ptr(n_valid), _ptr(m_valid), _ptr(inter), _ptr(ap), _ptr(at), ms)
+                self._counts(r, 0, B, ms)
                 self._mark("cost", main, False)
                 self._feature_sim(feat_p, feat_t, n_valid, m_valid, ms)
                 self._mark("solver", main, True)
-                _lib.call(self.solver_entry, None, _ptr(self.cos), _ptr(inter), _ptr(ap), _ptr(at), _ptr(score_p), B, N,
-                          M, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter), float(lr),
-                          int(is_test), _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.match_score),
-                          _ptr(self.det_score), _ptr(self.iters), None, ms)
+                self._solve(r, 0, B, ms)
                 self._mark("solver", main, False)
                 self._mark("mix", main, True)
-                _lib.call("dmm_mask_mix_to", None, _ptr(self.Rb), _ptr(masks_p), dt, B, N, M, Pp, HW, sp_b, sp_n,
-                          _ptr(n_valid), _ptr(m_valid), _ptr(self.full_outmask), _DT[self.out_dtype], self.so_b,
-                          self.so_m, ms)
+                self._mix(r, 0, B, ms)
                 self._mark("mix", main, False)
             return self.full_outmask, self.match_score, self.det_score
         if not self.pipeline:
-            _lib.call("dmm_match_forward_ws", self.device,
-                      _ptr(masks_p), _ptr(masks_t), dt, _ptr(feat_p), _ptr(feat_t), _ptr(score_p), B, N, M, HW, D, sp_b,
-                      sp_n, st_b, st_m, _ptr(n_valid), _ptr(m_valid), float(score_weight), int(max_iter), int(proj_iter),
-                      float(lr), int(is_test), _ptr(self.full_outmask), _ptr(self.match_score), _ptr(self.det_score),
-                      _ptr(self.sim), _ptr(self.R), _ptr(self.Rb), _ptr(self.iters), _ptr(self.workspace), self.ws_bytes,
-                      ctypes.byref(self._ws_state), _stream(masks_p))
+            self._fused(r, self.device, _stream(masks_p))
             return self.full_outmask, self.match_score, self.det_score
 
-        es = masks_p.element_size()
-        nv = lambda t, b: None if t is None else t.data_ptr() + 4 * b
         with _lib.device_guard(self.device):
             main = torch.cuda.current_stream(self.device)
             side = self.side
@@ -1202,32 +1144,19 @@ class ForwardPlan:
             self._feature_sim(feat_p, feat_t, n_valid, m_valid, ss)
             # ---- streaming lane: cost(A), cost(B) ------------------------------------------------------------
             for h, (b, e) in enumerate(self.halves):
-                inter, ap, at = self._tables(h)
                 self._mark("cost", main, True)
-                _lib.call("dmm_iou_counts", None, masks_p.data_ptr() + es * b * sp_b, masks_t.data_ptr() + es * b * st_b,
-                          dt, e - b, N, M, HW, sp_b, sp_n, st_b, st_m, nv(n_valid, b), nv(m_valid, b), _ptr(inter),
-                          _ptr(ap), _ptr(at), ms)
+                self._counts(r, b, e, ms)
                 self._mark("cost", main, False)
                 self.ev_cost[h].record(main)
             # ---- latency lane: solver(h) as soon as cost(h) is done ------------------------------------------
             for h, (b, e) in enumerate(self.halves):
-                inter, ap, at = self._tables(h)
                 side.wait_event(self.ev_cost[h])
-                _lib.call(
-                    self.solver_entry, None, self.cos.data_ptr() + 4 * b * M * N, _ptr(inter), _ptr(ap), _ptr(at),
-                    score_p.data_ptr() + 4 * b * N, e - b, N, M, nv(n_valid, b), nv(m_valid, b), float(score_weight), int(max_iter), int(proj_iter),
-                    float(lr), int(is_test), self.sim.data_ptr() + 4 * b * M * N,
-                    None if self.R is None else self.R.data_ptr() + 4 * b * M * Pp, self.Rb.data_ptr() + 4 * b * M * Pp,
-                    self.match_score.data_ptr() + 4 * b * M, self.det_score.data_ptr() + 4 * b * M,
-                    self.iters.data_ptr() + 4 * b, None, ss)
+                self._solve(r, b, e, ss)
                 self.ev_solved[h].record(side)
             # ---- streaming lane: mix(A) after solver(A), mix(B) after solver(B) ------------------------------
             for h, (b, e) in enumerate(self.halves):
                 main.wait_event(self.ev_solved[h])
                 self._mark("mix", main, True)
-                _lib.call("dmm_mask_mix_to", None, self.Rb.data_ptr() + 4 * b * M * Pp,
-                          masks_p.data_ptr() + es * b * sp_b, dt, e - b, N, M, Pp, HW, sp_b, sp_n, nv(n_valid, b),
-                          nv(m_valid, b), self.full_outmask.data_ptr() + self.full_outmask.element_size() * b * self.so_b,
-                          _DT[self.out_dtype], self.so_b, self.so_m, ms)
+                self._mix(r, b, e, ms)
                 self._mark("mix", main, False)
         return self.full_outmask, self.match_score, self.det_score
