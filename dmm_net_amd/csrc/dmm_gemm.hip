@@ -19,6 +19,7 @@
 // call is stream-ordered and graph-capturable (a shape first seen DURING a capture is never timed).
 #include <hipblaslt/hipblaslt.h>
 
+#include <initializer_list>
 #include <map>
 #include <mutex>
 #include <tuple>
@@ -51,7 +52,14 @@ hipblasLtHandle_t handle_of(int dev) {                                    // und
     g_handles[dev] = h;
     return h;
 }
-std::map<std::tuple<int, int64_t, int, int, int, int>, GemmPlan> g_plans;   // (device, rows, Cin, Cout, relu, residual)
+std::map<std::tuple<int, int64_t, int, int, int, int, int>, GemmPlan> g_plans;   // (device, rows, Cin, Cout, relu, residual, scratch)
+
+void release_plan(GemmPlan &p) {
+    if (p.desc) hipblasLtMatmulDescDestroy(p.desc);
+    for (hipblasLtMatrixLayout_t l : {p.a, p.b, p.c, p.d})
+        if (l) hipblasLtMatrixLayoutDestroy(l);
+    p = GemmPlan();
+}
 
 #define DMM_LT_TRY(expr)                                    \
     do {                                                    \
@@ -148,27 +156,35 @@ extern "C" int dmm_conv1x1_bf16(const void *x, const void *w, const float *bias,
     if (!x || !w || !bias || !y) return DMM_ERR_BAD_ARG;
     int dev = 0;
     DMM_HIP_TRY(hipGetDevice(&dev));
-    dmm::GemmPlan *plan = nullptr;
-    hipblasLtHandle_t handle = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(dmm::g_mu);
-        handle = dmm::handle_of(dev);
-        if (!handle) return DMM_ERR_LAUNCH;
-        auto key = std::make_tuple(dev, rows, cin, cout, relu ? 1 : 0, residual ? 1 : 0);
-        auto it = dmm::g_plans.find(key);
-        if (it == dmm::g_plans.end()) {
-            dmm::GemmPlan p;
-            if (!dmm::build_plan(handle, p, rows, cin, cout, relu != 0, residual != nullptr, workspace ? workspace_bytes : 0))
-                p.ok = false;
-            it = dmm::g_plans.emplace(key, p).first;
+    const size_t avail = workspace ? workspace_bytes : 0;
+    std::lock_guard<std::mutex> lk(dmm::g_mu);
+    hipblasLtHandle_t handle = dmm::handle_of(dev);
+    if (!handle) return DMM_ERR_LAUNCH;
+    // a plan is kept per scratch class (with / without a workspace): what the heuristic offers depends on the limit it was
+    // asked with, and a plan picked with scratch must not answer a call that brings none
+    auto key = std::make_tuple(dev, rows, cin, cout, relu ? 1 : 0, residual ? 1 : 0, avail ? 1 : 0);
+    auto it = dmm::g_plans.find(key);
+    if (it == dmm::g_plans.end()) {
+        dmm::GemmPlan p;
+        if (!dmm::build_plan(handle, p, rows, cin, cout, relu != 0, residual != nullptr, avail)) p.ok = false;
+        it = dmm::g_plans.emplace(key, p).first;
+    }
+    dmm::GemmPlan *plan = &it->second;
+    if (plan->ok && plan->workspace > avail) {
+        // a smaller workspace than the one the plan was picked under: pick again within what this call brings ("kernels
+        // that need one are then not considered"); the smaller plan serves the larger callers too
+        dmm::GemmPlan p;
+        if (!dmm::build_plan(handle, p, rows, cin, cout, relu != 0, residual != nullptr, avail)) p.ok = false;
+        if (p.ok && p.workspace > avail) p.ok = false;          // (a library that ignores the limit: no kernel for this call)
+        if (!p.ok) {
+            dmm::release_plan(p);
+            return DMM_ERR_UNSUPPORTED;                             // the kept plan still serves callers with enough scratch
         }
-        plan = &it->second;
+        dmm::release_plan(*plan);
+        *plan = p;
     }
     if (!plan->ok) return DMM_ERR_UNSUPPORTED;
-    if (plan->workspace > (workspace ? workspace_bytes : 0)) return DMM_ERR_WORKSPACE;
-    // the descriptor carries the bias pointer: set it under the lock-free assumption of one stream per plan user
-    // (pointer attributes are plain fields read at launch time)
-    std::lock_guard<std::mutex> lk(dmm::g_mu);
+    // the descriptor carries the bias pointer (a plain field read at launch time): set per call, under g_mu with the launch
     const void *bp = bias;
     if (hipblasLtMatmulDescSetAttribute(plan->desc, HIPBLASLT_MATMUL_DESC_BIAS_POINTER, &bp, sizeof(bp)) !=
         HIPBLAS_STATUS_SUCCESS)

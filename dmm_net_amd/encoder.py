@@ -467,7 +467,7 @@ class FastEncoder(nn.Module):
       pair of layout transposes + cast / zero helper kernels (112 + 56 of the 349 launches of one ResNet-50 forward at
       8 x 255 x 255, 27 % of its device time; profiles/r02_encoder_kernel_table_nchw_eager.md);
     * the 1x1 convolutions (2/3 of a bottleneck) ARE matrix products of the [B*H*W, Cin] activation matrix: they go to
-      hipBLASLt through ``torch.addmm`` / ``torch._addmm_activation`` with the bias (+ ReLU) in the GEMM epilogue;
+      hipBLASLt through ``dmm_conv1x1_bf16`` with the fp32 bias (+ residual) (+ ReLU) in the GEMM epilogue;
     * what is left after the 3x3 / 7x7 MIOpen convolutions -- bias, residual, ReLU -- is one in-place HIP launch
       (``dmm_bias_act_bf16``) instead of two or three eager ones.
 
@@ -475,7 +475,7 @@ class FastEncoder(nn.Module):
     kernel).  Wrap in ``GraphedEncoder(FastEncoder(enc))`` to replay from one HIP
     graph.  Reference: vision.py:6-38 (body), base.py:35-54 + model_encoder.py:136-146 (heads)."""
 
-    fused_gemm = True          # 1x1 convolutions through dmm_conv1x1_bf16 (False: torch.mm / addmm + the epilogue kernel)
+    fused_gemm = True          # 1x1 convolutions through dmm_conv1x1_bf16 (False: torch.mm + the epilogue kernel)
     # The `sk` / `prop` heads of a level only need that level's body output: they are issued on a SIDE stream as soon as
     # the level is done and run under the deeper levels of the body (at the product's batch sizes every convolution is a
     # 5-30 us launch that fills a fraction of the 256 CUs; the 12 head convolutions are ~30 % of the forward's kernel time
@@ -495,7 +495,7 @@ class FastEncoder(nn.Module):
         assert dtype == torch.bfloat16, "the fused epilogue kernel is bf16"
         self.dtype = dtype
         self.src = enc                       # folded fp32 parameters stay the source of truth (state_dict)
-        self._p = {}                         # id(conv) -> prepared (weight, fp32 bias, bf16 bias)
+        self._p = {}                         # id(conv) -> prepared (weight, fp32 bias, patch-matrix weight or None)
         self._ws = {}                        # scratch of the library GEMMs, one per stream that runs them
         self._side = {}                      # device index -> the heads' side stream
         self._on_side = False                # the call being issued belongs to the heads' stream
@@ -517,7 +517,7 @@ class FastEncoder(nn.Module):
             if m.kernel_size == (1, 1) and m.groups == 1:
                 assert m.padding == (0, 0), "a padded 1x1 convolution is not a plain matrix product"
                 wt = w.reshape(w.shape[0], w.shape[1]).t().contiguous().to(dtype)          # [Cin, Cout]
-                self._p[id(m)] = (wt, b, b.to(dtype))
+                self._p[id(m)] = (wt, b, None)
             else:
                 col = None
                 if self._patch_ok(m):                                  # [(kh, kw, cin), Cout]: rows of the patch matrix
@@ -548,7 +548,7 @@ class FastEncoder(nn.Module):
         """y = act(x @ W^T + b (+ residual)) on the activation matrix, ONE library GEMM with the whole tail in its
         epilogue (``dmm_conv1x1_bf16``: hipBLASLt, residual as the C operand).  stride 2 = a row subsample first."""
         from . import _lib
-        wt, b32, bl = self._p[id(conv)]
+        wt, b32, _ = self._p[id(conv)]
         if conv.stride == (2, 2) and x.is_cuda and x.dtype == torch.bfloat16 and x.is_contiguous(memory_format=torch.channels_last):
             from .train_encoder import _subsample                       # 16 bytes per thread (the strided copy below: 2)
             x = _subsample(x, 2)
@@ -570,15 +570,10 @@ class FastEncoder(nn.Module):
                            allow=(_lib.DMM_ERR_UNSUPPORTED,))           # (no kernel for this shape: the library GEMM below)
             if rc == _lib.DMM_OK:
                 return _from_rows(y, B, H, W)
-        if residual is not None:
-            # (torch.addmm(residual, rows, wt) would first COPY the residual into the output -- a DtoD memcpy per
-            # block, 16 per ResNet-50 forward -- so the residual rides in the epilogue launch instead)
-            return _bias_act_(_from_rows(torch.mm(rows, wt), B, H, W), b32, residual, relu)
-        if relu:
-            y = torch._addmm_activation(bl, rows, wt, use_gelu=False)  # bias + ReLU in the GEMM epilogue
-        else:
-            y = torch.addmm(bl, rows, wt)
-        return _from_rows(y, B, H, W)
+        # (torch.addmm(residual, rows, wt) would first COPY the residual into the output -- a DtoD memcpy per block, 16 per
+        # ResNet-50 forward -- and torch.addmm(bias, ...) needs the bias ROUNDED to bf16, which the contract does not allow
+        # (fp32 bias: 2^-9 |bias| would enter every output) -- so bias, residual and ReLU ride in the epilogue launch)
+        return _bias_act_(_from_rows(torch.mm(rows, wt), B, H, W), b32, residual, relu)
 
     # Opt-in (FastEncoder.patch_mode = "auto", set in code): 3x3 convolutions on SMALL feature maps as patch matrix + library GEMM.  layer3 / layer4
     # and the heads work on 16x16 ... 8x8 maps: the patch matrix is a few MB (one 3-4 us copy kernel) and the product runs
