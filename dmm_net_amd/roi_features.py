@@ -35,13 +35,15 @@ def convert_to_roi_format(boxes: Sequence) -> torch.Tensor:
 
 
 def _layout(feats):
-    """'nhwc' when every level is a channels_last tensor (memory [B,H,W,C]) the NHWC kernel accepts, else 'nchw'."""
+    """'nhwc' when every level is a channels_last tensor (memory [B,H,W,C]) the NHWC kernel accepts, else 'nchw'.  A level of
+    1 x 1 cells (a frame of at most 32 x 32 pixels) is the same memory in both layouts and is contiguous in both senses: it
+    goes with the other levels; when EVERY level is like that the two routes read the same bytes and 'nchw' is answered."""
     C = int(feats[0].shape[1])
     vec = 4 if feats[0].dtype == torch.float32 else 8
     lpc = C // vec
     ok = C % vec == 0 and ((lpc & (lpc - 1)) == 0 if lpc <= 64 else lpc % 64 == 0)
-    if ok and all(f.is_contiguous(memory_format=torch.channels_last) and not f.is_contiguous() and f.data_ptr() % 16 == 0
-                  for f in feats):
+    if ok and all(f.is_contiguous(memory_format=torch.channels_last) and f.data_ptr() % 16 == 0 for f in feats) \
+            and not all(f.is_contiguous() for f in feats):
         return "nhwc"
     return "nchw"
 
@@ -55,7 +57,8 @@ def _arrays(feats):
 
 def roialign4_mean_into(rois: torch.Tensor, feats, out: torch.Tensor) -> torch.Tensor:
     """Inference form with a caller-owned result: rois [R,5] fp32 (image index < 0 = dead row -> zeros), feats = the four
-    NCHW-contiguous levels, out [R, 4*C] fp32.  Nothing is allocated: this is what a captured frame step replays."""
+    NCHW-contiguous levels (or four channels-last levels the NHWC kernel accepts, see ``_layout``), out [R, 4*C] fp32.
+    Nothing is allocated: this is what a captured frame step replays."""
     f0 = feats[0]
     if not f0.is_cuda:
         raise _lib.DmmError("roi features need tensors on an MI355X device (no CPU fallback)")
