@@ -695,7 +695,9 @@ __global__ __launch_bounds__(256) void step_finish_kernel(
             if (do_commit && packed_hist) {                     // the history's 1-bit planes (ballot layout, pad bits 0)
                 const unsigned long long b0 = __ballot(acc[m][0] > 0.5f), b1 = __ballot(acc[m][1] > 0.5f);
                 const unsigned long long b2 = __ballot(acc[m][2] > 0.5f), b3 = __ballot(acc[m][3] > 0.5f);
-                if (lane < 4)
+                // a wave whose 256 pixels start at or after i_end owns no block of this plane: its words would be the next
+                // plane's first ones (the paste kernels bound the same store with i4 < i_end)
+                if (lane < 4 && i4 - 4 * lane < i_end)
                     packed_hist[((int64_t)b * M + m) * words + (i4 - 4 * lane) / 64 + lane] =
                         lane == 0 ? b0 : (lane == 1 ? b1 : (lane == 2 ? b2 : b3));
             }

@@ -253,6 +253,55 @@ def test_training_entries_validate_their_arguments_without_gpu():
     assert L.dmm_launch_count() >= 0
 
 
+def test_frame_step_entries_validate_their_arguments_without_gpu():
+    """The five fixed-slot entries of the frame step (include/dmm_match.h (7b), (8c)) answer before any launch: DMM_ERR_BAD_ARG
+    for a null pointer, a negative size, K <= 0, planes and packed both null and plane_stride < H W; DMM_OK where there is
+    nothing to do; DMM_ERR_UNSUPPORTED from the first mask size past the limit (Mm + 2 padding = 65 for the preparation
+    entries, 33 for dmm_step_finish_f32), R above 1024, more than 8 rows, Pp above 256, K above Pp.  (The largest legal sizes
+    launch: tests/test_gpu_step_ref.py.)"""
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    L = _lib.load()
+    p = ctypes.c_void_p(8)
+    OK, BAD, UNS = 0, 1, 2
+
+    def boxes(prob=p, bx=p, tight=p, images=1, R=4, M=28, H=8, W=8, pad=1):
+        return L.dmm_proposal_boxes_f32(prob, bx, None, images, R, M, H, W, 0.4, pad, None, tight, None)
+    for kw in (dict(prob=None), dict(bx=None), dict(tight=None), dict(images=-1), dict(R=-1), dict(M=0), dict(H=-1), dict(W=-1),
+               dict(pad=-1)):
+        assert boxes(**kw) == BAD, kw
+    assert boxes(images=0) == OK and boxes(R=0) == OK and boxes(images=0, prob=None) == OK
+    assert boxes(M=63) == UNS and boxes(M=65, pad=0) == UNS and boxes(images=1 << 16, R=1 << 15) == UNS
+
+    def nms(tight=p, scores=p, keep=p, cnt=p, images=1, R=4, K=2):
+        return L.dmm_nms_slots_f32(tight, scores, None, images, R, 0.5, K, None, keep, cnt, None)
+    for kw in (dict(tight=None), dict(scores=None), dict(keep=None), dict(cnt=None), dict(images=-1), dict(R=-1), dict(K=0),
+               dict(K=-1)):
+        assert nms(**kw) == BAD, kw
+    assert nms(images=0) == OK and nms(R=1025) == UNS
+
+    def paste(prob=p, bx=p, scores=p, tight=p, keep=p, cnt=p, images=1, R=4, M=28, K=2, H=8, W=8, pad=1, planes=p, stride=64,
+              packed=p):
+        return L.dmm_paste_kept_f32(prob, bx, scores, tight, keep, cnt, images, R, M, K, H, W, pad, None, None, planes, stride,
+                                    packed, None, None, None, None)
+    for kw in (dict(prob=None), dict(bx=None), dict(scores=None), dict(tight=None), dict(keep=None), dict(cnt=None),
+               dict(planes=None, packed=None), dict(stride=63), dict(stride=63, packed=None), dict(images=-1), dict(R=-1),
+               dict(M=0), dict(K=0), dict(K=-3), dict(H=-1), dict(W=-1), dict(pad=-1)):
+        assert paste(**kw) == BAD, kw
+    assert paste(images=0) == OK
+    assert paste(M=63) == UNS and paste(M=63, planes=None) == UNS and paste(images=1024, K=64) == UNS
+
+    def finish(Rb=p, Pp=6, prob=p, bx=p, keep=p, cnt=p, B=1, R=4, Mm=28, K=4, M=5, H=8, W=8, pad=1, full=p, hist=p):
+        return L.dmm_step_finish_f32(Rb, Pp, prob, bx, keep, cnt, B, R, Mm, K, M, H, W, pad, None, None, None, None, full, hist,
+                                     None, None, None)
+    for kw in (dict(Rb=None), dict(prob=None), dict(bx=None), dict(keep=None), dict(cnt=None), dict(full=None), dict(hist=None),
+               dict(B=-1), dict(R=-1), dict(Mm=0), dict(K=0), dict(K=-1), dict(M=-1), dict(H=-1), dict(W=-1), dict(pad=-1)):
+        assert finish(**kw) == BAD, kw
+    assert finish(B=0) == OK and finish(M=0) == OK and finish(H=0) == OK and finish(W=0, Rb=None) == OK
+    assert finish(Mm=31) == UNS and finish(Mm=33, pad=0) == UNS and finish(M=9, Pp=10) == UNS
+    assert finish(Pp=257, K=50) == UNS and finish(K=7) == UNS and finish(B=65536) == UNS
+
+
 def test_product_does_not_import_oracle():
     """The product package must never reach into oracle/ (CPU fallback would void parity)."""
     pkg = os.path.join(ROOT, "dmm_net_amd")
