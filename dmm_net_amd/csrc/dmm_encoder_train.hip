@@ -30,6 +30,8 @@
 
 namespace dmm {
 
+constexpr int kStatTileC8 = 32;           // channel tile of the statistics kernels: 32 sixteen-byte lanes = 256 channels
+
 typedef uint32_t u32x4t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ uint32_t bf16_round(float v) {
@@ -58,11 +60,12 @@ __device__ __forceinline__ void load8f(const float *p, float *f) {
     f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
 }
 
-// fold the 16 per-thread partials (two statistics x 8 channels) of the threads that share a channel group, then one
-// atomic per (channel, statistic) of the workgroup.  red: [256][16] floats.  c8t = channel groups of this workgroup's tile
-// (threads per row), cg0 = first channel group of the tile.
-__device__ __forceinline__ void fold_and_add(const float *acc16, float *red, int c8t, int cg0, int C,
-                                             float *__restrict__ out2C) {
+// fold the 16 per-thread partials (two statistics x 8 channels) of the threads that share a channel group, then per (channel,
+// statistic) of the workgroup one atomic into the [2][C] sums, or (DET) one store into this workgroup's row of a
+// [row groups][2][C] slab.  red: [256][16] floats.  c8t = channel groups of this workgroup's tile (threads per row), cg0 = first
+// channel group of the tile.
+template <bool DET>
+__device__ __forceinline__ void fold_partials(const float *acc16, float *red, int c8t, int cg0, int C, float *__restrict__ out2C) {
     const int t = threadIdx.x;
 #pragma unroll
     for (int k = 0; k < 16; ++k) red[t * 16 + k] = acc16[k];
@@ -72,23 +75,9 @@ __device__ __forceinline__ void fold_and_add(const float *acc16, float *red, int
         float s = 0.0f;
         for (int r = 0; r < rpp; ++r) s += red[(r * c8t) * 16 + j];
         const int cg = j >> 4, k = j & 15;
-        unsafeAtomicAdd(&out2C[(k >> 3) * C + (cg0 + cg) * 8 + (k & 7)], s);
-    }
-}
-
-// the deterministic form: the same fold, stored (no atomics) into this workgroup's row of a [row groups][2][C] slab
-__device__ __forceinline__ void fold_and_store(const float *acc16, float *red, int c8t, int cg0, int C,
-                                               float *__restrict__ slab_row) {
-    const int t = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) red[t * 16 + k] = acc16[k];
-    __syncthreads();
-    const int rpp = 256 / c8t;
-    for (int j = t; j < 16 * c8t; j += 256) {
-        float s = 0.0f;
-        for (int r = 0; r < rpp; ++r) s += red[(r * c8t) * 16 + j];
-        const int cg = j >> 4, k = j & 15;
-        slab_row[(k >> 3) * C + (cg0 + cg) * 8 + (k & 7)] = s;
+        float *o = &out2C[(k >> 3) * C + (cg0 + cg) * 8 + (k & 7)];
+        if (DET) *o = s;
+        else unsafeAtomicAdd(o, s);
     }
 }
 
@@ -146,7 +135,7 @@ template <bool DET>
 __global__ __launch_bounds__(256) void bn_stats_bf16_kernel(const uint16_t *__restrict__ x, int64_t rows, int c8,
                                                             float *__restrict__ stats) {
     __shared__ float red[256 * 16];
-    const int c8t = c8 < 32 ? c8 : 32, cg0 = blockIdx.y * c8t;
+    const int c8t = c8 < kStatTileC8 ? c8 : kStatTileC8, cg0 = blockIdx.y * c8t;
     const int cg = cg0 + threadIdx.x % c8t, ro = threadIdx.x / c8t, rpp = 256 / c8t;
     int64_t r0, r1;
     row_range(rows, rpp, r0, r1);
@@ -177,8 +166,7 @@ __global__ __launch_bounds__(256) void bn_stats_bf16_kernel(const uint16_t *__re
             }
         }
     }
-    if (DET) fold_and_store(acc, red, c8t, cg0, c8 * 8, stats);
-    else fold_and_add(acc, red, c8t, cg0, c8 * 8, stats);
+    fold_partials<DET>(acc, red, c8t, cg0, c8 * 8, stats);
 }
 
 // DET: `stats` is the [groups][nparts][2][C] slab of the deterministic statistics kernel, folded here in a fixed order
@@ -270,7 +258,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const uint16_t 
                                                                  const float *__restrict__ saved, const float *__restrict__ weight,
                                                                  const float *__restrict__ bias, float *__restrict__ sums) {
     __shared__ float red[256 * 16];
-    const int C = c8 * 8, c8t = c8 < 32 ? c8 : 32, cg0 = blockIdx.y * c8t;
+    const int C = c8 * 8, c8t = c8 < kStatTileC8 ? c8 : kStatTileC8, cg0 = blockIdx.y * c8t;
     const int cg = cg0 + threadIdx.x % c8t, ro = threadIdx.x / c8t, rpp = 256 / c8t;
     saved += (int64_t)blockIdx.z * 2 * C;                 // (blockIdx.z = the statistics group)
     sums += (int64_t)(DET ? blockIdx.z * gridDim.x + blockIdx.x : blockIdx.z) * 2 * C;
@@ -329,8 +317,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_bf16_kernel(const uint16_t 
             }
         }
     }
-    if (DET) fold_and_store(acc, red, c8t, cg0, C, sums);
-    else fold_and_add(acc, red, c8t, cg0, C, sums);
+    fold_partials<DET>(acc, red, c8t, cg0, C, sums);
 }
 
 // DET: `sums` is the [groups][nparts][2][C] slab of the deterministic reduce, folded here in a fixed order
@@ -538,15 +525,16 @@ __global__ __launch_bounds__(256) void bn_fold_kernel(const float *__restrict__ 
     }
 }
 
-static inline bool bn_shape_ok(int64_t rows, int C) {
-    if (rows <= 0 || C <= 0 || (C & 7)) return false;
+// widths the kernels take: C / 8 sixteen-byte lanes of a row, a divisor of the 256 threads
+static inline bool bn_width_ok(int C) {
+    if (C <= 0 || (C & 7)) return false;
     const int c8 = C / 8;
     return c8 <= 256 && 256 % c8 == 0;
 }
 
 // statistics kernels: (row groups, channel tiles); row groups x 2C atomics <= 128 k, >= 8 passes per workgroup
 static inline dim3 bn_stat_grid(int64_t rows, int c8, int groups) {      // rows: of ONE statistics group
-    const int c8t = c8 < 32 ? c8 : 32, rpp = 256 / c8t;
+    const int c8t = c8 < kStatTileC8 ? c8 : kStatTileC8, rpp = 256 / c8t;
     int64_t g = (rows + (int64_t)rpp * 8 - 1) / ((int64_t)rpp * 8);
     int64_t cap = 65536 / (8 * c8) < 256 ? 65536 / (8 * c8) : 256;
     cap = cap / groups > 0 ? cap / groups : 1;                             // (the atomics of all groups count)
@@ -566,44 +554,222 @@ static inline unsigned bn_grid(int64_t rows, int c8, int min_iters, int cap) {
 
 }  // namespace dmm
 
+// ---- the host side of the BatchNorm entries: one argument bundle, one check, one launcher per kernel ---------------------
 // rows = ALL rows; `groups` statistics groups of rows / groups consecutive rows each (groups calls of the layer on the groups'
 // row ranges, in order, in one launch).  stats / saved / sums: [groups][2][C].
 static inline bool bn_groups_ok(int64_t rows, int groups) { return groups >= 1 && groups <= 64 && rows % groups == 0; }
 
-extern "C" int dmm_bn_stats_grouped_bf16(const void *x, int64_t rows, int C, int groups, float *stats, dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!x || !stats) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    const int c8 = C / 8;
-    hipLaunchKernelGGL(dmm::bn_stats_bf16_kernel<false>, dmm::bn_stat_grid(rows / groups, c8, groups), dim3(256), 0,
-                       (hipStream_t)stream, (const uint16_t *)x, rows / groups, c8, stats);
+// The slab of one deterministic statistics / reduce launch: [groups][row groups][2][C] fp32, row groups = the statistics
+// grid's; 0 for what the entries do not take (with rows > 0 and groups dividing rows every group has a row, so the width is
+// all that is left to ask).  The one answer to "how large": the entries' check asks here too.
+extern "C" size_t dmm_bn_det_workspace_bytes(int64_t rows, int C, int groups) {
+    if (rows <= 0 || !bn_groups_ok(rows, groups) || !dmm::bn_width_ok(C)) return 0;
+    return (size_t)groups * dmm::bn_stat_grid(rows / groups, C / 8, groups).x * 2 * (size_t)C * sizeof(float);
+}
+
+namespace {
+
+// What the 13 entries fill in and the check and the launchers read: every tensor of the layer under ONE name, whichever
+// entry hands it over.  rows = all rows.  det: the deterministic form.  scratch: the sums between the two launches of a
+// direction -- atomic form: [groups][2][C] floats the caller zeroed (stats / sums); deterministic form: the slab (workspace) of
+// scratch_bytes bytes -- written by stats / reduce, read by apply / dx / fold.  relu: a flag for apply; for the backward 0 none,
+// 1 the mask from y, 2 the mask recomputed from x.  y and saved [groups][2][C] (mean, invstd) are written by apply and read by
+// the backward.  out: the fold's [groups][2][C].  Last, what bn_entry derives once the check has accepted the shape: c8 =
+// 16-byte lanes of a row, nparts = row groups of the slab (0 in the atomic form), grows = rows of one statistics group.
+struct BnArgs {
+    int64_t rows;
+    int C, groups;
+    bool det;
+    const void *scratch;
+    size_t scratch_bytes;
+    const void *x = nullptr, *residual = nullptr, *dy = nullptr, *dy2 = nullptr;
+    const float *weight = nullptr, *bias = nullptr;
+    int relu = 0;
+    float momentum = 0.0f, eps = 0.0f;
+    void *y = nullptr, *dx = nullptr, *dres = nullptr;
+    float *saved = nullptr, *running_mean = nullptr, *running_var = nullptr, *dweight = nullptr, *dbias = nullptr, *out = nullptr;
+    int c8 = 0, nparts = 0;
+    int64_t grows = 0;
+};
+
+enum BnKind { BN_STATS, BN_APPLY, BN_REDUCE, BN_DX, BN_FOLD };
+
+// The entries' answers, in this order for every kind and both forms (include/dmm_match.h (10) says the same):
+//   1. DMM_ERR_BAD_ARG      rows < 0, C <= 0, groups outside 1..64 or not dividing rows, (backward) relu outside 0..2
+//   2. DMM_OK               rows == 0: nothing to do, whatever the pointers and the width
+//   3. DMM_ERR_BAD_ARG      a null pointer the kind cannot do without -- the atomic form's stats / sums among them, the
+//                           deterministic form's workspace NOT yet --, one running statistic without the other, relu == 1
+//                           without y, relu == 2 without weight / bias or with dres
+//   4. DMM_ERR_UNSUPPORTED  a width the kernels do not take
+//   5. deterministic form   DMM_ERR_BAD_ARG for a null workspace, then DMM_ERR_WORKSPACE for a short one
+// so a missing or short workspace is named only for a call that is otherwise in order.
+int bn_entry_check(const BnArgs &a, BnKind kind) {
+    const bool bwd = kind == BN_REDUCE || kind == BN_DX;
+    if (a.rows < 0 || a.C <= 0 || (bwd && (a.relu < 0 || a.relu > 2)) || !bn_groups_ok(a.rows, a.groups)) return DMM_ERR_BAD_ARG;
+    if (a.rows == 0) return DMM_OK;
+    bool have = a.det || a.scratch;
+    switch (kind) {
+        case BN_STATS: have = have && a.x; break;
+        case BN_APPLY: have = have && a.x && a.weight && a.bias && a.y && a.saved && (!a.running_mean) == (!a.running_var); break;
+        case BN_REDUCE: have = have && a.dy && a.x && a.saved && (a.relu != 1 || a.y) && (a.relu != 2 || (a.weight && a.bias)); break;
+        case BN_DX:                       // (relu == 2 with dres: a residual in front of the ReLU, the mask needs the output)
+            have = have && a.dy && a.x && a.saved && a.weight && a.dx && a.dweight && a.dbias && (a.relu != 1 || a.y) &&
+                   (a.relu != 2 || (a.bias && !a.dres));
+            break;
+        case BN_FOLD: have = a.out != nullptr; break;
+    }
+    if (!have) return DMM_ERR_BAD_ARG;
+    if (!dmm::bn_width_ok(a.C)) return DMM_ERR_UNSUPPORTED;
+    if (a.det && !a.scratch) return DMM_ERR_BAD_ARG;
+    if (a.det && a.scratch_bytes < dmm_bn_det_workspace_bytes(a.rows, a.C, a.groups)) return DMM_ERR_WORKSPACE;
+    return DMM_OK;
+}
+
+// a run-time flag / relu mode as the template argument of the launch written in `f`
+template <typename F>
+void with_flag(bool on, F &&f) { on ? f(std::true_type{}) : f(std::false_type{}); }
+template <int I>
+using mode_c = std::integral_constant<int, I>;
+template <typename F>
+void with_relu_mode(int relu, F &&f) { relu == 2 ? f(mode_c<2>{}) : relu == 1 ? f(mode_c<1>{}) : f(mode_c<0>{}); }
+
+dim3 bn_stat_grid(const BnArgs &a) { return dmm::bn_stat_grid(a.grows, a.c8, a.groups); }
+dim3 bn_elementwise_grid(const BnArgs &a) { return dim3(dmm::bn_grid(a.grows, a.c8, 2, 4096 / a.groups), 1, (unsigned)a.groups); }
+
+void bn_stats_launch(const BnArgs &a, hipStream_t stream) {
+    with_flag(a.det, [&](auto det) {
+        hipLaunchKernelGGL(dmm::bn_stats_bf16_kernel<decltype(det)::value>, bn_stat_grid(a), dim3(256), 0, stream,
+                           (const uint16_t *)a.x, a.grows, a.c8, (float *)a.scratch);
+    });
+}
+
+void bn_apply_launch(const BnArgs &a, hipStream_t stream) {
+    with_flag(a.det, [&](auto det) { with_flag(a.residual != nullptr, [&](auto res) { with_flag(a.relu != 0, [&](auto relu) {
+        hipLaunchKernelGGL((dmm::bn_apply_bf16_kernel<decltype(res)::value, decltype(relu)::value, decltype(det)::value>),
+                           bn_elementwise_grid(a), dim3(256), 0, stream, (const uint16_t *)a.x, (const uint16_t *)a.residual,
+                           a.grows, a.c8, (const float *)a.scratch, a.weight, a.bias, a.running_mean, a.running_var,
+                           a.momentum, a.eps, (uint16_t *)a.y, a.saved, a.nparts);
+    }); }); });
+}
+
+void bn_reduce_launch(const BnArgs &a, hipStream_t stream) {
+    with_flag(a.det, [&](auto det) { with_relu_mode(a.relu, [&](auto mode) {
+        hipLaunchKernelGGL((dmm::bn_bwd_reduce_bf16_kernel<decltype(mode)::value, decltype(det)::value>), bn_stat_grid(a),
+                           dim3(256), 0, stream, (const uint16_t *)a.dy, (const uint16_t *)a.dy2, (const uint16_t *)a.x,
+                           (const uint16_t *)a.y, a.grows, a.c8, a.saved, a.weight, a.bias, (float *)a.scratch);
+    }); });
+}
+
+void bn_dx_launch(const BnArgs &a, hipStream_t stream) {
+    with_flag(a.det, [&](auto det) { with_relu_mode(a.relu, [&](auto mode) { with_flag(a.dres != nullptr, [&](auto dres) {
+        constexpr int RELU = decltype(mode)::value;                     // (mode 2 has no dres: the check refused it)
+        hipLaunchKernelGGL((dmm::bn_bwd_dx_bf16_kernel<RELU, RELU != 2 && decltype(dres)::value, decltype(det)::value>),
+                           bn_elementwise_grid(a), dim3(256), 0, stream, (const uint16_t *)a.dy, (const uint16_t *)a.dy2,
+                           (const uint16_t *)a.x, (const uint16_t *)a.y, a.grows, a.c8, a.saved, a.weight, a.bias,
+                           (const float *)a.scratch, (uint16_t *)a.dx, (uint16_t *)a.dres, a.dweight, a.dbias, a.nparts);
+    }); }); });
+}
+
+void bn_fold_launch(const BnArgs &a, hipStream_t stream) {
+    hipLaunchKernelGGL(dmm::bn_fold_kernel, dim3((unsigned)a.groups), dim3(256), 0, stream, (const float *)a.scratch, a.nparts,
+                       a.c8, a.out);
+}
+
+// what every entry ends with: the check, the derived sizes, the kind's launch
+int bn_entry(BnArgs a, BnKind kind, void (*launch)(const BnArgs &, hipStream_t), dmm_stream_t stream) {
+    const int rc = bn_entry_check(a, kind);
+    if (rc != DMM_OK || a.rows == 0) return rc;
+    a.c8 = a.C / 8, a.grows = a.rows / a.groups;
+    a.nparts = a.det ? (int)bn_stat_grid(a).x : 0;
+    launch(a, (hipStream_t)stream);
     return dmm::check_launch();
 }
 
-extern "C" int dmm_bn_stats_bf16(const void *x, int64_t rows, int C, float *stats, dmm_stream_t stream) {
-    return dmm_bn_stats_grouped_bf16(x, rows, C, 1, stats, stream);
+void bn_apply_fill(BnArgs &a, const void *residual, const float *weight, const float *bias, float *running_mean,
+                   float *running_var, float momentum, float eps, int relu, void *y, float *saved) {
+    a.residual = residual, a.weight = weight, a.bias = bias, a.running_mean = running_mean, a.running_var = running_var;
+    a.momentum = momentum, a.eps = eps, a.relu = relu, a.y = y, a.saved = saved;
+}
+
+void bn_bwd_fill(BnArgs &a, const void *dy, const void *dy2, const void *y, const float *saved, const float *weight,
+                 const float *bias, int relu, void *dx = nullptr, void *dres = nullptr, float *dweight = nullptr,
+                 float *dbias = nullptr) {
+    a.dy = dy, a.dy2 = dy2, a.y = const_cast<void *>(y), a.saved = const_cast<float *>(saved), a.weight = weight, a.bias = bias;
+    a.relu = relu, a.dx = dx, a.dres = dres, a.dweight = dweight, a.dbias = dbias;
+}
+
+}  // namespace
+
+extern "C" int dmm_bn_stats_grouped_bf16(const void *x, int64_t rows, int C, int groups, float *stats, dmm_stream_t stream) {
+    return bn_entry(BnArgs{rows, C, groups, false, stats, 0, x}, BN_STATS, bn_stats_launch, stream);
+}
+
+extern "C" int dmm_bn_stats_det_grouped_bf16(const void *x, int64_t rows, int C, int groups, void *ws, size_t ws_bytes,
+                                             dmm_stream_t stream) {
+    return bn_entry(BnArgs{rows, C, groups, true, ws, ws_bytes, x}, BN_STATS, bn_stats_launch, stream);
 }
 
 extern "C" int dmm_bn_apply_grouped_bf16(const void *x, const void *residual, int64_t rows, int C, int groups,
                                          const float *stats, const float *weight, const float *bias, float *running_mean,
                                          float *running_var, float momentum, float eps, int relu, void *y, float *saved,
                                          dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!x || !stats || !weight || !bias || !y || !saved || (!running_mean) != (!running_var)) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    const int c8 = C / 8;
-    const int64_t grows = rows / groups;
-    const dim3 grid(dmm::bn_grid(grows, c8, 2, 4096 / groups), 1, (unsigned)groups);
-#define DMM_BNA(RES_, RELU_)                                                                                             \
-    hipLaunchKernelGGL((dmm::bn_apply_bf16_kernel<RES_, RELU_, false>), grid, dim3(256), 0, (hipStream_t)stream,                \
-                       (const uint16_t *)x, (const uint16_t *)residual, grows, c8, stats, weight, bias, running_mean,    \
-                       running_var, momentum, eps, (uint16_t *)y, saved, 0)
-    if (residual) { if (relu) DMM_BNA(true, true); else DMM_BNA(true, false); }
-    else { if (relu) DMM_BNA(false, true); else DMM_BNA(false, false); }
-#undef DMM_BNA
-    return dmm::check_launch();
+    BnArgs a{rows, C, groups, false, stats, 0, x};
+    bn_apply_fill(a, residual, weight, bias, running_mean, running_var, momentum, eps, relu, y, saved);
+    return bn_entry(a, BN_APPLY, bn_apply_launch, stream);
+}
+
+extern "C" int dmm_bn_apply_det_grouped_bf16(const void *x, const void *residual, int64_t rows, int C, int groups,
+                                             const void *ws, size_t ws_bytes, const float *weight, const float *bias,
+                                             float *running_mean, float *running_var, float momentum, float eps, int relu,
+                                             void *y, float *saved, dmm_stream_t stream) {
+    BnArgs a{rows, C, groups, true, ws, ws_bytes, x};
+    bn_apply_fill(a, residual, weight, bias, running_mean, running_var, momentum, eps, relu, y, saved);
+    return bn_entry(a, BN_APPLY, bn_apply_launch, stream);
+}
+
+extern "C" int dmm_bn_bwd_reduce_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows, int C, int groups,
+                                              const float *saved, const float *weight, const float *bias, int relu,
+                                              float *sums, dmm_stream_t stream) {
+    BnArgs a{rows, C, groups, false, sums, 0, x};
+    bn_bwd_fill(a, dy, dy2, y, saved, weight, bias, relu);
+    return bn_entry(a, BN_REDUCE, bn_reduce_launch, stream);
+}
+
+extern "C" int dmm_bn_bwd_reduce_det_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows,
+                                                  int C, int groups, const float *saved, const float *weight, const float *bias,
+                                                  int relu, void *ws, size_t ws_bytes, dmm_stream_t stream) {
+    BnArgs a{rows, C, groups, true, ws, ws_bytes, x};
+    bn_bwd_fill(a, dy, dy2, y, saved, weight, bias, relu);
+    return bn_entry(a, BN_REDUCE, bn_reduce_launch, stream);
+}
+
+extern "C" int dmm_bn_bwd_dx_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows, int C, int groups,
+                                          const float *saved, const float *weight, const float *bias, const float *sums,
+                                          int relu, void *dx, void *dres, float *dweight, float *dbias, dmm_stream_t stream) {
+    BnArgs a{rows, C, groups, false, sums, 0, x};
+    bn_bwd_fill(a, dy, dy2, y, saved, weight, bias, relu, dx, dres, dweight, dbias);
+    return bn_entry(a, BN_DX, bn_dx_launch, stream);
+}
+
+extern "C" int dmm_bn_bwd_dx_det_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows, int C,
+                                              int groups, const float *saved, const float *weight, const float *bias,
+                                              const void *ws, size_t ws_bytes, int relu, void *dx, void *dres, float *dweight,
+                                              float *dbias, dmm_stream_t stream) {
+    BnArgs a{rows, C, groups, true, ws, ws_bytes, x};
+    bn_bwd_fill(a, dy, dy2, y, saved, weight, bias, relu, dx, dres, dweight, dbias);
+    return bn_entry(a, BN_DX, bn_dx_launch, stream);
+}
+
+extern "C" int dmm_bn_fold_det(const void *ws, size_t ws_bytes, int64_t rows, int C, int groups, float *out,
+                               dmm_stream_t stream) {
+    BnArgs a{rows, C, groups, true, ws, ws_bytes};
+    a.out = out;
+    return bn_entry(a, BN_FOLD, bn_fold_launch, stream);
+}
+
+// the plain entries: one statistics group, one gradient plane
+extern "C" int dmm_bn_stats_bf16(const void *x, int64_t rows, int C, float *stats, dmm_stream_t stream) {
+    return dmm_bn_stats_grouped_bf16(x, rows, C, 1, stats, stream);
 }
 
 extern "C" int dmm_bn_apply_bf16(const void *x, const void *residual, int64_t rows, int C, const float *stats,
@@ -613,164 +779,15 @@ extern "C" int dmm_bn_apply_bf16(const void *x, const void *residual, int64_t ro
                                      relu, y, saved, stream);
 }
 
-extern "C" int dmm_bn_bwd_reduce_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows, int C, int groups,
-                                              const float *saved, const float *weight, const float *bias, int relu,
-                                              float *sums, dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || relu < 0 || relu > 2 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!dy || !x || !saved || !sums || (relu == 1 && !y) || (relu == 2 && (!weight || !bias))) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    const int c8 = C / 8;
-    const int64_t grows = rows / groups;
-    const dim3 grid = dmm::bn_stat_grid(grows, c8, groups);
-#define DMM_BNR(R_)                                                                                                    \
-    hipLaunchKernelGGL((dmm::bn_bwd_reduce_bf16_kernel<R_, false>), grid, dim3(256), 0, (hipStream_t)stream, (const uint16_t *)dy, \
-                       (const uint16_t *)dy2, (const uint16_t *)x, (const uint16_t *)y, grows, c8, saved, weight, bias, sums)
-    if (relu == 2) DMM_BNR(2); else if (relu == 1) DMM_BNR(1); else DMM_BNR(0);
-#undef DMM_BNR
-    return dmm::check_launch();
-}
-
 extern "C" int dmm_bn_bwd_reduce_bf16(const void *dy, const void *x, const void *y, int64_t rows, int C, const float *saved,
                                       const float *weight, const float *bias, int relu, float *sums, dmm_stream_t stream) {
     return dmm_bn_bwd_reduce_grouped_bf16(dy, nullptr, x, y, rows, C, 1, saved, weight, bias, relu, sums, stream);
-}
-
-extern "C" int dmm_bn_bwd_dx_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows, int C, int groups,
-                                          const float *saved, const float *weight, const float *bias, const float *sums,
-                                          int relu, void *dx, void *dres, float *dweight, float *dbias, dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || relu < 0 || relu > 2 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!dy || !x || !saved || !weight || !sums || !dx || !dweight || !dbias || (relu == 1 && !y) || (relu == 2 && !bias))
-        return DMM_ERR_BAD_ARG;
-    if (relu == 2 && dres) return DMM_ERR_BAD_ARG;        // (a residual in front of the ReLU: the mask needs the output)
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    const int c8 = C / 8;
-    const int64_t grows = rows / groups;
-    const dim3 grid(dmm::bn_grid(grows, c8, 2, 4096 / groups), 1, (unsigned)groups);
-#define DMM_BND(RELU_, DRES_)                                                                                            \
-    hipLaunchKernelGGL((dmm::bn_bwd_dx_bf16_kernel<RELU_, DRES_, false>), grid, dim3(256), 0, (hipStream_t)stream,              \
-                       (const uint16_t *)dy, (const uint16_t *)dy2, (const uint16_t *)x, (const uint16_t *)y, grows, c8, saved,  \
-                       weight, bias, sums, (uint16_t *)dx, (uint16_t *)dres, dweight, dbias, 0)
-    if (relu == 2) DMM_BND(2, false);
-    else if (relu == 1) { if (dres) DMM_BND(1, true); else DMM_BND(1, false); }
-    else { if (dres) DMM_BND(0, true); else DMM_BND(0, false); }
-#undef DMM_BND
-    return dmm::check_launch();
 }
 
 extern "C" int dmm_bn_bwd_dx_bf16(const void *dy, const void *x, const void *y, int64_t rows, int C, const float *saved,
                                   const float *weight, const float *bias, const float *sums, int relu, void *dx, void *dres,
                                   float *dweight, float *dbias, dmm_stream_t stream) {
     return dmm_bn_bwd_dx_grouped_bf16(dy, nullptr, x, y, rows, C, 1, saved, weight, bias, sums, relu, dx, dres, dweight, dbias, stream);
-}
-
-// ---- deterministic forms: per-workgroup slabs folded in a fixed order by the consumer (no float atomics) ----------------
-// the slab of one statistics / reduce launch: [groups][row groups][2][C] fp32, row groups = the statistics grid's
-static inline int64_t bn_det_parts(int64_t rows, int C, int groups) {
-    return (int64_t)dmm::bn_stat_grid(rows / groups, C / 8, groups).x;
-}
-
-extern "C" size_t dmm_bn_det_workspace_bytes(int64_t rows, int C, int groups) {
-    if (rows <= 0 || !bn_groups_ok(rows, groups) || !dmm::bn_shape_ok(rows / groups, C)) return 0;
-    return (size_t)groups * (size_t)bn_det_parts(rows, C, groups) * 2 * (size_t)C * sizeof(float);
-}
-
-static inline int bn_det_ws_check(const void *ws, size_t ws_bytes, int64_t rows, int C, int groups) {
-    if (!ws) return DMM_ERR_BAD_ARG;
-    return ws_bytes < dmm_bn_det_workspace_bytes(rows, C, groups) ? DMM_ERR_WORKSPACE : DMM_OK;
-}
-
-extern "C" int dmm_bn_stats_det_grouped_bf16(const void *x, int64_t rows, int C, int groups, void *ws, size_t ws_bytes,
-                                             dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!x) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    if (const int rc = bn_det_ws_check(ws, ws_bytes, rows, C, groups)) return rc;
-    const int c8 = C / 8;
-    hipLaunchKernelGGL(dmm::bn_stats_bf16_kernel<true>, dmm::bn_stat_grid(rows / groups, c8, groups), dim3(256), 0,
-                       (hipStream_t)stream, (const uint16_t *)x, rows / groups, c8, (float *)ws);
-    return dmm::check_launch();
-}
-
-extern "C" int dmm_bn_apply_det_grouped_bf16(const void *x, const void *residual, int64_t rows, int C, int groups,
-                                             const void *ws, size_t ws_bytes, const float *weight, const float *bias,
-                                             float *running_mean, float *running_var, float momentum, float eps, int relu,
-                                             void *y, float *saved, dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!x || !weight || !bias || !y || !saved || (!running_mean) != (!running_var)) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    if (const int rc = bn_det_ws_check(ws, ws_bytes, rows, C, groups)) return rc;
-    const int c8 = C / 8, nparts = (int)bn_det_parts(rows, C, groups);
-    const int64_t grows = rows / groups;
-    const dim3 grid(dmm::bn_grid(grows, c8, 2, 4096 / groups), 1, (unsigned)groups);
-#define DMM_BNA(RES_, RELU_)                                                                                             \
-    hipLaunchKernelGGL((dmm::bn_apply_bf16_kernel<RES_, RELU_, true>), grid, dim3(256), 0, (hipStream_t)stream,          \
-                       (const uint16_t *)x, (const uint16_t *)residual, grows, c8, (const float *)ws, weight, bias,      \
-                       running_mean, running_var, momentum, eps, (uint16_t *)y, saved, nparts)
-    if (residual) { if (relu) DMM_BNA(true, true); else DMM_BNA(true, false); }
-    else { if (relu) DMM_BNA(false, true); else DMM_BNA(false, false); }
-#undef DMM_BNA
-    return dmm::check_launch();
-}
-
-extern "C" int dmm_bn_bwd_reduce_det_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows,
-                                                  int C, int groups, const float *saved, const float *weight, const float *bias,
-                                                  int relu, void *ws, size_t ws_bytes, dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || relu < 0 || relu > 2 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!dy || !x || !saved || (relu == 1 && !y) || (relu == 2 && (!weight || !bias))) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    if (const int rc = bn_det_ws_check(ws, ws_bytes, rows, C, groups)) return rc;
-    const int c8 = C / 8;
-    const int64_t grows = rows / groups;
-    const dim3 grid = dmm::bn_stat_grid(grows, c8, groups);
-#define DMM_BNR(R_)                                                                                                    \
-    hipLaunchKernelGGL((dmm::bn_bwd_reduce_bf16_kernel<R_, true>), grid, dim3(256), 0, (hipStream_t)stream,              \
-                       (const uint16_t *)dy, (const uint16_t *)dy2, (const uint16_t *)x, (const uint16_t *)y, grows, c8, \
-                       saved, weight, bias, (float *)ws)
-    if (relu == 2) DMM_BNR(2); else if (relu == 1) DMM_BNR(1); else DMM_BNR(0);
-#undef DMM_BNR
-    return dmm::check_launch();
-}
-
-extern "C" int dmm_bn_bwd_dx_det_grouped_bf16(const void *dy, const void *dy2, const void *x, const void *y, int64_t rows, int C,
-                                              int groups, const float *saved, const float *weight, const float *bias,
-                                              const void *ws, size_t ws_bytes, int relu, void *dx, void *dres, float *dweight,
-                                              float *dbias, dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || relu < 0 || relu > 2 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!dy || !x || !saved || !weight || !dx || !dweight || !dbias || (relu == 1 && !y) || (relu == 2 && !bias))
-        return DMM_ERR_BAD_ARG;
-    if (relu == 2 && dres) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    if (const int rc = bn_det_ws_check(ws, ws_bytes, rows, C, groups)) return rc;
-    const int c8 = C / 8, nparts = (int)bn_det_parts(rows, C, groups);
-    const int64_t grows = rows / groups;
-    const dim3 grid(dmm::bn_grid(grows, c8, 2, 4096 / groups), 1, (unsigned)groups);
-#define DMM_BND(RELU_, DRES_)                                                                                            \
-    hipLaunchKernelGGL((dmm::bn_bwd_dx_bf16_kernel<RELU_, DRES_, true>), grid, dim3(256), 0, (hipStream_t)stream,        \
-                       (const uint16_t *)dy, (const uint16_t *)dy2, (const uint16_t *)x, (const uint16_t *)y, grows, c8, \
-                       saved, weight, bias, (const float *)ws, (uint16_t *)dx, (uint16_t *)dres, dweight, dbias, nparts)
-    if (relu == 2) DMM_BND(2, false);
-    else if (relu == 1) { if (dres) DMM_BND(1, true); else DMM_BND(1, false); }
-    else { if (dres) DMM_BND(0, true); else DMM_BND(0, false); }
-#undef DMM_BND
-    return dmm::check_launch();
-}
-
-extern "C" int dmm_bn_fold_det(const void *ws, size_t ws_bytes, int64_t rows, int C, int groups, float *out,
-                               dmm_stream_t stream) {
-    if (rows < 0 || C <= 0 || !bn_groups_ok(rows, groups)) return DMM_ERR_BAD_ARG;
-    if (rows == 0) return DMM_OK;
-    if (!out) return DMM_ERR_BAD_ARG;
-    if (!dmm::bn_shape_ok(rows, C)) return DMM_ERR_UNSUPPORTED;
-    if (const int rc = bn_det_ws_check(ws, ws_bytes, rows, C, groups)) return rc;
-    hipLaunchKernelGGL(dmm::bn_fold_kernel, dim3((unsigned)groups), dim3(256), 0, (hipStream_t)stream, (const float *)ws,
-                       (int)bn_det_parts(rows, C, groups), C / 8, out);
-    return dmm::check_launch();
 }
 
 extern "C" int dmm_wprep3x3_bf16(const void *table, int n, int64_t tiles, dmm_stream_t stream) {

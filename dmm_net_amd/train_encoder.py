@@ -134,6 +134,19 @@ def _det_ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
 
 
+def _bn_scratch(det: bool, R: int, C: int, groups: int, device):
+    """What differs between the two forms of the ``dmm_bn_*_grouped_bf16`` entries: -> (the entry-name infix, the scratch
+    arguments, which sit at the same position in both forms, the tensor behind them).  Atomic: the [groups, 2, C] sums,
+    zeroed; deterministic: the slab of per-workgroup partials the consuming launch folds, with its byte count -- sized here
+    and nowhere else."""
+    if det:
+        from . import _lib
+        ws = _det_ws(int(_lib.load().dmm_bn_det_workspace_bytes(R, C, groups)), device)
+        return "_det", (ws.data_ptr(), ws.numel()), ws
+    sums = _zeroed(groups * 2 * C, device)
+    return "", (sums.data_ptr(),), sums
+
+
 # ---- BatchNorm (+ residual) (+ ReLU), training mode, bf16 NHWC: two launches each way -------------------------------
 class _BNActFn(torch.autograd.Function):
     """y = act(BN_train(x) (+ residual)) on a channels-last bf16 activation; statistics, scale and shift in fp32.
@@ -150,7 +163,7 @@ class _BNActFn(torch.autograd.Function):
         R = B * H * W
         stream = torch.cuda.current_stream(x.device).cuda_stream
         det = _det_now()
-        stats = None if det else _zeroed(groups * 2 * C, x.device)
+        form, scratch, _keep = _bn_scratch(det, R, C, groups, x.device)
         y = torch.empty_like(x, memory_format=_CL)
         saved = torch.empty((groups, 2, C), dtype=torch.float32, device=x.device)  # mean, invstd of every statistics group
         res = None
@@ -159,18 +172,10 @@ class _BNActFn(torch.autograd.Function):
             res = residual.contiguous(memory_format=_CL)
         rm = None if running_mean is None else running_mean.data_ptr()
         rv = None if running_var is None else running_var.data_ptr()
-        if det:                                           # (the slab of per-workgroup partials, folded by the apply launch)
-            ws = _det_ws(int(_lib.load().dmm_bn_det_workspace_bytes(R, C, groups)), x.device)
-            _lib.call("dmm_bn_stats_det_grouped_bf16", x.device, x.data_ptr(), R, C, groups, ws.data_ptr(), ws.numel(),
-                      stream)
-            _lib.call("dmm_bn_apply_det_grouped_bf16", x.device, x.data_ptr(), None if res is None else res.data_ptr(), R,
-                      C, groups, ws.data_ptr(), ws.numel(), weight.data_ptr(), bias.data_ptr(), rm, rv, float(momentum),
-                      float(eps), int(relu), y.data_ptr(), saved.data_ptr(), stream)
-        else:
-            _lib.call("dmm_bn_stats_grouped_bf16", x.device, x.data_ptr(), R, C, groups, stats.data_ptr(), stream)
-            _lib.call("dmm_bn_apply_grouped_bf16", x.device, x.data_ptr(), None if res is None else res.data_ptr(), R, C,
-                      groups, stats.data_ptr(), weight.data_ptr(), bias.data_ptr(), rm, rv, float(momentum), float(eps),
-                      int(relu), y.data_ptr(), saved.data_ptr(), stream)
+        _lib.call(f"dmm_bn_stats{form}_grouped_bf16", x.device, x.data_ptr(), R, C, groups, *scratch, stream)
+        _lib.call(f"dmm_bn_apply{form}_grouped_bf16", x.device, x.data_ptr(), None if res is None else res.data_ptr(), R, C,
+                  groups, *scratch, weight.data_ptr(), bias.data_ptr(), rm, rv, float(momentum), float(eps), int(relu),
+                  y.data_ptr(), saved.data_ptr(), stream)
         ctx.save_for_backward(x, y, weight, bias, saved)
         ctx.relu, ctx.has_res, ctx.groups, ctx.det = bool(relu), residual is not None, groups, det
         # fork: the output as TWO tensors (the second an alias) for its two consumers -- a residual block's first convolution and
@@ -193,26 +198,16 @@ class _BNActFn(torch.autograd.Function):
             dy2 = dy2.to(dy.dtype).contiguous(memory_format=_CL)
         stream = torch.cuda.current_stream(x.device).cuda_stream
         groups = ctx.groups
-        sums = None if ctx.det else _zeroed(groups * 2 * C, x.device)
+        form, scratch, _keep = _bn_scratch(ctx.det, R, C, groups, x.device)
         dx = torch.empty_like(x, memory_format=_CL)
         dres = torch.empty_like(x, memory_format=_CL) if ctx.has_res else None
         dw = torch.empty((C,), dtype=torch.float32, device=x.device)
         db = torch.empty((C,), dtype=torch.float32, device=x.device)
-        p2 = None if dy2 is None else dy2.data_ptr()
-        pdres = None if dres is None else dres.data_ptr()
-        if ctx.det:
-            ws = _det_ws(int(_lib.load().dmm_bn_det_workspace_bytes(R, C, groups)), x.device)
-            _lib.call("dmm_bn_bwd_reduce_det_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C,
-                      groups, saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), mode, ws.data_ptr(), ws.numel(), stream)
-            _lib.call("dmm_bn_bwd_dx_det_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C,
-                      groups, saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), ws.data_ptr(), ws.numel(), mode,
-                      dx.data_ptr(), pdres, dw.data_ptr(), db.data_ptr(), stream)
-            return dx, dw, db, None, None, None, None, None, dres, None, None
-        _lib.call("dmm_bn_bwd_reduce_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
-                  saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), mode, sums.data_ptr(), stream)
-        _lib.call("dmm_bn_bwd_dx_grouped_bf16", x.device, dy.data_ptr(), p2, x.data_ptr(), y.data_ptr(), R, C, groups,
-                  saved.data_ptr(), weight.data_ptr(), bias.data_ptr(), sums.data_ptr(), mode, dx.data_ptr(), pdres,
-                  dw.data_ptr(), db.data_ptr(), stream)
+        head = (dy.data_ptr(), None if dy2 is None else dy2.data_ptr(), x.data_ptr(), y.data_ptr(), R, C, groups,
+                saved.data_ptr(), weight.data_ptr(), bias.data_ptr())
+        _lib.call(f"dmm_bn_bwd_reduce{form}_grouped_bf16", x.device, *head, mode, *scratch, stream)
+        _lib.call(f"dmm_bn_bwd_dx{form}_grouped_bf16", x.device, *head, *scratch, mode, dx.data_ptr(),
+                  None if dres is None else dres.data_ptr(), dw.data_ptr(), db.data_ptr(), stream)
         return dx, dw, db, None, None, None, None, None, dres, None, None
 
 
@@ -423,17 +418,12 @@ def _channel_sums(dy, det: bool = False):
     c8 = C // 8
     if dy.is_cuda and dy.dtype == torch.bfloat16 and C % 8 == 0 and c8 <= 256 and 256 % c8 == 0:
         from . import _lib
+        R, stream = B * H * W, torch.cuda.current_stream(dy.device).cuda_stream
+        form, scratch, stats = _bn_scratch(det, R, C, 1, dy.device)
+        _lib.call(f"dmm_bn_stats{form}_grouped_bf16", dy.device, dy.data_ptr(), R, C, 1, *scratch, stream)
         if det:
-            L, R = _lib.load(), B * H * W
-            ws = _det_ws(int(L.dmm_bn_det_workspace_bytes(R, C, 1)), dy.device)
             stats = torch.empty((2 * C,), dtype=torch.float32, device=dy.device)
-            stream = torch.cuda.current_stream(dy.device).cuda_stream
-            _lib.call("dmm_bn_stats_det_grouped_bf16", dy.device, dy.data_ptr(), R, C, 1, ws.data_ptr(), ws.numel(), stream)
-            _lib.call("dmm_bn_fold_det", dy.device, ws.data_ptr(), ws.numel(), R, C, 1, stats.data_ptr(), stream)
-            return stats[:C]
-        stats = _zeroed(2 * C, dy.device)
-        _lib.call("dmm_bn_stats_bf16", dy.device, dy.data_ptr(), B * H * W, C, stats.data_ptr(),
-                  torch.cuda.current_stream(dy.device).cuda_stream)
+            _lib.call("dmm_bn_fold_det", dy.device, *scratch, R, C, 1, stats.data_ptr(), stream)
         return stats[:C]
     return dy.float().sum((0, 2, 3))
 

@@ -706,6 +706,15 @@ DMM_API int dmm_conv1x1_bf16(const void *x, const void *w, const float *bias, co
  * dx = w * invstd * (g - mean(g) - xhat * mean(g * xhat)), dres = g (NULL: no residual branch), dweight = sum(g * xhat),
  * dbias = sum(g).  relu: 0 none; 1 the mask from the output y; 2 (no residual: dres NULL) the mask recomputed from x with the forward's
  * own fma, x * (w * invstd) + (b - mean * w * invstd) > 0 -- weight / bias as the forward saw them; y is then not read at all.
+ * What every entry of (10) and (10a) answers, in this order (where two faults coincide, the earlier one is named):
+ *   1. DMM_ERR_BAD_ARG      rows < 0, C <= 0, groups outside 1..64 or not dividing rows, relu outside 0..2 (the backward
+ *                           entries; the apply entries take relu as a flag, any value other than 0 is a ReLU)
+ *   2. DMM_OK               rows == 0: nothing to do, whatever the pointers and C
+ *   3. DMM_ERR_BAD_ARG      a null pointer the entry cannot do without (stats / sums of the atomic entries among them, the
+ *                           workspace of the deterministic ones not yet), running_mean without running_var or the reverse,
+ *                           relu == 1 without y, relu == 2 without weight / bias (reduce), without bias or with dres (dx)
+ *   4. DMM_ERR_UNSUPPORTED  C % 8 != 0 or 256 % (C / 8) != 0
+ *   5. (10a) only           DMM_ERR_BAD_ARG for a null workspace, then DMM_ERR_WORKSPACE for a short one
  * ------------------------------------------------------------------------------------------- */
 DMM_API int dmm_bn_stats_bf16(const void *x, int64_t rows, int C, float *stats, dmm_stream_t stream);
 DMM_API int dmm_bn_apply_bf16(const void *x, const void *residual, int64_t rows, int C, const float *stats,

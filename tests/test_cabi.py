@@ -220,6 +220,105 @@ def test_count_entries_validate_their_arguments_without_gpu():
                 assert st(planes_t2=False, **kw) == BAD, (entry, kw)
 
 
+# the training BatchNorm entries of include/dmm_match.h (10), (10a) by kind, and the pointers each kind cannot do without at
+# relu = 0 (`stats` / `sums` are the `workspace` of the deterministic forms)
+BN_KINDS = {"stats": "x stats", "apply": "x stats weight bias y saved", "bwd_reduce": "dy x saved sums",
+            "bwd_dx": "dy x saved weight sums dx dweight dbias", "fold": "workspace out"}
+BN_SCALARS = dict(rows=64, C=32, groups=1, relu=0, momentum=0.1, eps=1e-5, workspace_bytes=1 << 20, stream=None)
+STATUS_NAMES = ("DMM_OK", "DMM_ERR_BAD_ARG", "DMM_ERR_UNSUPPORTED", "DMM_ERR_LAUNCH", "DMM_ERR_WORKSPACE")
+
+
+def bn_entries():
+    """{entry: (kind, parameter names in prototype order)} of the 13 BatchNorm entries that answer with a status, read from
+    the header."""
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dmm_match.h")).read(), flags=re.S)
+    out = {}
+    for name, params in re.findall(r"\bDMM_API\s+int\s+(dmm_bn_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", txt):
+        kind = next(k for k in sorted(BN_KINDS, key=len, reverse=True) if name.startswith("dmm_bn_" + k))
+        out[name] = (kind, [re.findall(r"\w+", p)[-1] for p in params.split(",")])
+    return out
+
+
+def bn_fault_rows(kind, params):
+    """{label: overrides} -- every call of one entry that must be answered before a launch: each row carries a fault, or has
+    no rows.  An override of None is a null pointer; every other pointer is the address 8."""
+    det = "workspace" in params
+    have = lambda *names: all(n in params for n in names)
+    slot = {"stats": "workspace", "sums": "workspace"} if det else {}
+    required = [slot.get(p, p) for p in BN_KINDS[kind].split()]
+    pointers = [p for p in params if p not in BN_SCALARS]
+    rows = [dict(rows=-1), dict(rows=0, **dict.fromkeys(pointers)), dict(C=0), dict(C=-8), dict(C=12), dict(C=24), dict(C=4096),
+            dict(rows=0, C=0), dict(rows=0, C=12), dict(rows=-1, C=24)]
+    rows += [{p: None} for p in required] + [{p: None, "C": 24} for p in required]          # a null pointer, alone and with an
+    if have("groups"):                                                                      # unsupported width
+        rows += [dict(groups=0), dict(rows=130, groups=65), dict(groups=3), dict(rows=0, groups=65), dict(groups=3, C=24)]
+    if have("running_mean"):
+        rows += [dict(running_mean=None), dict(running_var=None), dict(relu=3, C=12), dict(relu=-1, C=12)]
+    if kind in ("bwd_reduce", "bwd_dx"):
+        rows += [dict(relu=-1), dict(relu=3), dict(rows=0, relu=3), dict(relu=3, C=24), dict(relu=1, y=None), dict(relu=2, bias=None),
+                 dict(relu=2, weight=None), dict(relu=1, y=None, C=24)]
+    if have("dres"):
+        rows += [dict(relu=2), dict(relu=2, C=24)]                                          # (dres is given)
+    if det:
+        first = [p for p in required if p != "workspace"][-1]                              # an output where the entry has one
+        rows += [dict(workspace_bytes=255), dict(workspace_bytes=0), dict(workspace=None, workspace_bytes=0),
+                 dict(workspace_bytes=255, C=24), {"workspace_bytes": 255, first: None}, {"workspace": None, first: None}]
+    return {",".join(f"{k}={'null' if v is None else v}" for k, v in sorted(r.items())): r for r in rows}
+
+
+def bn_status(L, entry, params, overrides):
+    vals = {p: BN_SCALARS[p] if p in BN_SCALARS else ctypes.c_void_p(8) for p in params}
+    vals.update(overrides)
+    return STATUS_NAMES[getattr(L, entry)(*(vals[p] for p in params))]
+
+
+BN_GRID_TABLE = [(n * g, C, g) for C in (8, 32, 64, 256, 512, 1024, 2048) for g in (1, 3, 64)
+                 for n in (1, 63, 64, 65, 641, 4097, 100000)]
+BN_GRID_REFUSED = [(0, 32, 1), (-64, 32, 1), (64, 32, 0), (130, 32, 65), (64, 32, 3), (64, 0, 1), (64, 12, 1), (64, 24, 1),
+                   (64, 4096, 1)]
+
+
+def bn_entry_golden(L):
+    """What tests/golden/bn_entry_status.json holds, of the library ``L``."""
+    status = {e: {label: bn_status(L, e, params, r) for label, r in bn_fault_rows(kind, params).items()}
+              for e, (kind, params) in sorted(bn_entries().items())}
+    size = {f"{rows},{C},{g}": int(L.dmm_bn_det_workspace_bytes(rows, C, g)) for rows, C, g in BN_GRID_TABLE + BN_GRID_REFUSED}
+    return {"status_values": {n: i for i, n in enumerate(STATUS_NAMES)}, "status": status, "det_workspace_bytes": size}
+
+
+def test_bn_entries_keep_their_statuses_and_grids_without_gpu():
+    """The 13 training-BatchNorm entries' answers to every call they refuse or have nothing to do for -- which status, and
+    which of two coinciding faults is named --, and ``dmm_bn_det_workspace_bytes`` = groups x row groups x 2 C x 4 over a
+    table that pins the statistics grid (its row-group count, the 65536 / C cap, the / groups clamp and its floor at 1).
+    Expected: tests/golden/bn_entry_status.json, recorded with ``bn_entry_golden`` from a build of commit bf10b8c, where
+    each entry spelled its own checks out."""
+    import json
+    if not os.path.exists(_lib.LIB_PATH):
+        _lib.build()
+    L = _lib.load()
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "bn_entry_status.json")))
+    assert want["status_values"] == {n: getattr(_lib, n) for n in STATUS_NAMES}
+    entries = bn_entries()
+    assert len(entries) == 13 and sorted(want["status"]) == sorted(entries)
+    for e, (kind, params) in entries.items():
+        rows = bn_fault_rows(kind, params)
+        assert sorted(rows) == sorted(want["status"][e]), e
+        for label, r in rows.items():
+            # nothing here may launch: an accepted call has no rows, and the pointers are not memory
+            assert want["status"][e][label] in ("DMM_ERR_BAD_ARG", "DMM_ERR_UNSUPPORTED", "DMM_ERR_WORKSPACE") or \
+                (want["status"][e][label] == "DMM_OK" and r.get("rows") == 0), (e, label)
+            assert bn_status(L, e, params, r) == want["status"][e][label], (e, label)
+    size = want["det_workspace_bytes"]
+    assert len(size) == len(BN_GRID_TABLE) + len(BN_GRID_REFUSED) == 156
+    for rows, C, g in BN_GRID_TABLE + BN_GRID_REFUSED:
+        assert int(L.dmm_bn_det_workspace_bytes(rows, C, g)) == size[f"{rows},{C},{g}"], (rows, C, g)
+    for rows, C, g in BN_GRID_TABLE:                                                # (what the size is made of)
+        parts = size[f"{rows},{C},{g}"] // (g * 2 * C * 4)
+        rpp = 256 // min(C // 8, 32)
+        assert parts == max(min(-(-(rows // g) // (8 * rpp)), max(min(65536 // C, 256) // g, 1)), 1), (rows, C, g)
+    assert all(size[f"{rows},{C},{g}"] == 0 for rows, C, g in BN_GRID_REFUSED)
+
+
 def test_training_entries_validate_their_arguments_without_gpu():
     """(5d) / (5e) / (1e): workspace sizes are positive and grow with the batch, null pointers / negative sizes answer
     DMM_ERR_BAD_ARG, tables outside the fast kernels' envelope answer DMM_ERR_UNSUPPORTED (the caller then takes the granular

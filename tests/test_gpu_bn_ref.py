@@ -377,6 +377,56 @@ def test_bn_layer_against_fp64(name, det):
     assert not fails, fails
 
 
+# ---- the deterministic entries, bit for bit -----------------------------------------------------------------------------
+# more than one row group (c256_g1_n65: two); more than one channel tile (C = 512, 2048); groups > 1; 64 groups; the grid's
+# cap / groups clamp binding (bn_ref.CLAMP_CASE)
+DIGEST_CASES = ("c256_g1_n65", "c512_g3_n33", "c2048_g1_n65", "c32_g64_n9", bn_ref.CLAMP_CASE.name)
+
+
+def _sha(t):
+    import hashlib
+    return hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()
+
+
+def bn_det_digests(name):
+    """{launch / output: sha256 of its raw bytes} of every output of the deterministic chain on the case's seeded inputs:
+    stats -> fold, apply (relu x residual, running statistics), reduce -> dx (modes 0, 1, 2 x dy2, with and without dres)."""
+    c, dv = bn_ref.BY_NAME[name], _dev(name)
+    st, nb, tot = _stats(c, dv, True)
+    out = {"stats/slab": _sha(st), "fold/out": _sha(tot)}
+    for relu in (False, True):
+        for res in (None, dv["res"]):
+            o = _apply(c, dv, True, st, nb, relu, res)
+            for k in ("y", "saved", "rm", "rv"):
+                out[f"apply/relu{int(relu)}_res{int(res is not None)}/{k}"] = _sha(getattr(o, k))
+    for mode, relu, has_res in MODES:
+        fwd = _apply(c, dv, True, st, nb, relu, dv["res"] if has_res else None, running=False)
+        for dy2 in (None, dv["dy2"]):
+            tag = f"mode{mode}_dy2{int(dy2 is not None)}"
+            sums, snb, _ = _reduce(c, dv, True, mode, dy2, fwd)
+            out[f"reduce/{tag}/slab"] = _sha(sums)
+            for dres in (False, True) if mode != 2 else (False,):
+                o = _dx(c, dv, True, mode, dy2, fwd, sums, snb, dres=dres)
+                for k in ("dx", "dres", "dw", "db") if dres else ("dx", "dw", "db"):
+                    out[f"dx/{tag}_dres{int(dres)}/{k}"] = _sha(getattr(o, k))
+    return out
+
+
+@pytest.mark.parametrize("name", DIGEST_CASES)
+def test_bn_det_entries_keep_every_output_bit(name):
+    """The ``_det`` kernels are bit-reproducible, so their outputs on fixed inputs are a golden for any change that claims to
+    leave the device code alone: tests/golden/bn_det_digests.json, recorded with ``bn_det_digests`` on an MI355X from a
+    build of commit bf10b8c (twice, with equal digests).  The atomic entries' last bits are order-free: the fp64 tests above
+    hold them."""
+    import json
+    import os
+    from conftest import ROOT
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "bn_det_digests.json")))[name]
+    got = bn_det_digests(name)
+    assert sorted(got) == sorted(want)
+    assert not [k for k in got if got[k] != want[k]]
+
+
 # ---- refusals --------------------------------------------------------------------------------------------------------
 def test_bn_entries_refuse_what_they_do_not_take():
     L = _lib.load()
