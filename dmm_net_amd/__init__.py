@@ -57,6 +57,10 @@ def __getattr__(name):
     if name in ("RSISMask", "RefineStep"):
         from . import decoder
         return getattr(decoder, name)
+    # the fused mask losses (losses.py), lazily too
+    if name in ("softIoULoss", "mask_step_losses"):
+        from . import losses
+        return getattr(losses, name)
     raise AttributeError(f"module 'dmm_net_amd' has no attribute '{name}'")
 
 

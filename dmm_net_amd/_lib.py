@@ -69,7 +69,10 @@ def parse_header(text: str):
 
 try:
     with open(HEADER) as _f:
-        _DECLS, _ENUMS = parse_header(_f.read())
+        _TEXT = _f.read()
+    _DECLS, _ENUMS = parse_header(_TEXT)
+    MASK_LOSS_CHUNK = int(re.search(r"^#define\s+DMM_MASK_LOSS_CHUNK\s+(\d+)", _TEXT, re.M).group(1))   # (13): pixels per workgroup
+    del _TEXT
 except OSError as _e:
     raise DmmError(f"{os.path.normpath(HEADER)} is missing: the C ABI's bindings are read from it ({_e})") from None
 

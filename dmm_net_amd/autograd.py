@@ -376,3 +376,34 @@ def _hungarian_forward(pf, tf, pm, tm, sc, targets, score_weight, is_test):
             gt = matching_loss(pm_b, targets.unsqueeze(0).float(), cos.detach())[1]
         loss = ((cos - gt) ** 2).mean()                              # F.mse_loss(feature_sim, gt_matched) (:48)
     return full, ms, ds, loss
+
+
+class _MaskIoULossFn(torch.autograd.Function):
+    """``ops.mask_iou_loss`` with its closed-form backward (include/dmm_match.h (13)): pred [B,>=n_obj,HW | H,W] fp32 ->
+    (loss, hard_valid, hard_all, cost [B,n_obj], hard [B,n_obj]).  Only ``loss`` carries a gradient, and only to ``pred``
+    (the reference's targets, weights and valid flags are data; its hard IoU is computed under no_grad).  Saved for the
+    backward: the target and the forward's workspace block (the coefficient pair of every row) -- not pred."""
+
+    @staticmethod
+    def forward(ctx, pred, target, sw, valid, n_obj):
+        ctx.set_materialize_grads(False)
+        need = ctx.needs_input_grad[0]
+        loss, hard_valid, hard_all, cost, hard, ws = ops.mask_iou_loss(pred, target, sw, valid, n_obj, keep=need)
+        if need:
+            ctx.save_for_backward(target, ws)
+        ctx.pred_shape, ctx.n_obj = tuple(pred.shape), cost.shape[1]
+        ctx.mark_non_differentiable(hard_valid, hard_all, cost, hard)
+        return loss, hard_valid, hard_all, cost, hard
+
+    @staticmethod
+    def backward(ctx, d_loss, *_unused):
+        if d_loss is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None, None
+        target, ws = ctx.saved_tensors
+        return ops.mask_iou_loss_bwd(target, ws, d_loss, ctx.pred_shape, ctx.n_obj), None, None, None, None
+
+
+def mask_iou_loss(pred, target, sw, valid=None, n_obj=None):
+    """The fused mask loss with autograd -> (loss, hard_valid, hard_all, cost, hard); see ``ops.mask_iou_loss``."""
+    (pred,) = _no_grad_view(pred)
+    return _MaskIoULossFn.apply(pred, target, sw, valid, n_obj)

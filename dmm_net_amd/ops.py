@@ -791,6 +791,66 @@ def match_train_backward(masks_p, feat_p, feat_t, score_p, saved, has_loss, d_fu
     return g_t, g_p
 
 
+def _loss_planes(t: torch.Tensor):
+    """[B,K,HW] or [B,K,H,W] -> (the tensor as the C ABI reads its planes, frame stride, plane stride, K, HW).  What passes
+    ``_plane_rows`` goes in as it is: a ``y_mask[:, :n_obj]`` slice, ``alloc_planes`` strides."""
+    if t.dim() == 3:
+        t = t.unsqueeze(2)
+    t, s_b, s_k = _planes(t)
+    return t, s_b, s_k, t.shape[1], t.shape[2] * t.shape[3]
+
+
+def mask_iou_loss(pred: torch.Tensor, target: torch.Tensor, sw: torch.Tensor, valid=None, n_obj=None, keep: bool = True):
+    """The soft-IoU mask loss of the first ``n_obj`` planes of every frame with the logged hard IoU, two launches and no host
+    read (``dmm_mask_iou_loss_fwd``, include/dmm_match.h (13): objectives.py:25-35 on hungarian.py:62-86, trainer.py:188-196 /
+    :205-206 / :281-300).  pred [B,>=n_obj,HW] or [B,>=n_obj,H,W] fp32 probabilities; target the same with fp32 / fp16 / bf16
+    values; sw [B,>=n_obj] sample weights; valid [B,O] or None (then the two hard scalars are 0); n_obj: target's planes by
+    default.  -> (loss, hard_valid, hard_all: 0-dim; cost [B,n_obj]; hard [B,n_obj]; the workspace block
+    ``mask_iou_loss_bwd`` reads).  ``keep``: the block is the caller's until its backward has run (a fresh tensor); False: no
+    gradient will be asked for, the block is the cached one of (device, stream)."""
+    _need_gpu(pred, target, sw, valid)
+    assert pred.dtype == torch.float32 and target.dtype in _DT, (pred.dtype, target.dtype)
+    pred, sb_p, so_p, Kp, HW = _loss_planes(pred)
+    target, sb_t, so_t, Kt, HW_t = _loss_planes(target)
+    B = pred.shape[0]
+    n_obj = Kt if n_obj is None else int(n_obj)
+    assert target.shape[0] == B and HW_t == HW and 0 < n_obj <= min(Kp, Kt) and B > 0 and HW > 0, (pred.shape, target.shape, n_obj)
+    sw = sw.float()
+    if sw.dim() != 2 or sw.stride(1) != 1:
+        sw = sw.reshape(B, -1).contiguous()
+    assert sw.shape[0] == B and sw.shape[1] >= n_obj, sw.shape
+    O = n_obj
+    if valid is not None:
+        valid = valid.to(torch.int32).contiguous()
+        O = valid.shape[1]
+        assert valid.dim() == 2 and valid.shape[0] == B and O >= n_obj, valid.shape
+    dev = pred.device
+    stream = _stream(pred)
+    need = _need_cached(("ml", B, n_obj, HW), _lib.load().dmm_mask_iou_loss_workspace_bytes, B, n_obj, HW)
+    ws = torch.empty((need,), dtype=torch.uint8, device=dev) if keep else _cached_ws((dev.index, stream, "mask_loss"), need, dev)
+    R = B * n_obj
+    out = torch.empty((3 + 2 * R,), dtype=torch.float32, device=dev)            # scalars | cost | hard: one allocation
+    op = out.data_ptr()
+    _lib.call("dmm_mask_iou_loss_fwd", dev, pred.data_ptr(), sb_p, so_p, target.data_ptr(), _DT[target.dtype], sb_t, so_t,
+              sw.data_ptr(), sw.stride(0), _ptr(valid), B, O, n_obj, HW, op + 12, op + 12 + 4 * R, op, ws.data_ptr(), ws.numel(),
+              stream)
+    return out[0], out[1], out[2], out[3:3 + R].view(B, n_obj), out[3 + R:].view(B, n_obj), ws
+
+
+def mask_iou_loss_bwd(target: torch.Tensor, ws: torch.Tensor, d_loss: torch.Tensor, pred_shape, n_obj: int) -> torch.Tensor:
+    """d loss / d pred of ``mask_iou_loss`` in ``pred_shape``, one launch (``dmm_mask_iou_loss_bwd``): d_loss (0-dim, on the
+    device) times the closed-form gradient for the first ``n_obj`` planes of every frame, zeros for the others.  ``target``
+    and ``ws`` as the forward took and left them."""
+    _need_gpu(target, ws, d_loss)
+    target, sb_t, so_t, _Kt, HW = _loss_planes(target)
+    B, O = int(pred_shape[0]), int(pred_shape[1])
+    d_loss = d_loss.float().contiguous()
+    dpred = torch.empty(tuple(pred_shape), dtype=torch.float32, device=target.device)
+    _lib.call("dmm_mask_iou_loss_bwd", target.device, target.data_ptr(), _DT[target.dtype], sb_t, so_t, d_loss.data_ptr(), B, O,
+              int(n_obj), HW, ws.data_ptr(), ws.numel(), dpred.data_ptr(), O * HW, HW, _stream(target))
+    return dpred
+
+
 def match_forward_packed(masks_p, packed_p, masks_t, feat_p, feat_t, score_p, n_valid, m_valid, *, score_weight, max_iter,
                          proj_iter, lr, is_test, out=None, workspace=None):
     """``match_forward`` with the proposal side of the cost pass on the 1-bit planes ``packed_p`` [B,N,words] the caller

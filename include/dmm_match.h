@@ -854,6 +854,54 @@ DMM_API int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int
 DMM_API int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
                                   int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist, dmm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (13) The soft-IoU mask loss of the trainer's frame step, forward and backward, with the logged hard IoU riding along.
+ * Replaces softIoU (dmm/utils/hungarian.py:62-86, need_sigmoid = 0) under softIoULoss (dmm/utils/objectives.py:25-35) as the
+ * trainer calls it on the matching layer's output (dmm/modules/trainer.py:205-206) and on the refine decoder's
+ * (trainer.py:281-293), together with the hard IoU logged beside each (compute_iou_binary_mask_2D, match_helper.py:9-28, as
+ * called from trainer.py:188-196 and :296-300).  Rows are r = (b, t), b < B, t < n_obj <= O; p = pred (fp32 probabilities),
+ * y = target as a VALUE (not thresholded in the soft part):
+ *   I_r = sum p y      U_r = sum (p + y - p y) + 1e-6      cost_r = 1 - I_r / U_r
+ *   sel_r = ((uint8)sw[b, t] != 0) when any sw[b, t] > 0 (b < B, t < n_obj), else 1 for every row;  K = sum sel_r
+ *   loss = (1 / K) sum sel_r cost_r          (K == 0: NaN, the reference's mean of an empty selection)
+ *   hard_r = float(#(p > 0.5 & y > 0.5)) / (float(#(p > 0.5 | y > 0.5)) + 1e-6)         (strict >, fp32)
+ *   nv = sum valid[b, t] over ALL B * O slots (valid == NULL: nv = 0)
+ *   hard_valid = sum hard_r valid[b, t] / (nv + 1e-6), hard_all = sum hard_r / (nv + 1e-6); both 0 when nv == 0
+ *   d loss / d p[r, i] = sel_r / K * (I_r - (U_r + I_r) y[r, i]) / U_r^2                (nothing else gets a gradient)
+ * "any sw > 0" and "nv == 0" are decided on the device: no host read, both entries are graph capturable.  No float atomics:
+ * every sum has a fixed order (16 pixels per lane in ascending order, the 64-lane tree, waves in order, chunks in ascending
+ * order; the scalars: rows r, r + 256, ... per thread, the 64-lane tree, waves in order), results are bitwise reproducible.
+ *
+ * dmm_mask_iou_loss_fwd -- two launches.  pred: fp32 planes at pred + b * sb_pred + t * so_pred; target: planes of
+ * target_dtype (DMM_F32 / DMM_F16 / DMM_BF16) at strides sb_tgt / so_tgt; a plane is HW contiguous elements, plane strides are
+ * at least HW, rows need no alignment beyond their element's.  sw: float [B, >= n_obj], batch stride sb_sw; valid: int32
+ * [B, O] dense or NULL.  Writes cost [B, n_obj], hard [B, n_obj], scalars[3] = (loss, hard_valid, hard_all) and the
+ * workspace: the coefficient pairs the backward reads, then one 16-byte partial per (row, chunk of DMM_MASK_LOSS_CHUNK
+ * pixels).  workspace: dmm_mask_iou_loss_workspace_bytes(B, n_obj, HW) bytes (0 when any of the three is <= 0), 4-byte aligned.
+ *
+ * dmm_mask_iou_loss_bwd -- one launch.  The SAME workspace after the forward on the same B / n_obj / HW; d_loss: the upstream
+ * gradient of `loss`, one fp32 on the DEVICE.  Writes dpred[b, t] (HW contiguous fp32 at dpred + b * sb_dpred + t * so_dpred)
+ * for every t < O: the gradient for t < n_obj, zeros for n_obj <= t < O (here O = planes per frame of dpred).  The gradient is
+ * evaluated as d_loss * (a_r y + b_r (1 - y)) with the pair a_r = -sel_r / (K U_r), b_r = sel_r I_r / (K U_r^2) -- the formula
+ * above with I_r (1 - y) and U_r y kept apart, so that binary targets select a coefficient instead of cancelling two.
+ *
+ * What both entries answer, in this order (where two faults coincide, the earlier one is named):
+ *   1. DMM_ERR_BAD_ARG      B, O, n_obj or HW negative, n_obj > O, a plane stride below HW or a negative batch stride
+ *   2. DMM_OK               B == 0, HW == 0, n_obj == 0 (forward) or O == 0 (backward): nothing to do, pointers not looked at
+ *   3. DMM_ERR_BAD_ARG      a null pointer other than valid and the workspace
+ *   4. DMM_ERR_UNSUPPORTED  target_dtype is none of the three, or more than 65535 planes (B * O)
+ *   5. DMM_ERR_WORKSPACE    the workspace is null or shorter than dmm_mask_iou_loss_workspace_bytes
+ * ------------------------------------------------------------------------------------------- */
+#define DMM_MASK_LOSS_CHUNK 4096 /* pixels of one row per workgroup of the partials and backward kernels */
+DMM_API size_t dmm_mask_iou_loss_workspace_bytes(int B, int n_obj, int HW);
+DMM_API int dmm_mask_iou_loss_fwd(const float *pred, int64_t sb_pred, int64_t so_pred, const void *target, int target_dtype,
+                                  int64_t sb_tgt, int64_t so_tgt, const float *sw, int64_t sb_sw, const int *valid, int B,
+                                  int O, int n_obj, int HW, float *cost, float *hard, float scalars[3], void *workspace,
+                                  size_t workspace_bytes, dmm_stream_t stream);
+DMM_API int dmm_mask_iou_loss_bwd(const void *target, int target_dtype, int64_t sb_tgt, int64_t so_tgt, const float *d_loss,
+                                  int B, int O, int n_obj, int HW, const void *workspace, size_t workspace_bytes,
+                                  float *dpred, int64_t sb_dpred, int64_t so_dpred, dmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
