@@ -1,4 +1,5 @@
-from .determinism import deterministic, is_deterministic, set_deterministic  # noqa: F401
+from .determinism import (deterministic, get_deterministic_conv, is_deterministic, set_deterministic,  # noqa: F401
+                          set_deterministic_conv)
 
 
 def use_shipped_miopen_db(develop: bool = False, enable: bool = True):

@@ -8,7 +8,11 @@ Off by default.  ``None`` (the default setting) follows torch: the mode is on wh
 In the mode the reductions that add float partials in arrival order (BatchNorm statistics and backward sums, bias gradients,
 the mask-mix backward's dRb, the ROIAlign+mean backward) take their ``_det`` entries (include/dmm_match.h): fixed-order folds
 of per-workgroup slabs and a gather, no float atomics.  The library calls run under ``cudnn.deterministic``; DESIGN.md
-"Deterministic mode" records what that needed and what it costs."""
+"Deterministic mode" records what that needed and what it costs.
+
+``set_deterministic_conv("own")`` takes the mode's 3x3 convolutions (forward and data gradient) off MIOpen -- which answers
+``cudnn.deterministic`` with its naive reference kernel on gfx950 -- and onto ``dmm_conv3x3_bf16``; ``"library"`` (the
+default) leaves every route as it is.  The setting has no effect while the mode is off."""
 from __future__ import annotations
 
 import contextlib
@@ -17,6 +21,7 @@ from typing import Optional
 import torch
 
 _SETTING: Optional[bool] = None
+_CONV: str = "library"
 
 
 def set_deterministic(mode: Optional[bool]) -> None:
@@ -30,6 +35,19 @@ def set_deterministic(mode: Optional[bool]) -> None:
 def get_deterministic_setting() -> Optional[bool]:
     """The explicit setting (None = following torch)."""
     return _SETTING
+
+
+def set_deterministic_conv(which: str) -> None:
+    """Who computes the 3x3 convolutions of a deterministic step: ``"library"`` (MIOpen under cudnn.deterministic, the default)
+    or ``"own"`` (``dmm_conv3x3_bf16`` for every 3x3 / padding 1 convolution with widths that are multiples of 64)."""
+    global _CONV
+    if which not in ("library", "own"):
+        raise ValueError('set_deterministic_conv takes "library" or "own"')
+    _CONV = which
+
+
+def get_deterministic_conv() -> str:
+    return _CONV
 
 
 def is_deterministic() -> bool:

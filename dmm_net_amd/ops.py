@@ -1220,3 +1220,58 @@ class ForwardPlan:
                 self._mix(r, b, e, ms)
                 self._mark("mix", main, False)
         return self.full_outmask, self.match_score, self.det_score
+
+
+# ---- the deterministic mode's own 3x3 convolution (include/dmm_match.h (10d)) -------------------------------------------
+def conv3x3_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, stride: int = 1, *, out=None,
+                 workspace=None) -> torch.Tensor:
+    """3x3 / padding 1 convolution by ``dmm_conv3x3_bf16`` (MFMA implicit GEMM, fp32 accumulation, bias added in fp32, one
+    rounding; deterministic: bit-identical call after call, and an image's result does not depend on its batch).
+    x: [B, ci, H, W] bf16 channels-last; w: [co, ci, 3, 3] bf16 channels-last; bias: bf16 [co] or None -> y [B, co, Ho, Wo]
+    bf16 channels-last.  The data gradient of the convolution is the same call on dy with the flipped, transposed weight
+    (``flip(w, (2, 3)).transpose(0, 1)``; stride 2: on dy spread over zeros to the input's size, at stride 1).
+    ``out`` / ``workspace`` (uint8, >= ``dmm_conv3x3_workspace_bytes``) may be caller-owned; by default both are fresh."""
+    _need_gpu(x, w, bias)
+    cl = torch.channels_last
+    B, ci, H, W = x.shape
+    co = w.shape[0]
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or tuple(w.shape) != (co, ci, 3, 3):
+        raise _lib.DmmError("conv3x3_bf16 takes bf16 x [B, ci, H, W] and w [co, ci, 3, 3]")
+    if ci % 64 or co % 64 or ci <= 0 or co <= 0 or stride not in (1, 2):
+        raise _lib.DmmError(f"conv3x3_bf16: ci = {ci}, co = {co}, stride = {stride} is outside the kernel's envelope")
+    x, w = x.contiguous(memory_format=cl), w.contiguous(memory_format=cl)
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or tuple(bias.shape) != (co,):
+            raise _lib.DmmError("conv3x3_bf16 takes a bf16 bias [co]")
+        bias = bias.contiguous()
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    if out is None:
+        out = torch.empty((B, co, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=cl)
+    elif tuple(out.shape) != (B, co, Ho, Wo) or out.dtype != torch.bfloat16 or not out.is_contiguous(memory_format=cl):
+        raise _lib.DmmError("conv3x3_bf16: out must be bf16 channels-last [B, co, Ho, Wo]")
+    need = _need_cached(("c3", B, H, W, ci, co, stride), _lib.load().dmm_conv3x3_workspace_bytes, B, H, W, ci, co, stride)
+    if workspace is None and need:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=x.device)
+    _lib.call("dmm_conv3x3_bf16", x.device, _ptr(x), _ptr(w), _ptr(bias), B, H, W, ci, co, int(stride), _ptr(out),
+              _ptr(workspace) if need else None, workspace.numel() if need else 0, _stream(x))
+    return out
+
+
+def conv3x3_dgrad_bf16(dy: torch.Tensor, wt: torch.Tensor, in_hw: Tuple[int, int], stride: int = 1) -> torch.Tensor:
+    """The data gradient of ``conv3x3_bf16(x, w, stride=stride)`` for x of ``in_hw`` = (H, W), as a forward convolution:
+    ``wt`` = ``flip(w, (2, 3)).transpose(0, 1)`` ([ci, co, 3, 3] bf16 channels-last; ``dmm_wprep3x3_bf16``'s dstT) applied at
+    stride 1 to dy -- at stride 2 to dy spread over zeros to [B, co, H, W] (``dmm_upsample2_zero_bf16``), which is exact:
+    the taps that meet a zero contribute nothing."""
+    _need_gpu(dy, wt)
+    H, W = int(in_hw[0]), int(in_hw[1])
+    B, co = dy.shape[0], dy.shape[1]
+    if stride not in (1, 2) or tuple(dy.shape[2:]) != ((H - 1) // stride + 1, (W - 1) // stride + 1):
+        raise _lib.DmmError("conv3x3_dgrad_bf16: dy does not belong to an input of in_hw at this stride")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    if stride == 2:
+        if dy.dtype != torch.bfloat16:
+            raise _lib.DmmError("conv3x3_dgrad_bf16 takes a bf16 dy")
+        full = torch.empty((B, co, H, W), dtype=dy.dtype, device=dy.device, memory_format=torch.channels_last)
+        _lib.call("dmm_upsample2_zero_bf16", dy.device, _ptr(dy), B, H, W, co, _ptr(full), _stream(dy))
+        dy = full
+    return conv3x3_bf16(dy, wt, None, 1)

@@ -19,7 +19,8 @@ between):
 * **bf16 activations, channels-last, end to end; fp32 master weights.**  BatchNorm runs on bf16 activations with fp32
   parameters and statistics.  No autocast.
 * **1x1 convolutions are matrix products** of the [B*H*W, Cin] activation matrix (2/3 of a bottleneck): forward and data
-  gradient on hipBLASLt; 3x3 forward / data gradient on MIOpen; EVERY weight gradient from ``dmm_wgrad*_bf16``
+  gradient on hipBLASLt; 3x3 forward / data gradient on MIOpen (in the deterministic mode with
+  ``set_deterministic_conv("own")``: on ``dmm_conv3x3_bf16``, ``csrc/dmm_conv.hip``); EVERY weight gradient from ``dmm_wgrad*_bf16``
   (``csrc/dmm_wgrad.hip``: MFMA, split over the rows, fp32 straight into the master's gradient, no atomics) -- hipBLASLt's pick
   for these products has no split-K (66 us each), MIOpen's bf16 solvers bring a zeroing and a cast launch each.
 * **BatchNorm (+ residual) (+ ReLU) as two launches each way** (``dmm_bn_*`` in ``csrc/dmm_encoder_train.hip``) where the
@@ -50,7 +51,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .determinism import is_deterministic, library_flags
+from .determinism import get_deterministic_conv, is_deterministic, library_flags
 from .encoder import _NO_CTX, Bottleneck, FeatureEncoder, ResNetBody
 from .graphs import CaptureFailed, SafeGraph
 
@@ -127,6 +128,11 @@ class _det_scope:
         global _DET
         _DET = self.old
         return self.flags.__exit__(*exc)
+
+
+def _own_conv_now() -> bool:
+    """The deterministic mode's 3x3 convolutions on ``dmm_conv3x3_bf16`` (``set_deterministic_conv("own")``) instead of MIOpen."""
+    return _det_now() and get_deterministic_conv() == "own"
 
 
 def _det_ws(nbytes: int, device) -> torch.Tensor:
@@ -258,6 +264,8 @@ def _bn_act(x, bn: nn.BatchNorm2d, relu: bool, residual=None, fused: bool = True
 
 # ---- weight gradients: launched where the backward reaches them, or collected for a graph of their own -------------------
 _DGRAD_AS_FORWARD = True                 # (module switch for the A/B in tools/cfg4_probe.py)
+_DET_AS_GEMM = ("forward", "dgrad")     # (module switch for the A/B in tools/cfg4_probe.py: which of _DetConvFn's convolutions
+#                                          are an unfold + one GEMM under set_deterministic_conv("own"))
 _DEFER: Optional[list] = None            # set while a segment's backward is captured with ``overlap_wgrad``: the launches are
 #                                          recorded (operands kept alive) and captured afterwards into a SECOND graph that replays
 #                                          on a side stream beside the next segment's backward chain
@@ -364,7 +372,12 @@ class _Conv1x1Fn(torch.autograd.Function):
 class _Conv3x3Fn(torch.autograd.Function):
     """3x3 / padding 1 convolution (stride 1 or 2) of a channels-last bf16 activation with an fp32 MASTER weight: forward and
     data gradient on MIOpen, the weight gradient by ``dmm_wgrad3x3_bf16`` (implicit patch matrix, MFMA, fp32 out) -- MIOpen's
-    bf16 weight-gradient solvers cost a zeroing and a cast launch each and clear their workspace with a memset node."""
+    bf16 weight-gradient solvers cost a zeroing and a cast launch each and clear their workspace with a memset node.
+
+    ``own`` (the deterministic mode with ``set_deterministic_conv("own")``, resolved in the forward and kept for the backward):
+    forward, bias add and data gradient by ``dmm_conv3x3_bf16`` -- under cudnn.deterministic MIOpen answers with its naive
+    reference kernel.  The data gradient is then ALWAYS the forward convolution of dy with the flipped, transposed weight; at
+    stride 2, of dy spread over zeros to the input's size, at stride 1 (``ops.conv3x3_dgrad_bf16``)."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, shadow=None):
@@ -373,19 +386,25 @@ class _Conv3x3Fn(torch.autograd.Function):
         # kernel for it takes 28 us where its backward-data kernel takes 50 (profiles/r06_kernel_stats_config4_bf16.csv), on
         # the backward's critical chain; the flipped copy is made in the forward, off that chain.
         # shadow = (w, wt): both made for the caller's whole segment in one launch (``TrainEncoder._tick``)
+        own = _own_conv_now()
         if shadow is not None:
             w, wt = shadow
         else:
             w = weight.detach().to(dtype=torch.bfloat16, memory_format=_CL)
             wt = None
-            if _DGRAD_AS_FORWARD and stride == 1 and w.shape[0] == w.shape[1] and x.requires_grad:
-                wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
-        if not (_DGRAD_AS_FORWARD and stride == 1 and w.shape[0] == w.shape[1]):
+        flip = own or (_DGRAD_AS_FORWARD and stride == 1 and w.shape[0] == w.shape[1])
+        if not flip:
             wt = None
+        elif wt is None and x.requires_grad and (own or shadow is None):
+            wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
         b = None if bias is None else bias.detach().to(torch.bfloat16)
-        y = F.conv2d(x, w, b, stride, 1)
+        if own:
+            from . import ops
+            y = ops.conv3x3_bf16(x, w, b, stride)
+        else:
+            y = F.conv2d(x, w, b, stride, 1)
         ctx.save_for_backward(x, w, wt if wt is not None else w)
-        ctx.stride, ctx.has_bias, ctx.flipped, ctx.det = stride, bias is not None, wt is not None, _det_now()
+        ctx.stride, ctx.has_bias, ctx.flipped, ctx.det, ctx.own = stride, bias is not None, wt is not None, _det_now(), own
         return y
 
     @staticmethod
@@ -396,7 +415,10 @@ class _Conv3x3Fn(torch.autograd.Function):
         co = w.shape[0]
         dy = dy.contiguous(memory_format=_CL)
         dx = None
-        if ctx.needs_input_grad[0]:
+        if ctx.needs_input_grad[0] and ctx.own:
+            from . import ops
+            dx = ops.conv3x3_dgrad_bf16(dy, wt, (H, W), ctx.stride)
+        elif ctx.needs_input_grad[0]:
             with library_flags(ctx.det):
                 if ctx.flipped:
                     dx = F.conv2d(dy, wt, None, 1, 1)
@@ -451,6 +473,19 @@ def _conv(x, m: nn.Conv2d, dtype, linear_1x1: bool = True, own_wgrad: bool = Tru
     return F.conv2d(x, w, b, m.stride, m.padding, m.dilation, m.groups)
 
 
+def _conv_as_gemm(x, w, b, stride, padding):
+    """conv2d(x, w, b, stride, padding) of a plain convolution as unfold + one matrix product -> channels-last."""
+    co, ci, kh, kw = w.shape
+    B, _, H, W = x.shape
+    Ho = (H + 2 * padding[0] - kh) // stride[0] + 1
+    Wo = (W + 2 * padding[1] - kw) // stride[1] + 1
+    cols = F.unfold(x, (kh, kw), 1, padding, stride).transpose(1, 2).reshape(B * Ho * Wo, ci * kh * kw)
+    y = torch.mm(cols, w.reshape(co, ci * kh * kw).t())
+    if b is not None:
+        y = y + b
+    return y.view(B, Ho, Wo, co).permute(0, 3, 1, 2)
+
+
 class _DetConvFn(torch.autograd.Function):
     """The stock convolution (7x7 stem, head convolutions outside the own-kernel envelope) in the deterministic mode.  Its
     backward, which autograd runs after the TrainEncoder call has returned, must not reach MIOpen's split-K weight-gradient
@@ -458,12 +493,19 @@ class _DetConvFn(torch.autograd.Function):
     (MIOpen's naive reference kernel on gfx950: ~130 ms per call at config 4).  So: the weight gradient is an unfold + ONE
     GEMM (hipBLASLt), the data gradient of a stride-1 convolution the forward convolution of dy with the flipped, transposed
     weight, the bias gradient a torch reduction -- the convolutions under cudnn.deterministic, like the rest of the mode's
-    library calls."""
+    library calls.
+
+    With ``set_deterministic_conv("own")`` the forward of a plain convolution (no groups, no dilation) and its stride-1 data
+    gradient (the forward convolution of dy) are an unfold + ONE GEMM too, the product the weight gradient already takes: the
+    7x7 stem and the 32-channel heads leave MIOpen's naive kernel (profiles/r08_deterministic_conv.md)."""
 
     @staticmethod
     def forward(ctx, x, w, b, stride, padding, dilation, groups):
         ctx.save_for_backward(x, w)
         ctx.conf = (tuple(stride), tuple(padding), tuple(dilation), groups, b is not None)
+        ctx.own = get_deterministic_conv() == "own"
+        if ctx.own and "forward" in _DET_AS_GEMM and groups == 1 and tuple(dilation) == (1, 1):
+            return _conv_as_gemm(x, w, b, tuple(stride), tuple(padding))
         with library_flags(True):
             return F.conv2d(x, w, b, stride, padding, dilation, groups)
 
@@ -479,8 +521,11 @@ class _DetConvFn(torch.autograd.Function):
         if need[0]:
             if plain and stride == (1, 1) and padding[0] <= kh - 1 and padding[1] <= kw - 1:
                 wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
-                with library_flags(True):
-                    dx = F.conv2d(dy, wt, None, 1, (kh - 1 - padding[0], kw - 1 - padding[1]))
+                if ctx.own and "dgrad" in _DET_AS_GEMM:
+                    dx = _conv_as_gemm(dy, wt, None, (1, 1), (kh - 1 - padding[0], kw - 1 - padding[1]))
+                else:
+                    with library_flags(True):
+                        dx = F.conv2d(dy, wt, None, 1, (kh - 1 - padding[0], kw - 1 - padding[1]))
             else:
                 with library_flags(True):
                     dx = torch.ops.aten.convolution_backward(dy, x, w, None, list(stride), list(padding), list(dilation),
@@ -630,7 +675,8 @@ class TrainEncoder(nn.Module):
         convolution before: 99 launches of ~5.5 us in a ResNet-101 forward."""
         from . import _lib
         memo = self.__dict__.setdefault("_wprep", {})
-        key = tuple(id(m) for m in convs)
+        own = _own_conv_now()                           # every data gradient runs on the flipped weight, whatever the shape
+        key = tuple(id(m) for m in convs) + (own,)
         ptrs = tuple(m.weight.data_ptr() for m in convs)
         got = memo.get(key)
         if got is None or got[0] != ptrs:
@@ -642,7 +688,7 @@ class TrainEncoder(nn.Module):
                 co, ci = m.out_channels, m.in_channels
                 w = torch.empty((co, ci, 3, 3), dtype=torch.bfloat16, device=dev, memory_format=_CL)
                 wt = None
-                if _DGRAD_AS_FORWARD and m.stride == (1, 1) and co == ci:
+                if own or (_DGRAD_AS_FORWARD and m.stride == (1, 1) and co == ci):
                     wt = torch.empty((ci, co, 3, 3), dtype=torch.bfloat16, device=dev, memory_format=_CL)
                 rec += [m.weight.data_ptr(), w.data_ptr(), 0 if wt is None else wt.data_ptr(), co | (ci << 32), tile]
                 tile += (co // 32) * (ci // 32)
@@ -794,7 +840,8 @@ class TrainEncoder(nn.Module):
                 self.__dict__.get("_wcast", {}).clear()
             self.__dict__["_storage"] = fp
         # (the mode is part of the key: a graph captured in one mode never replays in the other)
-        key = (tuple(img.shape), img.dtype, img.device.index, self.skips_need_grad, bn_groups, det)
+        key = (tuple(img.shape), img.dtype, img.device.index, self.skips_need_grad, bn_groups,
+               det and get_deterministic_conv() == "own", det)
         plans = self._plans.setdefault(key, [])
         # a plan's static buffers belong to ONE forward until its backward has run: a second forward of the same shape before
         # that (the trainer's clip: one encoder call per frame, one backward; trainer.py:95-131) takes / captures another plan

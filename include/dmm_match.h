@@ -800,6 +800,24 @@ DMM_API int dmm_wgrad_bf16(const void *dy, const void *x, int64_t rows, int co, 
 DMM_API int dmm_wgrad3x3_bf16(const void *dy, const void *x, int B, int H, int W, int ci, int co, int stride, float *dw,
                               void *workspace, size_t workspace_bytes, dmm_stream_t stream);
 
+/* (10d) 3x3 / padding 1 convolution of the training encoder for the DETERMINISTIC mode (conv2 of the bottlenecks and the 3x3
+ * head convolutions, dmm/modules/vision.py:6-38 and base.py:35-54, as train.py:46 runs them under cudnn.deterministic):
+ *   y[b, ho, wo, co] = bf16( bias[co] + sum_(kh,kw,ci) x[b, s*ho+kh-1, s*wo+kw-1, ci] * w[co, kh, kw, ci] )      (zero outside)
+ * x [B, H, W, ci] and y [B, Ho, Wo, co] dense channels-last bf16, Ho = (H-1)/s + 1, Wo likewise, s in {1, 2}; w the bf16
+ * channels-last weight [co, kh, kw, ci] (what dmm_wprep3x3_bf16 writes as dst); bias bf16 [co] or NULL.  fp32 accumulation, the
+ * bias added in fp32, ONE rounding.  The DATA gradient of such a convolution is the same entry on dy with dmm_wprep3x3_bf16's
+ * dstT (stride 2: on dmm_upsample2_zero_bf16(dy), at stride 1).  Implicit GEMM on MFMA 32x32x16 bf16; no atomics: where the
+ * reduction is split, every split stores its fp32 partial into the caller's workspace and a second launch sums them in order.
+ * The split is a function of (H, W, ci, co, stride) only -- an image's result does not depend on B, on arrival order or on
+ * what else runs -- so results are bit-identical call after call, eagerly and in graph replay (no host reads, no allocation).
+ * workspace: dmm_conv3x3_workspace_bytes(...) bytes (0: none needed, NULL is fine; 0 as well for arguments the entry rejects).
+ * Answers, before any launch: DMM_ERR_BAD_ARG for B < 0, H / W / ci / co <= 0, a stride other than 1 or 2, ci or co not a
+ * multiple of 64; DMM_OK for B == 0; DMM_ERR_BAD_ARG for a null x / w / y, a pointer that is not 16-byte aligned, a needed
+ * workspace that is null or shorter than dmm_conv3x3_workspace_bytes. */
+DMM_API size_t dmm_conv3x3_workspace_bytes(int B, int H, int W, int ci, int co, int stride);
+DMM_API int dmm_conv3x3_bf16(const void *x, const void *w, const void *bias, int B, int H, int W, int ci, int co, int stride,
+                             void *y, void *workspace, size_t workspace_bytes, dmm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * (11) HIP-graph hygiene for captured steps that contain other libraries' launches (MIOpen, hipBLASLt, torch): between the
  * end of a stream capture and hipGraphInstantiate, replace every memset node (flags & 1; element size 1 / 2 / 4) and every

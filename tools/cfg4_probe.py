@@ -4,6 +4,9 @@ its time on MI355X: memory format, dtype policy, who runs the 1x1 convolutions, 
 
     python tools/cfg4_probe.py <variant> [--find] [--steps K]       one variant, one JSON line
         [--deterministic]   the step in dmm_net_amd's deterministic mode (set_deterministic(True))
+        [--det-conv {library,own}]   who runs the mode's 3x3 convolutions (set_deterministic_conv); a train variant with
+                            "nogemmfwd" / "nogemmdx" in its name keeps the forwards / data gradients of the stem and the
+                            32-channel heads on MIOpen under "own"
         [--repeats R]       R timed runs of K steps: ms_per_step_wall is their median, with min / max beside it
     python tools/cfg4_probe.py matrix <outfile>                     every variant in its own process (env differs)
 
@@ -27,8 +30,12 @@ def one(variant, find, steps, frames):
     torch.manual_seed(0)
     torch.backends.cudnn.benchmark = bool(find)
     det = "--deterministic" in sys.argv
+    det_conv = sys.argv[sys.argv.index("--det-conv") + 1] if "--det-conv" in sys.argv else "library"
+    if det_conv not in ("library", "own"):
+        sys.exit("--det-conv takes library or own")
+    import dmm_net_amd
+    dmm_net_amd.set_deterministic_conv(det_conv)
     if det:
-        import dmm_net_amd
         dmm_net_amd.set_deterministic(True)
     enc = FeatureEncoder("resnet101").to(dev).train()
     img = torch.randn(frames, 3, 255, 448, device=dev)
@@ -37,6 +44,7 @@ def one(variant, find, steps, frames):
     if variant.startswith("train"):
         from dmm_net_amd import train_encoder
         train_encoder._DGRAD_AS_FORWARD = "bwddata" not in variant
+        train_encoder._DET_AS_GEMM = tuple(k for k, v in (("forward", "nogemmfwd"), ("dgrad", "nogemmdx")) if v not in variant)
         from dmm_net_amd.train_encoder import TrainEncoder
         enc = TrainEncoder(enc, graphs="nograph" not in variant, linear_1x1="nolin" not in variant,
                            fused_bn="nofuse" not in variant, own_wgrad="nowgrad" not in variant, overlap_wgrad="inline" not in variant, skips_need_grad=False,
@@ -141,7 +149,7 @@ def one(variant, find, steps, frames):
     print(json.dumps({"variant": variant, "find": bool(find), "frames": frames, "clip_calls": clip, "bn_groups": bn_groups,
                       "suggest_nhwc": os.environ.get("PYTORCH_MIOPEN_SUGGEST_NHWC"),
                       "suggest_nhwc_bn": os.environ.get("PYTORCH_MIOPEN_SUGGEST_NHWC_BATCHNORM"),
-                      "deterministic": det, "repeats": repeats,
+                      "deterministic": det, "det_conv": det_conv, "repeats": repeats,
                       "ms_per_step_wall": round(wall, 3), "wall_min_ms": round(min(walls), 3),
                       "wall_max_ms": round(max(walls), 3), "fwd_ms": round(fwd, 3), "bwd_ms": round(bwd, 3),
                       "settle_s": round(settle_s, 1), "loss": float(loss),

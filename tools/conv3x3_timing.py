@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Per-layer time of the deterministic mode's own 3x3 convolution (``ops.conv3x3_bf16`` = dmm_conv3x3_bf16) on the in-envelope
+3x3 shapes of config 4 -- ResNet-101 body and heads at 12 x 3 x 255 x 448 -- beside ``F.conv2d`` with and without
+``cudnn.deterministic``.  HIP-event time per call over a window of launches after a warm-up; FLOP = 2 * B * Ho * Wo * co * 9 *
+ci, so TFLOP/s is the algorithm's work over the call's device time (a call of a split reduction is two launches).
+
+    python tools/conv3x3_timing.py [--frames 12] [--out FILE.json] [--skip-library-det]
+
+Prints a markdown table and one JSON line; needs an MI355X."""
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def shapes(frames):
+    """(ci, co, stride, H, W) -> how many convolutions of a ResNet-101 encoder step have it (forward hooks on one pass)."""
+    import torch
+    import torch.nn as nn
+    from dmm_net_amd.encoder import FeatureEncoder
+    from dmm_net_amd.train_encoder import _wgrad_ok
+    enc = FeatureEncoder("resnet101").to("cuda:0").eval()
+    seen, hooks = {}, []
+
+    def hook(m, inp, out):
+        k = (m.in_channels, m.out_channels, m.stride[0], inp[0].shape[2], inp[0].shape[3])
+        seen[k] = seen.get(k, 0) + 1
+    for m in enc.modules():
+        if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.padding == (1, 1) and _wgrad_ok(m):
+            hooks.append(m.register_forward_hook(hook))
+    with torch.no_grad():
+        enc(torch.randn(frames, 3, 255, 448, device="cuda:0"))
+    for h in hooks:
+        h.remove()
+    del enc
+    torch.cuda.empty_cache()
+    return seen
+
+
+def timed(fn, budget_ms=200.0, max_iters=200):
+    """Device time per call in ms: warm up, size the window from a first call, then one event pair round the window."""
+    import torch
+    for _ in range(2):
+        fn()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    fn()
+    b.record()
+    torch.cuda.synchronize()
+    n = int(max(3, min(max_iters, budget_ms / max(a.elapsed_time(b), 1e-3))))
+    a.record()
+    for _ in range(n):
+        fn()
+    b.record()
+    torch.cuda.synchronize()
+    return a.elapsed_time(b) / n
+
+
+def main():
+    import torch
+    import torch.nn.functional as F
+    from dmm_net_amd import ops
+    if not torch.cuda.is_available():
+        sys.exit("conv3x3_timing needs an MI355X")
+    a = sys.argv[1:]
+    frames = int(a[a.index("--frames") + 1]) if "--frames" in a else 12
+    cl = torch.channels_last
+    rows = []
+    g = torch.Generator(device="cuda:0").manual_seed(0)
+    for (ci, co, stride, H, W), count in sorted(shapes(frames).items(), key=lambda kv: (-kv[0][3], kv[0])):
+        x = torch.randn((frames, ci, H, W), generator=g, device="cuda:0").bfloat16().contiguous(memory_format=cl)
+        w = (torch.randn((co, ci, 3, 3), generator=g, device="cuda:0") / (3 * ci ** 0.5)).bfloat16().contiguous(memory_format=cl)
+        Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+        flop = 2.0 * frames * Ho * Wo * co * 9 * ci
+        own = timed(lambda: ops.conv3x3_bf16(x, w, None, stride))
+        with torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=False):
+            lib = timed(lambda: F.conv2d(x, w, None, stride, 1))
+            same = float((ops.conv3x3_bf16(x, w, None, stride).float() - F.conv2d(x, w, None, stride, 1).float()).abs().max())
+        lib_det = None
+        if "--skip-library-det" not in a:
+            with torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):
+                lib_det = timed(lambda: F.conv2d(x, w, None, stride, 1), budget_ms=60.0, max_iters=20)
+        rows.append({"ci": ci, "co": co, "stride": stride, "H": H, "W": W, "count": count, "gflop": round(flop / 1e9, 3),
+                     "own_ms": round(own, 4), "own_tflops": round(flop / own / 1e9, 1), "library_ms": round(lib, 4),
+                     "library_det_ms": None if lib_det is None else round(lib_det, 4), "max_abs_own_minus_library": same})
+    print("| ci | co | stride | H x W in | per step | GFLOP | own ms | own TFLOP/s | F.conv2d ms | F.conv2d deterministic ms |")
+    print("|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['ci']} | {r['co']} | {r['stride']} | {r['H']} x {r['W']} | {r['count']} | {r['gflop']} | {r['own_ms']} | "
+              f"{r['own_tflops']} | {r['library_ms']} | {r['library_det_ms']} |")
+    tot = lambda k: round(sum(r[k] * r["count"] for r in rows if r[k] is not None), 3)
+    summary = {"frames": frames, "forward_sum_ms": {"own": tot("own_ms"), "library": tot("library_ms"),
+                                                   "library_det": tot("library_det_ms")}, "rows": rows}
+    print(json.dumps(summary), flush=True)
+    if "--out" in a:
+        with open(a[a.index("--out") + 1], "w") as f:
+            json.dump(summary, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
