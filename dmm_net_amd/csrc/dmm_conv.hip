@@ -26,6 +26,9 @@
 // (layer4 at 12 x 255 x 448: 44 tiles); split s stores its fp32 partial tile with plain stores into slab s of the caller's
 // workspace, and a second launch sums the slabs in the order s = 0, 1, ..., adds the bias and rounds.  The number of splits is
 // a function of (H, W, ci, co, stride) -- NOT of the batch -- so an image's result does not depend on the batch it sits in.
+//
+// conv3x3_narrow_kernel (further down, with its own header) is the same product for widths that are multiples of 32 only, at
+// stride 1 and without a split: the 32-channel level-2 heads (dmm_conv3x3_narrow_bf16, include/dmm_match.h (10e)).
 #include "dmm_common.h"
 
 namespace dmm {
@@ -282,6 +285,175 @@ static ConvPlan conv_plan(int H, int W, int ci, int co, int stride) {
     return p;
 }
 
+
+// ---- the NARROW form: widths that are multiples of 32 (the 32-channel level-2 heads), stride 1 ------------------------------
+// Same product, same tile of 128 pixels, same 64-channel stage of 128-byte LDS rows with the same XOR swizzle -- so the
+// conflict argument of the header holds unchanged: a ds_read_b128 is served in groups of 16 lanes (rows {0-3, 12-15, 20-27} or
+// {4-11, 16-19, 28-31} of a fragment, one piece column), whose (row & 1) * 8 + (piece ^ ((row >> 1) & 7)) are 16 different
+// 16-byte columns of the 256-byte bank line; a ds_write_b128 in groups of 8 consecutive lanes = the 8 pieces of ONE row, a
+// permutation of the 8 columns of its 128 bytes.
+//
+// What differs.  (1) TCO = 32 exists: all four waves lie along the pixels, a wave owns ONE 32 x 32 MFMA tile, a thread fetches
+// one weight piece per stage.  (2) A tap holds ci / 32 HALF stages of 32 channels, which may be an odd number, so each half of
+// the 64-channel stage has its own (tap, channel block): half stage n = 2 * stage + half is tap n / (ci / 32), block
+// n % (ci / 32).  A thread's piece column fixes its half (pc >> 2), so it walks its own (kh, kw, block) by two half stages per
+// stage -- additions and carries, no branch.  The weight row [kh, kw, ci] is contiguous over ALL half stages: stage ks still
+// begins at element 64 * ks of the row.  When 9 * ci / 32 is odd the last stage's second half does not exist: its pieces are
+// loaded from a valid address (the tensor's first 64 bytes) and reach LDS as zeros, like a pixel outside the image.
+// No split of the reduction: the narrow shapes sit on the stride-4 / stride-8 levels, where the pixel tiles fill the chip.  The
+// summation order of an output element is a function of (ci, co) alone.
+template <int TCO>
+__global__ __launch_bounds__(256) void conv3x3_narrow_kernel(const uint16_t *__restrict__ x, const uint16_t *__restrict__ w,
+                                                             const uint16_t *__restrict__ bias, uint16_t *__restrict__ y,
+                                                             int H, int W, int Ci, int Co, int64_t M) {
+    constexpr int NI = TCO >= 64 ? 2 : 1;                // channel MFMA tiles per wave
+    constexpr int WCO = TCO / (32 * NI);                 // waves along the channels; 4 / WCO along the pixels
+    constexpr int NJ = WCO;                              // pixel MFMA tiles per wave: 128 / (4 / WCO) / 32
+    constexpr int NA = TCO / 32;                         // weight pieces per thread and stage (pixel pieces: 4)
+    constexpr int STAGE = (TCO + CONV_PX) * CONV_BK;
+    constexpr int OUT_LD = TCO + 8;
+    static_assert(2 * STAGE >= CONV_PX * OUT_LD, "the output image reuses the operand buffers");
+    __shared__ __attribute__((aligned(16))) uint16_t lds_[2 * STAGE];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int r = lane & 31, h = lane >> 5;
+    const int wco = wave % WCO, wpx = wave / WCO;
+    const int64_t m0 = (int64_t)blockIdx.x * CONV_PX;
+    const int co0 = blockIdx.y * TCO;
+    const int nc = Ci / 32;                              // half stages per tap
+    const int halves = 9 * nc;
+    const int stages = (halves + 1) / 2;
+
+    const int pc = t & 7, pr = t >> 3;
+    const int half = pc >> 2, c8 = 8 * (pc & 3);         // this thread's half of a stage, its channels inside the half
+    int64_t pix_base[4];
+    int hs[4], ws[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int64_t m = m0 + pr + 32 * q;
+        const bool in = m < M;
+        const int64_t mm = in ? m : 0;
+        const int64_t qd = mm / W;
+        const int wo = (int)(mm - qd * W);
+        const int b = (int)(qd / H);
+        const int ho = (int)(qd - (int64_t)b * H);
+        hs[q] = in ? ho : -(1 << 20);
+        ws[q] = wo;
+        pix_base[q] = (((int64_t)b * H + ho) * W + wo) * Ci;
+    }
+    int64_t a_off[NA];
+#pragma unroll
+    for (int q = 0; q < NA; ++q) a_off[q] = (int64_t)(co0 + pr + 32 * q) * 9 * Ci + 8 * pc;
+    int hn = half;                                       // the half stage to fetch next, its tap and channel block
+    int tap = half / nc, cc = half - tap * nc;           // (nc == 1: the second half begins at tap 1)
+    int kh = 0, kw = tap;
+
+    u32x4c ra[NA], rb[4];
+    uint32_t okm = 0;                                    // bit q: pixel piece q inside the image; bit 4: the half stage exists
+    auto fetch = [&]() {
+        const bool live = hn < halves;
+        okm = live ? 16u : 0u;
+#pragma unroll
+        for (int q = 0; q < NA; ++q) {
+            ra[q] = *reinterpret_cast<const u32x4c *>(w + (live ? a_off[q] : (int64_t)(8 * pc)));
+            a_off[q] += CONV_BK;
+        }
+        const int dh = kh - 1, dw = kw - 1;
+        const int64_t tap_off = ((int64_t)dh * W + dw) * Ci + cc * 32 + c8;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int hi = hs[q] + dh, wi = ws[q] + dw;
+            const bool in = live && hi >= 0 && hi < H && wi >= 0 && wi < W;
+            rb[q] = *reinterpret_cast<const u32x4c *>(x + (in ? pix_base[q] + tap_off : (int64_t)c8));
+            okm |= in ? (1u << q) : 0u;
+        }
+        hn += 2;
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {                    // two half stages on
+            const int c1 = ++cc == nc;
+            cc = c1 ? 0 : cc;
+            kw += c1;
+            const int c2 = kw == 3;
+            kw = c2 ? 0 : kw;
+            kh += c2;
+        }
+    };
+    auto stash = [&](int buf) {
+        const u32x4c z = {0u, 0u, 0u, 0u};
+        uint16_t *sa = lds_ + buf * STAGE, *sb = sa + TCO * CONV_BK;
+        const bool live = (okm & 16u) != 0u;
+#pragma unroll
+        for (int q = 0; q < NA; ++q) *reinterpret_cast<u32x4c *>(sa + conv_lds_at(pr + 32 * q, pc)) = live ? ra[q] : z;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) *reinterpret_cast<u32x4c *>(sb + conv_lds_at(pr + 32 * q, pc)) = (okm >> q) & 1u ? rb[q] : z;
+    };
+
+    f32x16c acc[NI][NJ];
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.0f;
+
+    fetch();
+    int buf = 0;
+    for (int ks = 0; ks < stages; ++ks) {
+        stash(buf);
+        fetch();
+        __syncthreads();
+        const uint16_t *sa = lds_ + buf * STAGE, *sb = sa + TCO * CONV_BK;
+#pragma unroll
+        for (int kk = 0; kk < CONV_BK / 16; ++kk) {
+            bf16x8c fa[NI], fb[NJ];
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                fa[i] = *reinterpret_cast<const bf16x8c *>(sa + conv_lds_at(wco * (32 * NI) + i * 32 + r, 2 * kk + h));
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                fb[j] = *reinterpret_cast<const bf16x8c *>(sb + conv_lds_at(wpx * (32 * NJ) + j * 32 + r, 2 * kk + h));
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+        }
+        buf ^= 1;
+    }
+
+    // D layout: column (the pixel side) = lane & 31, row (the channel side) = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
+    __syncthreads();                                     // (the last stage's fragment reads are done: the buffers become the image)
+#pragma unroll
+    for (int i = 0; i < NI; ++i)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4) {
+            const int cl = wco * (32 * NI) + i * 32 + 8 * g4 + 4 * h;
+            float bv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (bias) {
+                const u32x2c bb = *reinterpret_cast<const u32x2c *>(bias + co0 + cl);
+                bv[0] = __uint_as_float(bb[0] << 16);
+                bv[1] = __uint_as_float(bb[0] & 0xFFFF0000u);
+                bv[2] = __uint_as_float(bb[1] << 16);
+                bv[3] = __uint_as_float(bb[1] & 0xFFFF0000u);
+            }
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int pl = wpx * (32 * NJ) + j * 32 + r;
+                u32x2c o;
+                o[0] = conv_bf16_rne(acc[i][j][4 * g4] + bv[0]) | (conv_bf16_rne(acc[i][j][4 * g4 + 1] + bv[1]) << 16);
+                o[1] = conv_bf16_rne(acc[i][j][4 * g4 + 2] + bv[2]) | (conv_bf16_rne(acc[i][j][4 * g4 + 3] + bv[3]) << 16);
+                *reinterpret_cast<u32x2c *>(lds_ + pl * OUT_LD + cl) = o;
+            }
+        }
+    __syncthreads();
+    constexpr int PR = TCO / 8;                          // 16-byte pieces per output row
+#pragma unroll
+    for (int n = 0; n < CONV_PX * PR / 256; ++n) {
+        const int idx = t + 256 * n, pl = idx / PR, p8 = idx % PR;
+        const int64_t m = m0 + pl;
+        if (m < M)
+            *reinterpret_cast<u32x4c *>(y + m * Co + co0 + 8 * p8) = *reinterpret_cast<const u32x4c *>(lds_ + pl * OUT_LD + 8 * p8);
+    }
+}
+
 }  // namespace dmm
 
 extern "C" size_t dmm_conv3x3_workspace_bytes(int B, int H, int W, int ci, int co, int stride) {
@@ -328,5 +500,29 @@ extern "C" int dmm_conv3x3_bf16(const void *x, const void *w, const void *bias, 
     const int64_t n = g.M * co;
     hipLaunchKernelGGL(dmm::conv3x3_fold_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, (const float *)workspace,
                        p.splits, n, bp, co, (uint16_t *)y);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_conv3x3_narrow_bf16(const void *x, const void *w, const void *bias, int B, int H, int W, int ci, int co,
+                                       void *y, dmm_stream_t stream) {
+    if (B < 0 || H <= 0 || W <= 0 || ci <= 0 || co <= 0) return DMM_ERR_BAD_ARG;
+    if ((ci & 31) || (co & 31)) return DMM_ERR_BAD_ARG;
+    if (B == 0) return DMM_OK;
+    if (!x || !w || !y) return DMM_ERR_BAD_ARG;
+    if (((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)y & 15) || ((uintptr_t)bias & 15)) return DMM_ERR_BAD_ARG;
+    const int64_t M = (int64_t)B * H * W;
+    const int64_t tiles = (M + dmm::CONV_PX - 1) / dmm::CONV_PX;
+    if (tiles > 0x7fffffffLL) return DMM_ERR_BAD_ARG;
+    // the channel tile: from co alone (with ci it fixes an element's summation order)
+    const int tco = (co & 127) == 0 ? 128 : (co & 63) == 0 ? 64 : 32;
+    const dim3 grid((unsigned)tiles, (unsigned)(co / tco));
+    const uint16_t *xp = (const uint16_t *)x, *wp = (const uint16_t *)w, *bp = (const uint16_t *)bias;
+    hipStream_t s = (hipStream_t)stream;
+    if (tco == 128)
+        hipLaunchKernelGGL((dmm::conv3x3_narrow_kernel<128>), grid, dim3(256), 0, s, xp, wp, bp, (uint16_t *)y, H, W, ci, co, M);
+    else if (tco == 64)
+        hipLaunchKernelGGL((dmm::conv3x3_narrow_kernel<64>), grid, dim3(256), 0, s, xp, wp, bp, (uint16_t *)y, H, W, ci, co, M);
+    else
+        hipLaunchKernelGGL((dmm::conv3x3_narrow_kernel<32>), grid, dim3(256), 0, s, xp, wp, bp, (uint16_t *)y, H, W, ci, co, M);
     return dmm::check_launch();
 }

@@ -703,6 +703,128 @@ static int wgrad_launch(const void *dy, const void *x, int64_t R, int Co, int Cv
     return check_launch();
 }
 
+
+// ---- the NARROW 3x3 form: widths that are multiples of 32 (the 32-channel level-2 heads), stride 1 ---------------------------
+// wgrad_bf16_kernel<true> with two changes.  (1) The tap is decided per LANE: lane i owns the virtual columns cv0 + 2i, 2i + 1
+// (a channel pair never straddles a tap: Ci is even), so a 64-wide tile of virtual columns may span two taps of a 32-channel
+// input.  (2) The tiles are counted with ceilings: a lane whose output channel is >= Co or whose virtual column is >= 9 * Ci
+// loads nothing, contributes zero fragments, and its part of the tile is not stored.  Memory bound like its model, so the
+// half-empty tiles at Co = 32 cost nothing that shows.  The ordered fold and the [co, ci, 3, 3] layout are
+// wgrad_reduce_kernel<S, true>'s.
+__global__ __launch_bounds__(256) void wgrad3x3_narrow_kernel(const uint16_t *__restrict__ dy, const uint16_t *__restrict__ x,
+                                                              int64_t R, int Co, int Cv, float *__restrict__ out,
+                                                              int64_t group_stride, int64_t rows_per_wave, int cv_tiles,
+                                                              int H, int W, int Ci) {
+    __shared__ __attribute__((aligned(16))) float tile_s[64 * 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int i = lane & 31, g = lane >> 5;
+    const int tile = blockIdx.x;
+    const int co0 = (tile / cv_tiles) * 64, cv0 = (tile % cv_tiles) * 64;
+    const int64_t slab = (int64_t)blockIdx.y * 4 + wave;
+    const int64_t r0 = slab * rows_per_wave;
+    int64_t r1 = r0 + rows_per_wave;
+    if (r1 > R) r1 = R;
+    const bool a_in = co0 + 2 * i < Co, b_in = cv0 + 2 * i < Cv;
+    const int vcol = b_in ? cv0 + 2 * i : 0;
+    const int tap = vcol / Ci, cin = vcol - tap * Ci;
+    const int tap_dh = tap / 3 - 1, tap_dw = tap % 3 - 1;
+    const uint16_t *ap = dy + (a_in ? co0 + 2 * i : 0);
+    const uint16_t *bp = x + cin;
+    f32x16w acc00, acc01, acc10, acc11;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) acc00[k] = acc01[k] = acc10[k] = acc11[k] = 0.0f;
+    for (int64_t r = r0; r < r1; r += 16) {              // (a wave whose slab starts beyond R runs no step: zeros)
+        uint32_t wa[8], wb[8];
+        const int64_t rb = r + 8 * g;
+        const int64_t q = rb / W;                          // (b, h, w) of the lane's first row, then incremented
+        int pw = (int)(rb - q * W);
+        int pb = (int)(q / H);
+        int ph = (int)(q - (int64_t)pb * H);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t row = rb + j;
+            const bool ok = row < r1;
+            wa[j] = ok && a_in ? *reinterpret_cast<const uint32_t *>(ap + row * Co) : 0u;
+            const int hi = ph + tap_dh, wi = pw + tap_dw;
+            const bool in = ok && b_in && hi >= 0 && hi < H && wi >= 0 && wi < W;
+            wb[j] = in ? *reinterpret_cast<const uint32_t *>(bp + (((int64_t)pb * H + hi) * W + wi) * Ci) : 0u;
+            if (++pw == W) {
+                pw = 0;
+                if (++ph == H) { ph = 0; ++pb; }
+            }
+        }
+        u32x4w a0, a1, b0, b1;
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            a0[p] = pair_lo(wa[2 * p], wa[2 * p + 1]);
+            a1[p] = pair_hi(wa[2 * p], wa[2 * p + 1]);
+            b0[p] = pair_lo(wb[2 * p], wb[2 * p + 1]);
+            b1[p] = pair_hi(wb[2 * p], wb[2 * p + 1]);
+        }
+        const bf16x8w fa0 = __builtin_bit_cast(bf16x8w, a0), fa1 = __builtin_bit_cast(bf16x8w, a1);
+        const bf16x8w fb0 = __builtin_bit_cast(bf16x8w, b0), fb1 = __builtin_bit_cast(bf16x8w, b1);
+        acc00 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb0, acc00, 0, 0, 0);
+        acc01 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa0, fb1, acc01, 0, 0, 0);
+        acc10 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb0, acc10, 0, 0, 0);
+        acc11 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa1, fb1, acc11, 0, 0, 0);
+    }
+    // fold the four waves in a FIXED order through one 16 KB LDS tile, as wgrad_bf16_kernel does
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int m = (reg & 3) + 8 * (reg >> 2) + 4 * g;
+                float2 *t0 = reinterpret_cast<float2 *>(&tile_s[(2 * m) * 64 + 2 * i]);
+                float2 *t1 = reinterpret_cast<float2 *>(&tile_s[(2 * m + 1) * 64 + 2 * i]);
+                float2 v0 = make_float2(acc00[reg], acc01[reg]), v1 = make_float2(acc10[reg], acc11[reg]);
+                if (w > 0) {
+                    const float2 p0 = *t0, p1 = *t1;
+                    v0.x += p0.x; v0.y += p0.y; v1.x += p1.x; v1.y += p1.y;
+                }
+                *t0 = v0;
+                *t1 = v1;
+            }
+        }
+        __syncthreads();
+    }
+    float *o = out + (int64_t)blockIdx.y * group_stride;
+    const int row = threadIdx.x >> 2, c4 = (threadIdx.x & 3) * 16;
+    if (co0 + row >= Co) return;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (cv0 + c4 + 4 * k < Cv)                         // (Cv is a multiple of 32: a float4 lies inside or outside)
+            *reinterpret_cast<float4 *>(o + (int64_t)(co0 + row) * Cv + cv0 + c4 + 4 * k) =
+                *reinterpret_cast<const float4 *>(&tile_s[row * 64 + c4 + 4 * k]);
+}
+
+struct NarrowPlan {
+    int64_t rows_per_wave, groups, tiles;
+    int cv_tiles;
+};
+
+// wgrad_plan's 64-wide branch with the tiles counted by ceilings: ~2048 waves per launch, >= 8 steps of 16 rows per wave,
+// partial tables of <= ~16 MB in all; 4 slabs = 1 group
+static NarrowPlan wgrad_narrow_plan(int64_t R, int Co, int Cv) {
+    NarrowPlan p;
+    p.cv_tiles = (Cv + 63) / 64;
+    p.tiles = (int64_t)((Co + 63) / 64) * p.cv_tiles;
+    int64_t slabs = (2048 + p.tiles - 1) / p.tiles;
+    const int64_t by_rows = (R + 127) / 128;
+    if (slabs > by_rows) slabs = by_rows;
+    int64_t groups = (slabs + 3) / 4;
+    const int64_t by_bytes = (4LL << 20) / ((int64_t)Co * Cv);
+    if (groups > by_bytes) groups = by_bytes;
+    if (groups < 1) groups = 1;
+    const int64_t rpw = (R + groups * 4 - 1) / (groups * 4);
+    p.rows_per_wave = (rpw + 15) / 16 * 16;
+    p.groups = (R + p.rows_per_wave * 4 - 1) / (p.rows_per_wave * 4);
+    return p;
+}
+
+static bool wgrad_narrow_sizes_ok(int B, int H, int W, int ci, int co) {
+    return B >= 0 && H > 0 && W > 0 && ci > 0 && co > 0 && !(ci & 31) && !(co & 31);
+}
+
 }  // namespace dmm
 
 extern "C" size_t dmm_wgrad_workspace_bytes(int64_t rows, int co, int cv) {
@@ -742,4 +864,50 @@ extern "C" int dmm_wgrad3x3_bf16(const void *dy, const void *x, int B, int H, in
     pg.Wo = (W - 1) / stride + 1;
     const int64_t R = (int64_t)B * pg.Ho * pg.Wo;
     return dmm::wgrad_launch(dy, x, R, co, 9 * ci, co, ci, dw, workspace, workspace_bytes, true, pg, (hipStream_t)stream);
+}
+
+extern "C" size_t dmm_wgrad3x3_narrow_workspace_bytes(int B, int H, int W, int ci, int co) {
+    if (B <= 0 || !dmm::wgrad_narrow_sizes_ok(B, H, W, ci, co)) return 0;
+    const dmm::NarrowPlan p = dmm::wgrad_narrow_plan((int64_t)B * H * W, co, 9 * ci);
+    if (p.tiles > 0x7fffffffLL || p.groups > 65535) return 0;
+    return sizeof(float) * (size_t)(p.groups * (int64_t)co * 9 * ci);
+}
+
+extern "C" int dmm_wgrad3x3_narrow_bf16(const void *dy, const void *x, int B, int H, int W, int ci, int co, float *dw,
+                                        void *workspace, size_t workspace_bytes, dmm_stream_t stream) {
+    if (!dmm::wgrad_narrow_sizes_ok(B, H, W, ci, co)) return DMM_ERR_BAD_ARG;
+    if (!dw || ((uintptr_t)dw & 3)) return DMM_ERR_BAD_ARG;
+    if (B == 0) {
+        DMM_HIP_TRY(dmm::zero_async(dw, sizeof(float) * (size_t)co * 9 * ci, (hipStream_t)stream));
+        return DMM_OK;
+    }
+    if (!dy || !x || ((uintptr_t)dy & 3) || ((uintptr_t)x & 3)) return DMM_ERR_BAD_ARG;       // (dword loads of channel pairs)
+    const int64_t R = (int64_t)B * H * W;
+    const int Cv = 9 * ci;
+    const dmm::NarrowPlan p = dmm::wgrad_narrow_plan(R, co, Cv);
+    if (p.tiles > 0x7fffffffLL || p.groups > 65535) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)co * Cv;
+    if (!workspace || workspace_bytes < sizeof(float) * (size_t)(p.groups * n)) return DMM_ERR_WORKSPACE;
+    if ((uintptr_t)workspace & 15) return DMM_ERR_BAD_ARG;                                     // (float4 stores)
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(dmm::wgrad3x3_narrow_kernel, dim3((unsigned)p.tiles, (unsigned)p.groups), dim3(256), 0, s,
+                       (const uint16_t *)dy, (const uint16_t *)x, R, co, Cv, (float *)workspace, n, p.rows_per_wave, p.cv_tiles,
+                       H, W, ci);
+    int rc = dmm::check_launch();
+    if (rc != DMM_OK) return rc;
+    const int64_t outs = n / 9;
+    int S = 1;
+    while (S < 16 && 2 * S <= p.groups && outs * S < 256 * 1024) S *= 2;
+#define DMM_WRED9(S_)                                                                                                           \
+    hipLaunchKernelGGL((dmm::wgrad_reduce_kernel<S_, true>), dim3((unsigned)((outs + 256 / S_ - 1) / (256 / S_))), dim3(256), 0, \
+                       s, (const float *)workspace, (int)p.groups, n, Cv, ci, dw)
+    switch (S) {
+        case 1: DMM_WRED9(1); break;
+        case 2: DMM_WRED9(2); break;
+        case 4: DMM_WRED9(4); break;
+        case 8: DMM_WRED9(8); break;
+        default: DMM_WRED9(16); break;
+    }
+#undef DMM_WRED9
+    return dmm::check_launch();
 }

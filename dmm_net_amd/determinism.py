@@ -12,7 +12,10 @@ of per-workgroup slabs and a gather, no float atomics.  The library calls run un
 
 ``set_deterministic_conv("own")`` takes the mode's 3x3 convolutions (forward and data gradient) off MIOpen -- which answers
 ``cudnn.deterministic`` with its naive reference kernel on gfx950 -- and onto ``dmm_conv3x3_bf16``; ``"library"`` (the
-default) leaves every route as it is.  The setting has no effect while the mode is off."""
+default) leaves every route as it is.  ``"own_all"`` is ``"own"`` plus the narrow 3x3 convolutions (stride 1, widths that
+are multiples of 32 but not of 64: the 32-channel level-2 heads), which ``"own"`` runs as unfold + GEMM: forward and data
+gradient on ``dmm_conv3x3_narrow_bf16``, the weight gradient on ``dmm_wgrad3x3_narrow_bf16``.  The setting has no effect while
+the mode is off."""
 from __future__ import annotations
 
 import contextlib
@@ -38,11 +41,13 @@ def get_deterministic_setting() -> Optional[bool]:
 
 
 def set_deterministic_conv(which: str) -> None:
-    """Who computes the 3x3 convolutions of a deterministic step: ``"library"`` (MIOpen under cudnn.deterministic, the default)
-    or ``"own"`` (``dmm_conv3x3_bf16`` for every 3x3 / padding 1 convolution with widths that are multiples of 64)."""
+    """Who computes the 3x3 convolutions of a deterministic step: ``"library"`` (MIOpen under cudnn.deterministic, the default),
+    ``"own"`` (``dmm_conv3x3_bf16`` for every 3x3 / padding 1 convolution with widths that are multiples of 64) or
+    ``"own_all"`` (``"own"``, and ``dmm_conv3x3_narrow_bf16`` / ``dmm_wgrad3x3_narrow_bf16`` for the stride-1 ones whose widths
+    are multiples of 32 only)."""
     global _CONV
-    if which not in ("library", "own"):
-        raise ValueError('set_deterministic_conv takes "library" or "own"')
+    if not isinstance(which, str) or which not in ("library", "own", "own_all"):
+        raise ValueError('set_deterministic_conv takes "library", "own" or "own_all"')
     _CONV = which
 
 

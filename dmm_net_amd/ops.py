@@ -1275,3 +1275,67 @@ def conv3x3_dgrad_bf16(dy: torch.Tensor, wt: torch.Tensor, in_hw: Tuple[int, int
         _lib.call("dmm_upsample2_zero_bf16", dy.device, _ptr(dy), B, H, W, co, _ptr(full), _stream(dy))
         dy = full
     return conv3x3_bf16(dy, wt, None, 1)
+
+
+# ---- the narrow 3x3 convolutions of the deterministic mode (include/dmm_match.h (10e)) -----------------------------------
+def conv3x3_narrow_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, out=None) -> torch.Tensor:
+    """3x3 / padding 1 / stride 1 convolution by ``dmm_conv3x3_narrow_bf16`` for widths that are multiples of 32 (MFMA implicit
+    GEMM, fp32 accumulation, bias added in fp32, one rounding; no split of the reduction and no workspace; deterministic:
+    bit-identical call after call, and an image's result does not depend on its batch).
+    x: [B, ci, H, W] bf16 channels-last; w: [co, ci, 3, 3] bf16 channels-last; bias: bf16 [co] or None -> y [B, co, H, W] bf16
+    channels-last.  ``out`` may be caller-owned; by default it is fresh."""
+    _need_gpu(x, w, bias)
+    cl = torch.channels_last
+    if x.dim() != 4 or w.dim() != 4:
+        raise _lib.DmmError("conv3x3_narrow_bf16 takes bf16 x [B, ci, H, W] and w [co, ci, 3, 3]")
+    B, ci, H, W = x.shape
+    co = w.shape[0]
+    if x.dtype != torch.bfloat16 or w.dtype != torch.bfloat16 or tuple(w.shape) != (co, ci, 3, 3):
+        raise _lib.DmmError("conv3x3_narrow_bf16 takes bf16 x [B, ci, H, W] and w [co, ci, 3, 3]")
+    if ci % 32 or co % 32 or ci <= 0 or co <= 0:
+        raise _lib.DmmError(f"conv3x3_narrow_bf16: ci = {ci}, co = {co} is outside the kernel's envelope")
+    x, w = x.contiguous(memory_format=cl), w.contiguous(memory_format=cl)
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or tuple(bias.shape) != (co,):
+            raise _lib.DmmError("conv3x3_narrow_bf16 takes a bf16 bias [co]")
+        bias = bias.contiguous()
+    if out is None:
+        out = torch.empty((B, co, H, W), dtype=torch.bfloat16, device=x.device, memory_format=cl)
+    elif tuple(out.shape) != (B, co, H, W) or out.dtype != torch.bfloat16 or not out.is_contiguous(memory_format=cl):
+        raise _lib.DmmError("conv3x3_narrow_bf16: out must be bf16 channels-last [B, co, H, W]")
+    _lib.call("dmm_conv3x3_narrow_bf16", x.device, _ptr(x), _ptr(w), _ptr(bias), B, H, W, ci, co, _ptr(out), _stream(x))
+    return out
+
+
+def conv3x3_narrow_dgrad_bf16(dy: torch.Tensor, wt: torch.Tensor) -> torch.Tensor:
+    """The data gradient of ``conv3x3_narrow_bf16(x, w)`` as a forward convolution: at stride 1 / padding 1,
+    dx[b, ci, h, w] = sum dy[b, co, h - kh + 1, w - kw + 1] * w[co, ci, kh, kw] is the same 3x3 / padding 1 convolution of dy
+    with ``wt`` = ``flip(w, (2, 3)).transpose(0, 1)`` ([ci, co, 3, 3] bf16 channels-last; ``dmm_wprep3x3_bf16``'s dstT)."""
+    return conv3x3_narrow_bf16(dy, wt, None)
+
+
+def wgrad3x3_narrow_bf16(dy: torch.Tensor, x: torch.Tensor, *, out=None, workspace=None) -> torch.Tensor:
+    """The weight gradient of ``conv3x3_narrow_bf16(x, w)`` by ``dmm_wgrad3x3_narrow_bf16``: dy [B, co, H, W] and x [B, ci, H, W]
+    bf16 channels-last, widths multiples of 32 -> fp32 [co, ci, 3, 3] (the parameter's own layout), overwritten; implicit patch
+    matrix, row slabs folded in a fixed order, no atomics.  ``out`` / ``workspace`` (uint8, >=
+    ``dmm_wgrad3x3_narrow_workspace_bytes``) may be caller-owned; by default both are fresh."""
+    _need_gpu(dy, x)
+    cl = torch.channels_last
+    if dy.dim() != 4 or x.dim() != 4 or dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 \
+            or dy.shape[0] != x.shape[0] or tuple(dy.shape[2:]) != tuple(x.shape[2:]):
+        raise _lib.DmmError("wgrad3x3_narrow_bf16 takes bf16 dy [B, co, H, W] and x [B, ci, H, W]")
+    B, ci, H, W = x.shape
+    co = dy.shape[1]
+    if ci % 32 or co % 32 or ci <= 0 or co <= 0:
+        raise _lib.DmmError(f"wgrad3x3_narrow_bf16: ci = {ci}, co = {co} is outside the kernel's envelope")
+    dy, x = dy.contiguous(memory_format=cl), x.contiguous(memory_format=cl)
+    if out is None:
+        out = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (co, ci, 3, 3) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.DmmError("wgrad3x3_narrow_bf16: out must be fp32 contiguous [co, ci, 3, 3]")
+    need = _need_cached(("w3n", B, H, W, ci, co), _lib.load().dmm_wgrad3x3_narrow_workspace_bytes, B, H, W, ci, co)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=x.device)
+    _lib.call("dmm_wgrad3x3_narrow_bf16", x.device, _ptr(dy), _ptr(x), B, H, W, ci, co, _ptr(out), _ptr(workspace),
+              workspace.numel(), _stream(x))
+    return out

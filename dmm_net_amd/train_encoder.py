@@ -20,7 +20,8 @@ between):
   parameters and statistics.  No autocast.
 * **1x1 convolutions are matrix products** of the [B*H*W, Cin] activation matrix (2/3 of a bottleneck): forward and data
   gradient on hipBLASLt; 3x3 forward / data gradient on MIOpen (in the deterministic mode with
-  ``set_deterministic_conv("own")``: on ``dmm_conv3x3_bf16``, ``csrc/dmm_conv.hip``); EVERY weight gradient from ``dmm_wgrad*_bf16``
+  ``set_deterministic_conv("own")``: on ``dmm_conv3x3_bf16``, ``csrc/dmm_conv.hip``; with ``"own_all"`` the 32-channel heads
+  too, on ``dmm_conv3x3_narrow_bf16`` / ``dmm_wgrad3x3_narrow_bf16``); EVERY weight gradient from ``dmm_wgrad*_bf16``
   (``csrc/dmm_wgrad.hip``: MFMA, split over the rows, fp32 straight into the master's gradient, no atomics) -- hipBLASLt's pick
   for these products has no split-K (66 us each), MIOpen's bf16 solvers bring a zeroing and a cast launch each.
 * **BatchNorm (+ residual) (+ ReLU) as two launches each way** (``dmm_bn_*`` in ``csrc/dmm_encoder_train.hip``) where the
@@ -131,8 +132,15 @@ class _det_scope:
 
 
 def _own_conv_now() -> bool:
-    """The deterministic mode's 3x3 convolutions on ``dmm_conv3x3_bf16`` (``set_deterministic_conv("own")``) instead of MIOpen."""
-    return _det_now() and get_deterministic_conv() == "own"
+    """The deterministic mode's 3x3 convolutions on ``dmm_conv3x3_bf16`` (``set_deterministic_conv("own")`` / ``"own_all"``)
+    instead of MIOpen."""
+    return _det_now() and get_deterministic_conv() in ("own", "own_all")
+
+
+def _narrow_conv_now() -> bool:
+    """The deterministic mode's NARROW 3x3 convolutions (``_narrow_ok``) on ``dmm_conv3x3_narrow_bf16`` /
+    ``dmm_wgrad3x3_narrow_bf16`` (``set_deterministic_conv("own_all")``) instead of unfold + GEMM."""
+    return _det_now() and get_deterministic_conv() == "own_all"
 
 
 def _det_ws(nbytes: int, device) -> torch.Tensor:
@@ -282,6 +290,11 @@ def _wgrad_launch(rec):
         ws = torch.empty((max(int(L.dmm_wgrad_workspace_bytes(rows, co, ci)), 16),), dtype=torch.uint8, device=dev)
         _lib.call("dmm_wgrad_bf16", dev, dy.data_ptr(), x.data_ptr(), rows, co, ci, co, ci, dw.data_ptr(), ws.data_ptr(),
                   ws.numel(), stream)
+    elif kind == "3x3n":
+        B, H, W, ci, co = dims
+        ws = torch.empty((max(int(L.dmm_wgrad3x3_narrow_workspace_bytes(B, H, W, ci, co)), 16),), dtype=torch.uint8, device=dev)
+        _lib.call("dmm_wgrad3x3_narrow_bf16", dev, dy.data_ptr(), x.data_ptr(), B, H, W, ci, co, dw.data_ptr(), ws.data_ptr(),
+                  ws.numel(), stream)
     else:
         B, H, W, ci, co, stride, Ho, Wo = dims
         ws = torch.empty((max(int(L.dmm_wgrad_workspace_bytes(B * Ho * Wo, co, 9 * ci)), 16),), dtype=torch.uint8, device=dev)
@@ -300,6 +313,13 @@ def _wgrad(rec):
 def _wgrad_ok(m: nn.Conv2d) -> bool:
     return (m.groups == 1 and m.dilation == (1, 1) and m.in_channels % 64 == 0 and m.out_channels % 64 == 0
             and m.stride in ((1, 1), (2, 2)))
+
+
+def _narrow_ok(m: nn.Conv2d) -> bool:
+    """A 3x3 / padding 1 / stride 1 convolution whose widths are multiples of 32 and that ``_wgrad_ok`` does not take (one of
+    them is no multiple of 64): the 32-channel level-2 heads."""
+    return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.stride == (1, 1) and m.groups == 1 and m.dilation == (1, 1)
+            and m.in_channels % 32 == 0 and m.out_channels % 32 == 0 and not _wgrad_ok(m))
 
 
 def _subsample(x, stride: int):
@@ -432,6 +452,48 @@ class _Conv3x3Fn(torch.autograd.Function):
         return dx, dw, db, None, None
 
 
+class _ConvNarrowFn(torch.autograd.Function):
+    """A narrow 3x3 / padding 1 / stride 1 convolution (``_narrow_ok``) of a channels-last bf16 activation with an fp32 MASTER
+    weight in the deterministic mode under ``set_deterministic_conv("own_all")`` (resolved by ``_conv`` in the forward; the
+    backward needs no setting): forward, bias add and data gradient by ``dmm_conv3x3_narrow_bf16`` -- the data gradient is the
+    forward convolution of dy with the flipped, transposed weight --, the weight gradient by ``dmm_wgrad3x3_narrow_bf16``
+    (deferred and captured like the others), the bias gradient by the deterministic statistics kernel."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, shadow=None):
+        from . import ops
+        # shadow = (w, wt): both made for the caller's whole segment in one launch (``TrainEncoder._tick``)
+        if shadow is not None:
+            w, wt = shadow
+        else:
+            w, wt = weight.detach().to(dtype=torch.bfloat16, memory_format=_CL), None
+        if wt is None and x.requires_grad:
+            wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
+        b = None if bias is None else bias.detach().to(torch.bfloat16)
+        y = ops.conv3x3_narrow_bf16(x, w, b)
+        ctx.save_for_backward(x, wt if wt is not None else w)
+        ctx.has_bias, ctx.flipped, ctx.det = bias is not None, wt is not None, _det_now()
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import ops
+        x, wt = ctx.saved_tensors
+        B, ci, H, W = x.shape
+        co = dy.shape[1]
+        dy = dy.contiguous(memory_format=_CL)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            if not ctx.flipped:                              # (x began to require a gradient after the forward: not a TrainEncoder flow)
+                wt = torch.flip(wt, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
+            dx = ops.conv3x3_narrow_dgrad_bf16(dy, wt)
+        dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)      # the master's own layout
+        _wgrad(("3x3n", dy, x, (B, H, W, ci, co), dw))
+        db = _channel_sums(dy, ctx.det) if ctx.has_bias else None
+        return dx, dw, db, None
+
+
 def _channel_sums(dy, det: bool = False):
     """sum over (batch, rows, columns) of a channels-last bf16 gradient in fp32 (a bias gradient): the statistics kernel's first
     row -- one launch where ``dy.float().sum((0, 2, 3))`` is a cast of the whole tensor and a reduction.  ``det``: the
@@ -454,13 +516,17 @@ def _conv(x, m: nn.Conv2d, dtype, linear_1x1: bool = True, own_wgrad: bool = Tru
     """Convolution ``m`` (fp32 master weight) on a channels-last activation in the compute dtype.  On the device in bf16: a
     1x1 convolution is the product of the activation matrix with W^T (hipBLASLt forward and data gradient), a 3x3 one runs on
     MIOpen, and both take their weight gradient from ``dmm_wgrad*_bf16``; anything else (the 7x7 stem, widths that are not a
-    multiple of 64, fp32 mode, the CPU) goes through the stock ops with a differentiable cast of the weight."""
+    multiple of 64, fp32 mode, the CPU) goes through the stock ops with a differentiable cast of the weight -- except, in the
+    deterministic mode under ``set_deterministic_conv("own_all")``, a narrow 3x3 convolution (``_narrow_ok``), which runs on
+    ``_ConvNarrowFn``."""
     fast = own_wgrad and x.is_cuda and dtype == torch.bfloat16 and x.dtype == dtype and _wgrad_ok(m)
     one = m.kernel_size == (1, 1) and m.padding == (0, 0)
     if fast and linear_1x1 and one and m.bias is None:
         return _Conv1x1Fn.apply(x.contiguous(memory_format=_CL), m.weight, m.stride[0], shadow)
     if fast and m.kernel_size == (3, 3) and m.padding == (1, 1):
         return _Conv3x3Fn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias, m.stride[0], shadow)
+    if own_wgrad and x.is_cuda and dtype == torch.bfloat16 and x.dtype == dtype and _narrow_conv_now() and _narrow_ok(m):
+        return _ConvNarrowFn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias, shadow)
     b = None if m.bias is None else m.bias.to(dtype)
     if linear_1x1 and one and m.groups == 1 and m.dilation == (1, 1):
         if m.stride != (1, 1):
@@ -503,7 +569,7 @@ class _DetConvFn(torch.autograd.Function):
     def forward(ctx, x, w, b, stride, padding, dilation, groups):
         ctx.save_for_backward(x, w)
         ctx.conf = (tuple(stride), tuple(padding), tuple(dilation), groups, b is not None)
-        ctx.own = get_deterministic_conv() == "own"
+        ctx.own = get_deterministic_conv() in ("own", "own_all")
         if ctx.own and "forward" in _DET_AS_GEMM and groups == 1 and tuple(dilation) == (1, 1):
             return _conv_as_gemm(x, w, b, tuple(stride), tuple(padding))
         with library_flags(True):
@@ -640,8 +706,9 @@ class TrainEncoder(nn.Module):
                     t[id(m)] = w
                 self._cast_1x1(convs, dst)
         if self.own_wgrad:
+            narrow = _narrow_conv_now()                      # (the narrow heads share the segment's one wprep launch)
             convs = [m for m in mods if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.padding == (1, 1)
-                     and _wgrad_ok(m)]
+                     and (_wgrad_ok(m) or (narrow and _narrow_ok(m)))]
             if convs:
                 self._prep_3x3(convs, t)
 
@@ -676,7 +743,7 @@ class TrainEncoder(nn.Module):
         from . import _lib
         memo = self.__dict__.setdefault("_wprep", {})
         own = _own_conv_now()                           # every data gradient runs on the flipped weight, whatever the shape
-        key = tuple(id(m) for m in convs) + (own,)
+        key = tuple(id(m) for m in convs) + (own, _narrow_conv_now())     # (tables of one setting are not reused under another)
         ptrs = tuple(m.weight.data_ptr() for m in convs)
         got = memo.get(key)
         if got is None or got[0] != ptrs:
@@ -840,8 +907,9 @@ class TrainEncoder(nn.Module):
                 self.__dict__.get("_wcast", {}).clear()
             self.__dict__["_storage"] = fp
         # (the mode is part of the key: a graph captured in one mode never replays in the other)
-        key = (tuple(img.shape), img.dtype, img.device.index, self.skips_need_grad, bn_groups,
-               det and get_deterministic_conv() == "own", det)
+        conv = get_deterministic_conv() if det else "library"
+        key = (tuple(img.shape), img.dtype, img.device.index, self.skips_need_grad, bn_groups, conv,
+               conv in ("own", "own_all"), det)
         plans = self._plans.setdefault(key, [])
         # a plan's static buffers belong to ONE forward until its backward has run: a second forward of the same shape before
         # that (the trainer's clip: one encoder call per frame, one backward; trainer.py:95-131) takes / captures another plan

@@ -818,6 +818,29 @@ DMM_API size_t dmm_conv3x3_workspace_bytes(int B, int H, int W, int ci, int co, 
 DMM_API int dmm_conv3x3_bf16(const void *x, const void *w, const void *bias, int B, int H, int W, int ci, int co, int stride,
                              void *y, void *workspace, size_t workspace_bytes, dmm_stream_t stream);
 
+/* (10e) The NARROW 3x3 / padding 1 / stride 1 convolutions of the training encoder for the DETERMINISTIC mode: widths that are
+ * multiples of 32 but not of 64 -- the level-2 heads of base.py:35-54 (256 -> 32, 32 -> 128) as train.py:46 runs them under
+ * cudnn.deterministic -- which (10b) and (10d) reject.  Multiples of 64 are taken too.
+ * dmm_conv3x3_narrow_bf16: the contract of (10d) at stride 1: x [B, H, W, ci] and y [B, H, W, co] dense channels-last bf16, w the
+ *   bf16 channels-last weight [co, kh, kw, ci] (dmm_wprep3x3_bf16's dst), bias bf16 [co] or NULL; fp32 accumulation, the bias added
+ *   in fp32, ONE rounding.  The DATA gradient is the same entry on dy with dmm_wprep3x3_bf16's dstT.  No atomics, no split of the
+ *   reduction, no workspace: the summation order of an output element is a function of (ci, co) alone, an image's bits do not
+ *   depend on its batch, results are bit-identical call after call, eagerly and in graph replay.  Answers, before any launch:
+ *   DMM_ERR_BAD_ARG for B < 0, H / W / ci / co <= 0, ci or co not a multiple of 32; DMM_OK for B == 0; DMM_ERR_BAD_ARG for a null
+ *   x / w / y, a pointer that is not 16-byte aligned, more than 2^31 - 1 tiles of 128 pixels.
+ * dmm_wgrad3x3_narrow_bf16:  dw[co, ci, kh, kw] = sum_(b,h,w) dy[(b,h,w), co] * x[b, h+kh-1, w+kw-1, ci]   (zero outside), dy
+ *   [B*H*W, co] and x [B, H, W, ci] dense bf16; dw fp32 in the parameter's own [co, ci, 3, 3] layout, OVERWRITTEN (no zeroing, no
+ *   atomics: row slabs -> partial tables in the caller's workspace -> summed in slab order, as (10b)).  workspace:
+ *   dmm_wgrad3x3_narrow_workspace_bytes(...) bytes, 16-byte aligned (0 for arguments the entry rejects and for B == 0).  Answers,
+ *   before any launch: DMM_ERR_BAD_ARG for B < 0, H / W / ci / co <= 0, a width that is not a multiple of 32, a null dw; for
+ *   B == 0 dw is zeroed and the answer is DMM_OK; DMM_ERR_BAD_ARG for a null dy / x, a dy / x / dw that is not 4-byte aligned;
+ *   DMM_ERR_WORKSPACE for a null or short workspace. */
+DMM_API int dmm_conv3x3_narrow_bf16(const void *x, const void *w, const void *bias, int B, int H, int W, int ci, int co,
+                                    void *y, dmm_stream_t stream);
+DMM_API size_t dmm_wgrad3x3_narrow_workspace_bytes(int B, int H, int W, int ci, int co);
+DMM_API int dmm_wgrad3x3_narrow_bf16(const void *dy, const void *x, int B, int H, int W, int ci, int co, float *dw,
+                                     void *workspace, size_t workspace_bytes, dmm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * (11) HIP-graph hygiene for captured steps that contain other libraries' launches (MIOpen, hipBLASLt, torch): between the
  * end of a stream capture and hipGraphInstantiate, replace every memset node (flags & 1; element size 1 / 2 / 4) and every

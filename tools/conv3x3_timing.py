@@ -4,9 +4,14 @@
 ``cudnn.deterministic``.  HIP-event time per call over a window of launches after a warm-up; FLOP = 2 * B * Ho * Wo * co * 9 *
 ci, so TFLOP/s is the algorithm's work over the call's device time (a call of a split reduction is two launches).
 
-    python tools/conv3x3_timing.py [--frames 12] [--out FILE.json] [--skip-library-det]
+    python tools/conv3x3_timing.py [--frames 12] [--out FILE.json] [--skip-library-det] [--narrow-only]
 
-Prints a markdown table and one JSON line; needs an MI355X."""
+Then the NARROW shapes (``ops.conv3x3_narrow_bf16`` = dmm_conv3x3_narrow_bf16; the level-2 heads at frames x 64 x 112: 256 -> 32
+and 32 -> 128 forward, 32 -> 256 and 128 -> 32 as their data gradients): the own kernel beside ``F.conv2d`` with and without
+``cudnn.deterministic`` and beside the unfold + ``mm`` route the "own" setting takes, and the narrow weight gradient
+(``ops.wgrad3x3_narrow_bf16``) beside unfold + ``mm``.
+
+Prints two markdown tables and one JSON line; needs an MI355X."""
 import json
 import os
 import sys
@@ -58,6 +63,55 @@ def timed(fn, budget_ms=200.0, max_iters=200):
     return a.elapsed_time(b) / n
 
 
+NARROW = [(256, 32), (32, 128), (32, 256), (128, 32)]      # (ci, co) at frames x 64 x 112
+
+
+def narrow_rows(frames, skip_library_det):
+    """The narrow shapes: forward / data gradient (the same entry) and weight gradient, own kernels beside the other routes."""
+    import torch
+    import torch.nn.functional as F
+    from dmm_net_amd import ops
+    from dmm_net_amd.train_encoder import _conv_as_gemm
+    cl = torch.channels_last
+    H, W = 64, 112
+    g = torch.Generator(device="cuda:0").manual_seed(1)
+    rows = []
+    for ci, co in NARROW:
+        x = torch.randn((frames, ci, H, W), generator=g, device="cuda:0").bfloat16().contiguous(memory_format=cl)
+        w = (torch.randn((co, ci, 3, 3), generator=g, device="cuda:0") / (3 * ci ** 0.5)).bfloat16().contiguous(memory_format=cl)
+        dy = torch.randn((frames, co, H, W), generator=g, device="cuda:0").bfloat16().contiguous(memory_format=cl)
+        flop = 2.0 * frames * H * W * co * 9 * ci
+        own = timed(lambda: ops.conv3x3_narrow_bf16(x, w, None))
+        unfold = timed(lambda: _conv_as_gemm(x, w, None, (1, 1), (1, 1)), budget_ms=100.0, max_iters=50)
+        with torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=False):
+            lib = timed(lambda: F.conv2d(x, w, None, 1, 1))
+            same = float((ops.conv3x3_narrow_bf16(x, w, None).float() - F.conv2d(x, w, None, 1, 1).float()).abs().max())
+        lib_det = None
+        if not skip_library_det:
+            with torch.backends.cudnn.flags(enabled=True, benchmark=False, deterministic=True):
+                lib_det = timed(lambda: F.conv2d(x, w, None, 1, 1), budget_ms=60.0, max_iters=20)
+        wg_own = timed(lambda: ops.wgrad3x3_narrow_bf16(dy, x))
+
+        def wg_unfold():                                 # _DetConvFn's weight gradient
+            cols = F.unfold(x, (3, 3), 1, 1, 1).transpose(1, 2).reshape(frames * H * W, ci * 9)
+            return torch.mm(dy.permute(0, 2, 3, 1).reshape(frames * H * W, co).t(), cols)
+        wg_un = timed(wg_unfold, budget_ms=100.0, max_iters=50)
+        rows.append({"ci": ci, "co": co, "H": H, "W": W, "gflop": round(flop / 1e9, 3), "own_ms": round(own, 4),
+                     "own_tflops": round(flop / own / 1e9, 1), "unfold_mm_ms": round(unfold, 4), "library_ms": round(lib, 4),
+                     "library_det_ms": None if lib_det is None else round(lib_det, 4), "max_abs_own_minus_library": same,
+                     "wgrad_own_ms": round(wg_own, 4), "wgrad_unfold_mm_ms": round(wg_un, 4)})
+        del x, w, dy
+        torch.cuda.empty_cache()
+    print()
+    print("| ci | co | H x W | GFLOP | own ms | own TFLOP/s | unfold + mm ms | F.conv2d ms | F.conv2d deterministic ms | "
+          "wgrad own ms | wgrad unfold + mm ms |")
+    print("|---|---|---|---|---|---|---|---|---|---|---|")
+    for r in rows:
+        print(f"| {r['ci']} | {r['co']} | {r['H']} x {r['W']} | {r['gflop']} | {r['own_ms']} | {r['own_tflops']} | "
+              f"{r['unfold_mm_ms']} | {r['library_ms']} | {r['library_det_ms']} | {r['wgrad_own_ms']} | {r['wgrad_unfold_mm_ms']} |")
+    return rows
+
+
 def main():
     import torch
     import torch.nn.functional as F
@@ -69,7 +123,8 @@ def main():
     cl = torch.channels_last
     rows = []
     g = torch.Generator(device="cuda:0").manual_seed(0)
-    for (ci, co, stride, H, W), count in sorted(shapes(frames).items(), key=lambda kv: (-kv[0][3], kv[0])):
+    wide = {} if "--narrow-only" in a else shapes(frames)
+    for (ci, co, stride, H, W), count in sorted(wide.items(), key=lambda kv: (-kv[0][3], kv[0])):
         x = torch.randn((frames, ci, H, W), generator=g, device="cuda:0").bfloat16().contiguous(memory_format=cl)
         w = (torch.randn((co, ci, 3, 3), generator=g, device="cuda:0") / (3 * ci ** 0.5)).bfloat16().contiguous(memory_format=cl)
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
@@ -92,7 +147,8 @@ def main():
               f"{r['own_tflops']} | {r['library_ms']} | {r['library_det_ms']} |")
     tot = lambda k: round(sum(r[k] * r["count"] for r in rows if r[k] is not None), 3)
     summary = {"frames": frames, "forward_sum_ms": {"own": tot("own_ms"), "library": tot("library_ms"),
-                                                   "library_det": tot("library_det_ms")}, "rows": rows}
+                                                   "library_det": tot("library_det_ms")}, "rows": rows,
+               "narrow_rows": narrow_rows(frames, "--skip-library-det" in a)}
     print(json.dumps(summary), flush=True)
     if "--out" in a:
         with open(a[a.index("--out") + 1], "w") as f:
