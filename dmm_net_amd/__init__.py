@@ -62,6 +62,10 @@ def __getattr__(name):
     if name in ("softIoULoss", "mask_step_losses"):
         from . import losses
         return getattr(losses, name)
+    # the DAVIS J / F scores (measures.py), lazily too
+    if name in ("clip_counts", "scores_from_counts", "sequence_results", "ClipScorer"):
+        from . import measures
+        return getattr(measures, name)
     raise AttributeError(f"module 'dmm_net_amd' has no attribute '{name}'")
 
 

@@ -943,6 +943,44 @@ DMM_API int dmm_mask_iou_loss_bwd(const void *target, int target_dtype, int64_t 
                                   int B, int O, int n_obj, int HW, const void *workspace, size_t workspace_bytes,
                                   float *dpred, int64_t sb_dpred, int64_t so_dpred, dmm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (14) The integer counts under the DAVIS measures of a clip: region similarity J and boundary accuracy F per frame and object.
+ * Replaces the pixel work of db_eval_iou (dmm/measures/jaccard.py:15-37) and db_eval_boundary with seg2bmap
+ * (dmm/measures/f_boundary.py:14-78 and :80-140; skimage's binary_dilation by disk(bound_pix) at :47-50) as db_eval_sequence
+ * calls them on `an == obj_id, sg == obj_id` (dmm/dataloader/evaluation.py:44-46).  The divisions and the case analysis of
+ * the two measures stay on the host (dmm_net_amd/measures.py): everything here is an integer, equal to the reference bit for bit.
+ *
+ * pred, gt: uint8 label maps, frame f at pred + f * frame_stride_pred (gt likewise), H dense rows of W pixels; 0 = background,
+ * o + 1 = object o; a label above n_obj belongs to no object.  For frame f and object o, S = (pred == o + 1), A = (gt == o + 1):
+ *   counts[f, o, 0] = #(S & A)                       counts[f, o, 1] = #(S | A)
+ *   counts[f, o, 2] = #bmap(S)          (n_fg)       counts[f, o, 3] = #bmap(A)          (n_gt)
+ *   counts[f, o, 4] = #(bmap(S) & dil(bmap(A)))      counts[f, o, 5] = #(bmap(A) & dil(bmap(S)))
+ * (slot 4 / slot 2 is the reference's precision, slot 5 / slot 3 its recall: its names fg_match / gt_match are crossed.)
+ * bmap is seg2bmap at equal size: with e, s, se the mask shifted by one pixel towards the origin from the east, the south
+ * and the south-east (zero where the shift leaves the image), b = (m ^ e) | (m ^ s) | (m ^ se); then the last row is
+ * m ^ e, then the last column is m ^ s, then the bottom-right pixel is 0 -- in this order, which decides the corner and the
+ * 1 x W and H x 1 images.  dil is the binary dilation by the disk dx * dx + dy * dy <= radius * radius, zeros outside the image.
+ *
+ * Two launches (a clearing kernel, not a memset node, then the counts); no host synchronisation, no allocation: capturable.
+ * Band partials meet in `counts` by integer atomics, so the bytes are the same on every run and the workspace is empty:
+ * dmm_davis_counts_workspace_bytes answers 0 today and callers still ask it.  A workgroup owns DMM_DAVIS_BAND_ROWS(radius)
+ * rows (fewer when H is smaller) of a column tile of 64-pixel words.
+ *
+ * What the entry answers, in this order (where two faults coincide, the earlier one is named):
+ *   1. DMM_ERR_BAD_ARG      frames, n_obj, H, W or radius negative, or a frame stride below H * W
+ *   2. DMM_OK               frames == 0 or n_obj == 0: nothing to do, nothing launched, pointers not looked at
+ *   3. DMM_ERR_BAD_ARG      pred, gt or counts null
+ *   4. DMM_ERR_UNSUPPORTED  radius > DMM_DAVIS_MAX_RADIUS, n_obj > 255, H * W >= 2^31, or 2^31 or more workgroups / count words
+ *   5. DMM_ERR_WORKSPACE    the workspace is null or shorter than dmm_davis_counts_workspace_bytes (when that is not 0)
+ * H == 0 or W == 0 (after these checks): every count is 0.
+ * ------------------------------------------------------------------------------------------- */
+#define DMM_DAVIS_MAX_RADIUS 63 /* a horizontal shift crosses at most one 64-bit word boundary */
+#define DMM_DAVIS_BAND_ROWS(radius) (3 * (radius) + 8 < 16 ? 16 : 3 * (radius) + 8 > 64 ? 64 : 3 * (radius) + 8)
+DMM_API size_t dmm_davis_counts_workspace_bytes(int frames, int n_obj, int H, int W, int radius);
+DMM_API int dmm_davis_counts_u8(const uint8_t *pred, const uint8_t *gt, int frames, int n_obj, int H, int W,
+                                int64_t frame_stride_pred, int64_t frame_stride_gt, int radius, int32_t *counts, void *workspace,
+                                size_t workspace_bytes, dmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
