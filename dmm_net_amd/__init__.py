@@ -66,6 +66,10 @@ def __getattr__(name):
     if name in ("clip_counts", "scores_from_counts", "sequence_results", "ClipScorer"):
         from . import measures
         return getattr(measures, name)
+    # the clip augmentation (augment.py), lazily too
+    if name in ("affine_matrix", "draw_clip_params", "augment_clip", "AugmentedClip"):
+        from . import augment
+        return getattr(augment, name)
     raise AttributeError(f"module 'dmm_net_amd' has no attribute '{name}'")
 
 

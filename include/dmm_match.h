@@ -981,6 +981,61 @@ DMM_API int dmm_davis_counts_u8(const uint8_t *pred, const uint8_t *gt, int fram
                                 int64_t frame_stride_pred, int64_t frame_stride_gt, int radius, int32_t *counts, void *workspace,
                                 size_t workspace_bytes, dmm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (15) The augmentation of training clips: one nearest-neighbour affine warp per frame, applied to the image planes, the
+ * annotation and every pasted proposal mask, with the proposals' boxes and the target planes out of the same pass.  Replaces
+ * the per-plane Python loop of dmm/dataloader/dataset.py:222-258 -- the clip's flip, Affine(tf_matrix, interp='nearest')
+ * (th_affine2d(center=True) + th_nearest_interp2d, dmm/dataloader/transforms/utils.py:67-148) on img, annot and each mask,
+ * binmask_to_bbox_xyxy_pt (dmm/utils/utils.py:114-143, pad = 0) of each warped mask > 0.5 -- and sequence_from_masks
+ * (dataset.py:300-338) on the warped annotation.
+ *
+ * n frames (a clip, or clips back to back).  Frame f has its own row-major 3 x 3 fp32 matrix m = matrices + 9 f (the last row
+ * is not read) and its own flip flag flips[f] (the reference flips a whole clip: repeat the flag; flips == NULL: none).  The
+ * source of output pixel (r, c), in fp32 with one rounding per operation, in exactly this order:
+ *   cr = H / 2 - 0.5,  cc = W / 2 - 0.5                   (formed in double, rounded to fp32 once)
+ *   x  = float(r) - cr;  y = float(c) - cc
+ *   sr = (((m[0] * x) + (m[1] * y)) + m[2]) + cr
+ *   sc = (((m[3] * x) + (m[4] * y)) + m[5]) + cc
+ *   ri = (int) rintf(min(max(sr, 0), H - 1))              (clamp BEFORE rounding; ties to even)
+ *   ci = (int) rintf(min(max(sc, 0), W - 1))
+ *   if flips[f]: ci = W - 1 - ci                          (the reference flips first and warps the flipped frame)
+ * and out[r, c] = in[ri, ci] for every plane of the frame (a plane is H dense rows of W elements):
+ *   C image planes   fp32, plane ch of frame f at frames_in + f * fs_frames_in + ch * ps_frames_in (frames_out likewise)
+ *   1 label plane    uint8, frame f at labels_in + f * fs_labels_in (labels_out likewise)
+ *   P mask planes    fp32 soft masks at masks_in + f * fs_masks_in + p * ps_masks_in (masks_out likewise); P may be 0
+ * Strides are in elements; output planes must not overlap each other or any input.
+ *   boxes_out [n, P, 4] fp32 xyxy, box_valid [n, P] int32: the inclusive min / max column and row of (masks_out[f, p] > 0.5)
+ *     (strict) and 1; where the warped mask has no such pixel, boxes_in[f, p] copied through and 0 (the reference keeps the
+ *     old box).  Until the last launch boxes_out holds the integer table the workgroups meet in.
+ *   targets [n, F, H, W] fp32 dense: targets[f, o] = (labels_out[f] == o + 1) as 1.0 / 0.0; sizes [n, F] int32: its pixel
+ *     count.  Labels 0, 255 and anything above F belong to no plane.  (Label 0 is ALWAYS background: the reference's
+ *     np.unique(annot)[1:] drops the smallest object id of a frame without a background pixel; that is not reproduced.)
+ *
+ * At most three launches: a clearing kernel for the two integer tables (a kernel, not a memset node), the warp, and -- when
+ * P > 0 -- the box finish.  No host synchronisation, no allocation: capturable.  Boxes meet by integer max and sizes by
+ * integer add, both order-free, so the bytes are the same on every run and the workspace is empty:
+ * dmm_augment_clip_workspace_bytes answers 0 today and callers still ask it.
+ *
+ * What the entry answers, in this order (where two faults coincide, the earlier one is named):
+ *   1. DMM_ERR_BAD_ARG      n, C, P, F, H or W negative; a frame stride of the labels below H * W; with C > 0 a frame or plane
+ *                           stride of the image planes below H * W; with P > 0 likewise of the mask planes
+ *   2. DMM_OK               n == 0, H == 0 or W == 0: nothing to do, nothing launched, nothing written, pointers not looked at
+ *   3. DMM_ERR_BAD_ARG      labels_in, labels_out or matrices null; with C > 0 frames_in or frames_out; with P > 0 masks_in,
+ *                           masks_out, boxes_in, boxes_out or box_valid; with F > 0 targets or sizes; or an output that IS its
+ *                           input (labels, frames, masks, boxes): a gather cannot run in place
+ *   4. DMM_ERR_UNSUPPORTED  H * W >= 2^31, F > DMM_AUGMENT_MAX_TARGETS, or 2^31 or more workgroups, box words or size words
+ *   5. DMM_ERR_WORKSPACE    the workspace is null or shorter than dmm_augment_clip_workspace_bytes (when that is not 0)
+ * ------------------------------------------------------------------------------------------- */
+#define DMM_AUGMENT_MAX_TARGETS 254 /* label 255 is "ignore" in DAVIS 2017 and is never a target plane */
+DMM_API size_t dmm_augment_clip_workspace_bytes(int n, int C, int P, int F, int H, int W);
+DMM_API int dmm_augment_clip_f32(const float *frames_in, int64_t fs_frames_in, int64_t ps_frames_in, float *frames_out,
+                                 int64_t fs_frames_out, int64_t ps_frames_out, const uint8_t *labels_in, int64_t fs_labels_in,
+                                 uint8_t *labels_out, int64_t fs_labels_out, const float *masks_in, int64_t fs_masks_in,
+                                 int64_t ps_masks_in, float *masks_out, int64_t fs_masks_out, int64_t ps_masks_out,
+                                 const float *boxes_in, float *boxes_out, int32_t *box_valid, float *targets, int32_t *sizes,
+                                 const float *matrices, const int32_t *flips, int n, int C, int P, int F, int H, int W,
+                                 void *workspace, size_t workspace_bytes, dmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
