@@ -46,6 +46,7 @@ pin the plumbing with).  Off the GPU (or with ``graphs=False``) the same segment
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
@@ -57,11 +58,11 @@ from .encoder import _NO_CTX, Bottleneck, FeatureEncoder, ResNetBody
 from .graphs import CaptureFailed, SafeGraph
 
 _CL = torch.channels_last
-_CAPTURE_LOCK = __import__("threading").Lock()     # plan captures set module-level scratch (_ARENA, _DEFER) and put the process
+_CAPTURE_LOCK = __import__("threading").Lock()     # plan captures set module-level scratch (_CAPTURE) and put the process
 #                                                    into HIP's global capture mode: one at a time (nn.DataParallel threads)
 
 
-# ---- scratch for the BatchNorm statistics ------------------------------------------------------------------------------
+# ---- scratch of a graph capture: the BatchNorm statistics' arena, the deferred weight-gradient launches ------------------
 class _Arena:
     """fp32 scratch the statistics kernels accumulate into (they need zeroed [2, C] blocks): inside a captured segment ONE
     zeroing launch at the head of the graph clears the blocks of all its layers -- a ``torch.zeros`` per layer and direction
@@ -81,28 +82,41 @@ class _Arena:
         return t
 
 
-_ARENA: Optional[_Arena] = None          # set while a segment is being captured (captures never run side by side)
+class _Capture:
+    """What the ops of ONE graph capture share: ``arena`` (the statistics scratch of the graph, or None) and ``records``
+    (``overlap_wgrad``: the weight-gradient launches of a segment's backward chain, recorded with their operands kept alive
+    instead of launched, and captured afterwards into a SECOND graph that replays on a side stream beside the next
+    segment's chain; None: they are launched where the backward reaches them)."""
+
+    def __init__(self, arena: Optional[_Arena], defer: bool):
+        self.arena, self.records = arena, ([] if defer else None)
+
+
+# The capture that is running, or None.  Process-global ON PURPOSE, guarded by _CAPTURE_LOCK (captures never run side by
+# side): the backward nodes that ``torch.autograd.grad`` runs inside a capture execute on autograd's device worker thread,
+# not on the capturing thread -- a thread-local or a ``contextvars`` variable would be unset where ``_zeroed`` and ``_wgrad``
+# read it.
+_CAPTURE: Optional[_Capture] = None
+
+
+@contextmanager
+def _capture_scope(arena: Optional[_Arena] = None, defer: bool = False):
+    """Entered INSIDE a graph capture, for its length.  -> the ``_Capture``."""
+    global _CAPTURE
+    cap = _CAPTURE = _Capture(arena, defer)
+    try:
+        if arena is not None:
+            arena.buf.zero_()                # a fill KERNEL (captured: replayed at the head of the graph)
+        yield cap
+    finally:
+        _CAPTURE = None
 
 
 def _zeroed(n: int, device) -> torch.Tensor:
-    if _ARENA is not None and _ARENA.buf.device == device:
-        return _ARENA.take(n)
+    cap = _CAPTURE
+    if cap is not None and cap.arena is not None and cap.arena.buf.device == device:
+        return cap.arena.take(n)
     return torch.zeros(n, dtype=torch.float32, device=device)
-
-
-class _arena_scope:
-    def __init__(self, arena):
-        self.arena = arena
-
-    def __enter__(self):
-        global _ARENA
-        _ARENA = self.arena
-        self.arena.buf.zero_()               # a fill KERNEL (captured: replayed at the head of the graph)
-        return self.arena
-
-    def __exit__(self, *exc):
-        global _ARENA
-        _ARENA = None
 
 
 # ---- deterministic mode (dmm_net_amd.determinism): resolved once per TrainEncoder call and pinned while it builds / runs ----
@@ -144,8 +158,16 @@ def _narrow_conv_now() -> bool:
 
 
 def _det_ws(nbytes: int, device) -> torch.Tensor:
-    """Slab workspace of a deterministic reduction: written whole by the launch that fills it, so never zeroed."""
+    """Slab workspace of a deterministic reduction (the BatchNorm statistics', a weight gradient's): written whole by the
+    launch that fills it, so never zeroed."""
     return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
+
+
+def _stats_channels_ok(C: int) -> bool:
+    """The channel envelope of the statistics kernels (``dmm_bn_*_grouped_bf16``): C % 8 == 0 and C / 8 a divisor of 256 (eight
+    channels per thread, whole rows per 256-thread workgroup)."""
+    c8 = C // 8
+    return C % 8 == 0 and 0 < c8 <= 256 and 256 % c8 == 0
 
 
 def _bn_scratch(det: bool, R: int, C: int, groups: int, device):
@@ -242,9 +264,7 @@ class _TapSplit(torch.autograd.Function):
 
 
 def _bn_fusable(bn: nn.BatchNorm2d) -> bool:
-    c8 = bn.num_features // 8
-    return (bn.affine and bn.track_running_stats and bn.momentum is not None and bn.num_features % 8 == 0
-            and 0 < c8 <= 256 and 256 % c8 == 0)
+    return bn.affine and bn.track_running_stats and bn.momentum is not None and _stats_channels_ok(bn.num_features)
 
 
 def _bn_act(x, bn: nn.BatchNorm2d, relu: bool, residual=None, fused: bool = True, counted: bool = False, groups: int = 1,
@@ -274,37 +294,36 @@ def _bn_act(x, bn: nn.BatchNorm2d, relu: bool, residual=None, fused: bool = True
 _DGRAD_AS_FORWARD = True                 # (module switch for the A/B in tools/cfg4_probe.py)
 _DET_AS_GEMM = ("forward", "dgrad")     # (module switch for the A/B in tools/cfg4_probe.py: which of _DetConvFn's convolutions
 #                                          are an unfold + one GEMM under set_deterministic_conv("own"))
-_DEFER: Optional[list] = None            # set while a segment's backward is captured with ``overlap_wgrad``: the launches are
-#                                          recorded (operands kept alive) and captured afterwards into a SECOND graph that replays
-#                                          on a side stream beside the next segment's backward chain
 
 
 def _wgrad_launch(rec):
-    from . import _lib
-    L = _lib.load()
+    """One weight gradient, ``rec`` = (kind, dy, x, dims, dw): "1x1" (rows, co, ci), "3x3" (B, H, W, ci, co, stride, Ho, Wo),
+    "3x3n" (B, H, W, ci, co; the narrow kernel, sized and launched by its wrapper in ``ops``) -> dw, overwritten."""
+    from . import _lib, ops
     kind, dy, x, dims, dw = rec
+    if kind == "3x3n":
+        ops.wgrad3x3_narrow_bf16(dy, x, out=dw)
+        return
+    need = _lib.load().dmm_wgrad_workspace_bytes
     dev = x.device
     stream = torch.cuda.current_stream(dev).cuda_stream
     if kind == "1x1":
         rows, co, ci = dims
-        ws = torch.empty((max(int(L.dmm_wgrad_workspace_bytes(rows, co, ci)), 16),), dtype=torch.uint8, device=dev)
+        ws = _det_ws(need(rows, co, ci), dev)
         _lib.call("dmm_wgrad_bf16", dev, dy.data_ptr(), x.data_ptr(), rows, co, ci, co, ci, dw.data_ptr(), ws.data_ptr(),
-                  ws.numel(), stream)
-    elif kind == "3x3n":
-        B, H, W, ci, co = dims
-        ws = torch.empty((max(int(L.dmm_wgrad3x3_narrow_workspace_bytes(B, H, W, ci, co)), 16),), dtype=torch.uint8, device=dev)
-        _lib.call("dmm_wgrad3x3_narrow_bf16", dev, dy.data_ptr(), x.data_ptr(), B, H, W, ci, co, dw.data_ptr(), ws.data_ptr(),
                   ws.numel(), stream)
     else:
         B, H, W, ci, co, stride, Ho, Wo = dims
-        ws = torch.empty((max(int(L.dmm_wgrad_workspace_bytes(B * Ho * Wo, co, 9 * ci)), 16),), dtype=torch.uint8, device=dev)
+        ws = _det_ws(need(B * Ho * Wo, co, 9 * ci), dev)
         _lib.call("dmm_wgrad3x3_bf16", dev, dy.data_ptr(), x.data_ptr(), B, H, W, ci, co, stride, dw.data_ptr(),
                   ws.data_ptr(), ws.numel(), stream)
 
 
 def _wgrad(rec):
-    if _DEFER is not None:
-        _DEFER.append(rec)
+    """A weight gradient where the backward reaches it: launched, or recorded for the running capture's second graph."""
+    cap = _CAPTURE
+    if cap is not None and cap.records is not None:
+        cap.records.append(rec)
     else:
         _wgrad_launch(rec)
 
@@ -320,6 +339,44 @@ def _narrow_ok(m: nn.Conv2d) -> bool:
     them is no multiple of 64): the 32-channel level-2 heads."""
     return (m.kernel_size == (3, 3) and m.padding == (1, 1) and m.stride == (1, 1) and m.groups == 1 and m.dilation == (1, 1)
             and m.in_channels % 32 == 0 and m.out_channels % 32 == 0 and not _wgrad_ok(m))
+
+
+def _conv_route(m: nn.Module, linear_1x1: bool = True, own_wgrad: bool = True) -> Optional[str]:
+    """The route of convolution module ``m`` on a bf16 activation on the device: "1x1" (``_Conv1x1Fn``), "3x3" (``_Conv3x3Fn``),
+    "narrow" (``_ConvNarrowFn``: only under the narrow setting, ``_narrow_conv_now``), or None (the stock ops).  ``_conv`` takes
+    it, and ``TrainEncoder._tick`` prepares the weight copies of exactly the modules it names."""
+    if not (own_wgrad and isinstance(m, nn.Conv2d)):
+        return None
+    if not _wgrad_ok(m):
+        return "narrow" if _narrow_ok(m) and _narrow_conv_now() else None
+    if linear_1x1 and m.kernel_size == (1, 1) and m.padding == (0, 0) and m.bias is None:
+        return "1x1"
+    return "3x3" if m.kernel_size == (3, 3) and m.padding == (1, 1) else None
+
+
+def _dgrad_on_flipped(own: bool, stride: int, co: int, ci: int) -> bool:
+    """A 3x3 convolution's data gradient runs as the FORWARD convolution of dy with the flipped, transposed weight: always on
+    the own kernels; on MIOpen at stride 1 with as many channels in as out (conv2 of a bottleneck), where dX = conv(dY,
+    W'[ci, co, kh, kw] = W[co, ci, 2 - kh, 2 - kw]) is the same convolution problem -- MIOpen's forward kernel for it takes
+    28 us where its backward-data kernel takes 50 (profiles/r06_kernel_stats_config4_bf16.csv), on the backward's critical
+    chain."""
+    return own or (_DGRAD_AS_FORWARD and stride == 1 and co == ci)
+
+
+def _flipped(w):
+    """W'[ci, co, kh, kw] = W[co, ci, K - 1 - kh, K - 1 - kw], channels-last: the weight of a data gradient run as a forward."""
+    return torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
+
+
+def _bf16_weights(weight, bias, shadow, flip: bool):
+    """-> (w, wt, b) of a 3x3 convolution: the bf16 channels-last copy of the fp32 master, its flipped copy or None, the bf16
+    bias or None.  ``shadow`` = (w, wt): both made for the caller's whole segment in one launch (``TrainEncoder._tick``), wt
+    None where the data gradient does not run on it; ``flip``: make a missing wt here (in the forward, off the backward's
+    critical chain)."""
+    w, wt = shadow if shadow is not None else (weight.detach().to(dtype=torch.bfloat16, memory_format=_CL), None)
+    if wt is None and flip:
+        wt = _flipped(w)
+    return w, wt, None if bias is None else bias.detach().to(torch.bfloat16)
 
 
 def _subsample(x, stride: int):
@@ -401,23 +458,11 @@ class _Conv3x3Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, shadow=None):
-        # stride 1 and as many channels in as out (conv2 of a bottleneck): the data gradient is the SAME convolution problem with
-        # the weight flipped and transposed, dX = conv(dY, W'[ci, co, kh, kw] = W[co, ci, 2 - kh, 2 - kw]) -- MIOpen's forward
-        # kernel for it takes 28 us where its backward-data kernel takes 50 (profiles/r06_kernel_stats_config4_bf16.csv), on
-        # the backward's critical chain; the flipped copy is made in the forward, off that chain.
-        # shadow = (w, wt): both made for the caller's whole segment in one launch (``TrainEncoder._tick``)
         own = _own_conv_now()
-        if shadow is not None:
-            w, wt = shadow
-        else:
-            w = weight.detach().to(dtype=torch.bfloat16, memory_format=_CL)
-            wt = None
-        flip = own or (_DGRAD_AS_FORWARD and stride == 1 and w.shape[0] == w.shape[1])
+        flip = _dgrad_on_flipped(own, stride, weight.shape[0], weight.shape[1])
+        w, wt, b = _bf16_weights(weight, bias, shadow, flip and x.requires_grad and (own or shadow is None))
         if not flip:
             wt = None
-        elif wt is None and x.requires_grad and (own or shadow is None):
-            wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
-        b = None if bias is None else bias.detach().to(torch.bfloat16)
         if own:
             from . import ops
             y = ops.conv3x3_bf16(x, w, b, stride)
@@ -462,14 +507,7 @@ class _ConvNarrowFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, shadow=None):
         from . import ops
-        # shadow = (w, wt): both made for the caller's whole segment in one launch (``TrainEncoder._tick``)
-        if shadow is not None:
-            w, wt = shadow
-        else:
-            w, wt = weight.detach().to(dtype=torch.bfloat16, memory_format=_CL), None
-        if wt is None and x.requires_grad:
-            wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
-        b = None if bias is None else bias.detach().to(torch.bfloat16)
+        w, wt, b = _bf16_weights(weight, bias, shadow, x.requires_grad)
         y = ops.conv3x3_narrow_bf16(x, w, b)
         ctx.save_for_backward(x, wt if wt is not None else w)
         ctx.has_bias, ctx.flipped, ctx.det = bias is not None, wt is not None, _det_now()
@@ -486,7 +524,7 @@ class _ConvNarrowFn(torch.autograd.Function):
         dx = None
         if ctx.needs_input_grad[0]:
             if not ctx.flipped:                              # (x began to require a gradient after the forward: not a TrainEncoder flow)
-                wt = torch.flip(wt, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
+                wt = _flipped(wt)
             dx = ops.conv3x3_narrow_dgrad_bf16(dy, wt)
         dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)      # the master's own layout
         _wgrad(("3x3n", dy, x, (B, H, W, ci, co), dw))
@@ -499,8 +537,7 @@ def _channel_sums(dy, det: bool = False):
     row -- one launch where ``dy.float().sum((0, 2, 3))`` is a cast of the whole tensor and a reduction.  ``det``: the
     deterministic statistics kernel and a fold launch (no consumer kernel folds this slab)."""
     B, C, H, W = dy.shape
-    c8 = C // 8
-    if dy.is_cuda and dy.dtype == torch.bfloat16 and C % 8 == 0 and c8 <= 256 and 256 % c8 == 0:
+    if dy.is_cuda and dy.dtype == torch.bfloat16 and _stats_channels_ok(C):
         from . import _lib
         R, stream = B * H * W, torch.cuda.current_stream(dy.device).cuda_stream
         form, scratch, stats = _bn_scratch(det, R, C, 1, dy.device)
@@ -519,16 +556,15 @@ def _conv(x, m: nn.Conv2d, dtype, linear_1x1: bool = True, own_wgrad: bool = Tru
     multiple of 64, fp32 mode, the CPU) goes through the stock ops with a differentiable cast of the weight -- except, in the
     deterministic mode under ``set_deterministic_conv("own_all")``, a narrow 3x3 convolution (``_narrow_ok``), which runs on
     ``_ConvNarrowFn``."""
-    fast = own_wgrad and x.is_cuda and dtype == torch.bfloat16 and x.dtype == dtype and _wgrad_ok(m)
-    one = m.kernel_size == (1, 1) and m.padding == (0, 0)
-    if fast and linear_1x1 and one and m.bias is None:
+    route = _conv_route(m, linear_1x1, own_wgrad) if x.is_cuda and dtype == torch.bfloat16 and x.dtype == dtype else None
+    if route == "1x1":
         return _Conv1x1Fn.apply(x.contiguous(memory_format=_CL), m.weight, m.stride[0], shadow)
-    if fast and m.kernel_size == (3, 3) and m.padding == (1, 1):
+    if route == "3x3":
         return _Conv3x3Fn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias, m.stride[0], shadow)
-    if own_wgrad and x.is_cuda and dtype == torch.bfloat16 and x.dtype == dtype and _narrow_conv_now() and _narrow_ok(m):
+    if route == "narrow":
         return _ConvNarrowFn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias, shadow)
     b = None if m.bias is None else m.bias.to(dtype)
-    if linear_1x1 and one and m.groups == 1 and m.dilation == (1, 1):
+    if linear_1x1 and m.kernel_size == (1, 1) and m.padding == (0, 0) and m.groups == 1 and m.dilation == (1, 1):
         if m.stride != (1, 1):
             x = x[:, :, ::m.stride[0], ::m.stride[1]].contiguous(memory_format=_CL)
         w = m.weight.view(m.out_channels, m.in_channels).to(dtype)
@@ -586,7 +622,7 @@ class _DetConvFn(torch.autograd.Function):
         plain = groups == 1 and dilation == (1, 1)
         if need[0]:
             if plain and stride == (1, 1) and padding[0] <= kh - 1 and padding[1] <= kw - 1:
-                wt = torch.flip(w, (2, 3)).transpose(0, 1).contiguous(memory_format=_CL)
+                wt = _flipped(w)
                 if ctx.own and "dgrad" in _DET_AS_GEMM:
                     dx = _conv_as_gemm(dy, wt, None, (1, 1), (kh - 1 - padding[0], kw - 1 - padding[1]))
                 else:
@@ -654,34 +690,43 @@ class TrainEncoder(nn.Module):
         chain = [("stem", ["stem"], None), ("layer1", list(body.layer1), 0), ("layer2", list(body.layer2), 1)]
         chain += [(f"layer3_{i}" if n3 > 1 else "layer3", l3[cuts[i]:cuts[i + 1]], 2 if i == n3 - 1 else None) for i in range(n3)]
         chain.append(("layer4", list(body.layer4), 3))
-        self.__dict__["_chain"] = chain
         self.segments = tuple(c[0] for c in chain) + ("heads",)
-        self.__dict__["_plans"] = {}             # (shape, device) -> _Plan; not module state
-        self.__dict__["_hubs"] = {}              # device index -> {segment: hub leaf}
-        self.__dict__["_pending"] = {}           # segment -> plans whose backward of it ran in the current backward pass
-        self.__dict__["_ticked"] = {}            # id(module) -> covered by the running segment's _tick (rebuilt per call)
-        self.__dict__["_shadows"] = {}           # id(1x1 conv) -> its persistent bf16 weight copy
+        # The call state and the caches: plain attributes (lists, dicts, tuples and ints -- ``nn.Module.__setattr__`` only takes
+        # Parameters, Modules and registered buffers aside), so none of it is module state.
+        self._chain = chain
+        self._plans = {}                         # (shape, device, mode) -> [_Plan]
+        self._hubs = {}                          # device index -> {segment: hub leaf}
+        self._pending = {}                       # segment -> plans whose backward of it ran in the current backward pass
+        self._late = None                        # (segment, plans) whose hand-over waits for the next segment's (``_flush``)
+        self._ticked = {}                        # id(module) -> covered by the running segment's _tick (rebuilt per call)
+        self._bn_groups = 1                      # the running call's ``bn_groups``
+        self._shadows = {}                       # id(1x1 conv) -> its persistent bf16 weight copy
+        self._wcast = {}                         # ids of a segment's 1x1 convs -> the device table of ``_cast_1x1``
+        self._wprep = {}                         # ids of a segment's 3x3 convs + the setting -> ``_prep_3x3``'s table and copies
+        self._storage = None                     # the addresses of parameters and buffers the plans were captured with
+
+    def _invalidate(self, hubs: bool):
+        """Drops what a change of the parameters' storage makes stale: the captured graphs (which hold the old addresses) and
+        the bf16 weight copies with their tables; ``hubs``: the hub leaves too (``_apply``: the module may change device)."""
+        for d in (self._plans, self._shadows, self._pending, self._wprep, self._wcast) + ((self._hubs,) if hubs else ()):
+            d.clear()
 
     def _apply(self, fn, *args, **kwargs):
-        # .to() / .cuda() / .float() re-create the parameters' storage: the captured graphs (which hold the old addresses), the
-        # bf16 weight copies and the hub leaves go; the next forward captures again
-        self._plans.clear(), self._shadows.clear(), self._hubs.clear(), self._pending.clear()
-        self.__dict__.get("_wprep", {}).clear()
-        self.__dict__.get("_wcast", {}).clear()
+        # .to() / .cuda() / .float() re-create the parameters' storage, maybe on another device; the next forward captures again
+        self._invalidate(hubs=True)
         return super()._apply(fn, *args, **kwargs)
 
     # ---- the encoder in segments (plain functions of tensors; parameters come from self.src) ------------------------
     def _cbr(self, x, conv, bn, relu, residual=None, fork=False):
-        t = self.__dict__["_ticked"]
+        t = self._ticked
         y = _conv(x, conv, self.dtype, self.linear_1x1, self.own_wgrad, t.get(id(conv)))
-        return _bn_act(y, bn, relu, residual, self.fused_bn, counted=id(bn) in t, groups=self.__dict__.get("_bn_groups", 1),
-                       fork=fork)
+        return _bn_act(y, bn, relu, residual, self.fused_bn, counted=id(bn) in t, groups=self._bn_groups, fork=fork)
 
     def _tick(self, name: str, x: torch.Tensor, mods=None):
         """Per-segment housekeeping in ONE launch each instead of one per layer: ``num_batches_tracked += 1`` of every
         BatchNorm that takes the fused kernels (116 launches per ResNet-101 step before), and the bf16 copies of the 1x1
-        weights (70).  ``_ticked`` tells ``_cbr`` which modules were covered."""
-        t = self.__dict__["_ticked"]
+        weights (70), and of the 3x3 ones.  ``_ticked`` tells ``_cbr`` which modules were covered."""
+        t = self._ticked
         if not (x.is_cuda and self.dtype == torch.bfloat16 and self.training):
             return
         mods = [m for mod in (self._seg_modules()[name] if mods is None else mods) for m in mod.modules()]
@@ -689,34 +734,30 @@ class TrainEncoder(nn.Module):
             bns = [m for m in mods if isinstance(m, nn.BatchNorm2d) and m.training and _bn_fusable(m)]
             if bns:
                 with torch.no_grad():
-                    torch._foreach_add_([m.num_batches_tracked for m in bns], self.__dict__.get("_bn_groups", 1))
+                    torch._foreach_add_([m.num_batches_tracked for m in bns], self._bn_groups)
                 for m in bns:
                     t[id(m)] = True
-        if self.own_wgrad and self.linear_1x1:
-            convs = [m for m in mods if isinstance(m, nn.Conv2d) and m.kernel_size == (1, 1) and m.padding == (0, 0)
-                     and m.bias is None and _wgrad_ok(m)]
-            if convs:
-                sh = self.__dict__["_shadows"]
-                dst = []
-                for m in convs:
-                    w = sh.get(id(m))
-                    if w is None or w.device != m.weight.device:
-                        w = sh[id(m)] = torch.empty((m.out_channels, m.in_channels), dtype=torch.bfloat16, device=m.weight.device)
-                    dst.append(w)
-                    t[id(m)] = w
-                self._cast_1x1(convs, dst)
-        if self.own_wgrad:
-            narrow = _narrow_conv_now()                      # (the narrow heads share the segment's one wprep launch)
-            convs = [m for m in mods if isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.padding == (1, 1)
-                     and (_wgrad_ok(m) or (narrow and _narrow_ok(m)))]
-            if convs:
-                self._prep_3x3(convs, t)
+        routes = [(m, _conv_route(m, self.linear_1x1, self.own_wgrad)) for m in mods]     # (where ``_conv`` will send them)
+        convs = [m for m, r in routes if r == "1x1"]
+        if convs:
+            dst = []
+            for m in convs:
+                w = self._shadows.get(id(m))
+                if w is None or w.device != m.weight.device:
+                    w = self._shadows[id(m)] = torch.empty((m.out_channels, m.in_channels), dtype=torch.bfloat16,
+                                                           device=m.weight.device)
+                dst.append(w)
+                t[id(m)] = w
+            self._cast_1x1(convs, dst)
+        convs = [m for m, r in routes if r in ("3x3", "narrow")]
+        if convs:                                            # (the narrow heads share the segment's one wprep launch)
+            self._prep_3x3(convs, t)
 
     def _cast_1x1(self, convs, dst):
         """The bf16 copies of a segment's 1x1 weights by ONE launch over a device table (``torch._foreach_copy_`` with a dtype
         change: 20-38 us per segment); inside a capture without a table yet, the multi-tensor copy."""
         from . import _lib
-        memo = self.__dict__.setdefault("_wcast", {})
+        memo = self._wcast
         key = tuple(id(m) for m in convs)
         ptrs = tuple(m.weight.data_ptr() for m in convs) + tuple(d.data_ptr() for d in dst)
         got = memo.get(key)
@@ -741,7 +782,7 @@ class TrainEncoder(nn.Module):
         run on as forward convolutions) by ONE launch over a device table -- a cast, a layout copy and a flip launch per
         convolution before: 99 launches of ~5.5 us in a ResNet-101 forward."""
         from . import _lib
-        memo = self.__dict__.setdefault("_wprep", {})
+        memo = self._wprep
         own = _own_conv_now()                           # every data gradient runs on the flipped weight, whatever the shape
         key = tuple(id(m) for m in convs) + (own, _narrow_conv_now())     # (tables of one setting are not reused under another)
         ptrs = tuple(m.weight.data_ptr() for m in convs)
@@ -755,7 +796,7 @@ class TrainEncoder(nn.Module):
                 co, ci = m.out_channels, m.in_channels
                 w = torch.empty((co, ci, 3, 3), dtype=torch.bfloat16, device=dev, memory_format=_CL)
                 wt = None
-                if own or (_DGRAD_AS_FORWARD and m.stride == (1, 1) and co == ci):
+                if _dgrad_on_flipped(own, m.stride[0], co, ci):
                     wt = torch.empty((ci, co, 3, 3), dtype=torch.bfloat16, device=dev, memory_format=_CL)
                 rec += [m.weight.data_ptr(), w.data_ptr(), 0 if wt is None else wt.data_ptr(), co | (ci << 32), tile]
                 tile += (co // 32) * (ci // 32)
@@ -829,7 +870,13 @@ class TrainEncoder(nn.Module):
     def _seg_heads(self, x2, x3, x4, x5):
         self._tick("heads", x2)
         lv = [self._head_level(k, x, tick=False) for k, x in ((2, x2), (3, x3), (4, x4), (5, x5))]
-        return tuple(p for p, _ in lv) + tuple(sk for _, sk in reversed(lv))       # props 2..5, skips 5..2
+        return self._heads_order(lv)
+
+    @staticmethod
+    def _heads_order(levels):
+        """[``_head_level(k)`` = (prop_k, skip_k) for k = 2..5] -> the heads' outputs as ``_pack`` takes them: props 2..5, skips
+        5..2."""
+        return tuple(p for p, _ in levels) + tuple(sk for _, sk in reversed(levels))
 
     def _seg_modules(self) -> Dict[str, List[nn.Module]]:
         s, body = self.src, self.src.base
@@ -859,7 +906,7 @@ class TrainEncoder(nn.Module):
         for mod in self._seg_modules()[name]:
             for m in mod.modules():
                 if isinstance(m, nn.BatchNorm2d):
-                    n += self.__dict__.get("_bn_groups", 1) * 2 * m.num_features + 64
+                    n += self._bn_groups * 2 * m.num_features + 64
                 elif isinstance(m, nn.Conv2d) and m.bias is not None:
                     n += 2 * m.out_channels + 64            # (its bias gradient: the statistics kernel's sums)
         return n + 1024
@@ -890,9 +937,9 @@ class TrainEncoder(nn.Module):
         assert img.dim() == 4 and img.shape[1] == 3, img.shape           # model_encoder.py:91-92
         bn_groups = int(bn_groups) if self.training else 1
         assert bn_groups >= 1 and img.shape[0] % bn_groups == 0, (img.shape[0], bn_groups)
-        self.__dict__["_bn_groups"] = bn_groups
-        self.__dict__["_ticked"].clear()
-        self.__dict__.pop("_late", None)         # (a hand-over left behind by a backward pass that raised)
+        self._bn_groups = bn_groups
+        self._ticked.clear()
+        self._late = None                        # (a hand-over left behind by a backward pass that raised)
         det = is_deterministic()
         if not (self.graphs and img.is_cuda and self.training and torch.is_grad_enabled()):
             with _det_scope(det):
@@ -900,12 +947,10 @@ class TrainEncoder(nn.Module):
         # the captured graphs hold the ADDRESSES of parameters and buffers: storage that was swapped since (``p.data = ...``,
         # ``load_state_dict(assign=True)``; ``.to()`` goes through ``_apply``) makes every plan stale -- captured again
         fp = tuple(t.data_ptr() for t in self.src.parameters()) + tuple(t.data_ptr() for t in self.src.buffers())
-        if fp != self.__dict__.get("_storage"):
-            if self.__dict__.get("_storage") is not None:
-                self._plans.clear(), self._shadows.clear(), self._pending.clear()
-                self.__dict__.get("_wprep", {}).clear()
-                self.__dict__.get("_wcast", {}).clear()
-            self.__dict__["_storage"] = fp
+        if fp != self._storage:
+            if self._storage is not None:
+                self._invalidate(hubs=False)             # (the hub leaves hold no address of a parameter: they stay)
+            self._storage = fp
         # (the mode is part of the key: a graph captured in one mode never replays in the other)
         conv = get_deterministic_conv() if det else "library"
         key = (tuple(img.shape), img.dtype, img.device.index, self.skips_need_grad, bn_groups, conv,
@@ -925,7 +970,7 @@ class TrainEncoder(nn.Module):
                 import warnings
                 warnings.warn(f"TrainEncoder: graph capture failed ({str(e)[:200]}); this call runs eagerly", RuntimeWarning)
                 torch.cuda.synchronize(img.device)
-                self.__dict__["_ticked"].clear()
+                self._ticked.clear()
                 with _det_scope(det):
                     return self._eager(img)
             plans.append(plan)
@@ -950,13 +995,13 @@ class TrainEncoder(nn.Module):
         backward runs last, is handed over together with its predecessor."""
         hub.grad = None
         plans = self._pending.pop(name, [])
-        late = self.__dict__.pop("_late", None)
+        late, self._late = self._late, None
         if late is not None:
             self._hand_over(*late)
         if not plans:
             return
         if any(p.side is not None and (name in p.wgrad or name == "heads") for p in plans) and name != self.segments[0]:
-            self.__dict__["_late"] = (name, plans)
+            self._late = (name, plans)
         else:
             self._hand_over(name, plans)
 
@@ -972,30 +1017,48 @@ class TrainEncoder(nn.Module):
         _deliver(params, base)
 
 
+def _leaf(t):
+    return t.detach().requires_grad_(True)
+
+
 class _Plan:
     """The captured graphs of one input shape: forward graphs along ``enc.segments`` (stem -> layer1 -> layer2 -> layer3 in parts
     -> layer4 -> heads; each reads its predecessor's static outputs in place), backward graphs in the reverse order (each reads its successors' static input
     gradients in place), all in one memory pool and captured in the order they replay."""
 
     def __init__(self, enc: TrainEncoder, img: torch.Tensor):
-        self.enc = enc
-        dev = img.device
-        chain = enc._chain
+        self.enc, self.dev = enc, img.device
         self.params = enc._seg_params()
         self.static_img = img.detach().clone()
-        pool = torch.cuda.graph_pool_handle()
-        # ---- warm-up (eager, off the capture): MIOpen / hipBLASLt pick their kernels, the allocator reaches its size;
+        self.pool = torch.cuda.graph_pool_handle()
         # BatchNorm's running statistics are put back afterwards (the warm-up and the captures are not training steps)
         bns = [m for m in enc.src.modules() if isinstance(m, nn.BatchNorm2d)]
         keep = [(m.running_mean.clone(), m.running_var.clone(), m.num_batches_tracked.clone()) for m in bns]
         try:
-            self._build(enc, img, dev, chain, pool)
+            self._build()
         finally:                                          # (also when a capture failed: the caller falls back to the eager step)
             for (rm, rv, nb), m in zip(keep, bns):
                 with torch.no_grad():
                     m.running_mean.copy_(rm), m.running_var.copy_(rv), m.num_batches_tracked.copy_(nb)
 
-    def _build(self, enc, img, dev, chain, pool):
+    def _build(self):
+        self._warm_up()
+        levels = self._capture_forward()                   # [(prop, skip)] of the four pyramid levels
+        self._capture_backward(levels)
+        self.tap_of = {name: tap for name, _, tap in self.enc._chain}
+        self.token = torch.zeros((), device=self.dev)      # what the segment nodes hand each other (autograd ordering only)
+        self.zero = torch.zeros((), device=self.dev)       # their gradient: the data moves in the static buffers
+        self.busy = False
+        self.aliased = False                               # some p.grad may still BE one of this plan's static buffers
+        # what the rewrite found: {segment: (memset nodes, memcpy nodes) turned into kernel nodes} per direction
+        tot = lambda gs: tuple(sum(g.rewritten[q] for g in gs) for q in (0, 1))
+        self.rewritten = {"fwd": {"body": tot(self.fwd_body), "heads": tot(self.fwd_head)},
+                          "bwd": dict({k: g.rewritten for k, g in self.bwd.items()}, heads=tot(self.bwd_head)),
+                          "wgrad": {k: tot(gs) for k, gs in self.wgrad.items()}}
+
+    def _warm_up(self):
+        """Eager steps, off the capture: MIOpen / hipBLASLt pick their kernels, the allocator reaches its size."""
+        enc, dev = self.enc, self.dev
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         old = torch.backends.cudnn.benchmark
@@ -1014,39 +1077,35 @@ class _Plan:
             torch.backends.cudnn.benchmark = old
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
-        # ---- forward captures, in replay order; a segment's input is a DETACHED view of its predecessor's output that
-        # requires grad, so that every segment owns a separate autograd graph.  The BODY is captured as one graph per tap
-        # interval (stem + layer1 | layer2 | layer3 | layer4: what the forward needs between two taps; the finer segments only
-        # matter to the backward), the heads as one graph per pyramid level: a level's heads only need that level's tap, so
-        # their graph replays on the SIDE stream beside the deeper body graphs (two graphs on two streams overlap on this
-        # runtime, tools/graph_branch_probe.py); likewise their backward runs beside the body's backward chain.  Everything
-        # that replays on the side stream allocates from a pool of its own.
-        self.bwd, self.ins, self.outs = {}, {}, {}
-        self.arenas = []                                  # statistics scratch of every captured graph (kept alive with it)
-        overlap = enc.overlap_wgrad
-        self.side = torch.cuda.Stream(device=dev) if overlap else None
-        pool_s = torch.cuda.graph_pool_handle()           # the side stream's graphs (head levels, weight gradients)
 
-        def leaf(t):
-            return t.detach().requires_grad_(True)
+    def _arena(self, floats: int) -> _Arena:
+        """The statistics scratch of one captured graph, kept alive with the plan."""
+        self.arenas.append(_Arena(self.dev, floats))
+        return self.arenas[-1]
 
-        def new_arena(floats):
-            a = _Arena(dev, floats)
-            self.arenas.append(a)
-            return a
+    def _capture_forward(self):
+        """The forward captures, in replay order; a segment's input is a DETACHED view of its predecessor's output that
+        requires grad, so that every segment owns a separate autograd graph.  The BODY is captured as one graph per tap
+        interval (stem + layer1 | layer2 | layer3 | layer4: what the forward needs between two taps; the finer segments only
+        matter to the backward), the heads as one graph per pyramid level: a level's heads only need that level's tap, so
+        their graph replays on the SIDE stream beside the deeper body graphs (two graphs on two streams overlap on this
+        runtime, tools/graph_branch_probe.py); likewise their backward runs beside the body's backward chain.  Everything
+        that replays on the side stream allocates from a pool of its own.  -> [(prop, skip)] of the four levels; leaves the
+        segments' static inputs and outputs in ``ins`` / ``outs``."""
+        enc, chain = self.enc, self.enc._chain
+        self.ins, self.outs, self.arenas = {}, {}, []
+        self.side = torch.cuda.Stream(device=self.dev) if enc.overlap_wgrad else None
+        self.pool_s = torch.cuda.graph_pool_handle()      # the side stream's graphs (head levels, weight gradients)
         head_floats = enc._arena_floats("heads", False)
         self.fwd_body, self.fwd_head = [], []             # per tap interval: the body graph, the level's heads graph
         taps, hin, lv, x, k_ = [None] * 4, [None] * 4, [None] * 4, self.static_img, 0
         while k_ < len(chain):
             g = SafeGraph()
-            todo = []
-            for q in range(k_, len(chain)):
-                todo.append(chain[q])
-                if chain[q][2] is not None:
-                    break
-            with g.capture(pool=pool), _arena_scope(new_arena(sum(enc._arena_floats(n, False) for n, _, _ in todo))):
+            end = next(q for q in range(k_, len(chain)) if chain[q][2] is not None) + 1      # (the chain ends with a tap: layer4)
+            todo = chain[k_:end]                                                             # the segments up to the next tap
+            with g.capture(pool=self.pool), _capture_scope(self._arena(sum(enc._arena_floats(n, False) for n, _, _ in todo))):
                 for (name, _, tap) in todo:
-                    inp = x if name == chain[0][0] else leaf(x)
+                    inp = x if name == chain[0][0] else _leaf(x)
                     (x,) = enc._seg_body(name, inp)
                     self.ins[name], self.outs[name] = (inp,), (x,)
             tap = todo[-1][2]
@@ -1054,76 +1113,76 @@ class _Plan:
             k_ += len(todo)
             self.fwd_body.append(g)
             gh_ = SafeGraph()
-            hin[tap] = leaf(x)
-            with gh_.capture(pool=pool_s), _arena_scope(new_arena(head_floats)):
+            hin[tap] = _leaf(x)
+            with gh_.capture(pool=self.pool_s), _capture_scope(self._arena(head_floats)):
                 lv[tap] = enc._head_level(tap + 2, hin[tap])
             self.fwd_head.append(gh_)
-        heads = tuple(p_ for p_, _ in lv) + tuple(sk for _, sk in reversed(lv))     # props 2..5, skips 5..2 (as _seg_heads)
-        self.ins["heads"], self.outs["heads"] = tuple(hin), heads
+        self.heads = enc._heads_order(lv)
+        self.ins["heads"], self.outs["heads"] = tuple(hin), self.heads
+        self.taps = taps
         self.ev_tap = [torch.cuda.Event() for _ in range(4)]
         self.ev_heads_fwd = torch.cuda.Event()
-        # ---- backward captures, reverse order.  Gradients that arrive from outside: one static buffer per head output that
-        # requires grad.  Gradients between segments: the tensors autograd.grad returned in the successor's capture.
-        self.gout = [torch.zeros_like(o) if o.requires_grad else None for o in heads]
-        self.pgrads = {}
+        return lv
 
-        # weight gradients on a side stream (``overlap_wgrad``): a segment's backward is captured as TWO graphs -- the chain
-        # (BatchNorm backward, data gradients, everything the next layer down waits for) and, from the launches recorded while
-        # that capture ran, the weight gradients.  On replay the second graph runs on a side stream beside the NEXT segment's
-        # chain.  The recorded operands (dY, X) are kept alive for the plan's lifetime -- the chain of the next segment must
-        # not reuse their memory while the side stream reads it.
-        self.wgrad, self.keep = {}, {}
+    def _capture_bwd(self, name, outs, make_gouts, inputs, ps, chain_pool):
+        """One backward chain.  -> (gradients of ``inputs``, gradients of ``ps``, chain graph, recorded weight-gradient launches
+        or None).  ``make_gouts``: called INSIDE the capture (sums of gradient buffers of two consumers are part of the graph)."""
+        wrt = [t for t in inputs if t.requires_grad] + ps
+        g = SafeGraph()
+        enc = self.enc
+        with g.capture(pool=chain_pool), _capture_scope(self._arena(enc._arena_floats(name, True)), enc.overlap_wgrad) as cap:
+            grads = list(torch.autograd.grad(outs, wrt, make_gouts(), allow_unused=True))
+            # a gradient is handed over in its PARAMETER's layout (the multi-tensor optimisers refuse anything else:
+            # "params, grads ... must have same dtype, device, and layout"): the stock convolutions' weight gradients
+            # come back channels-last strided (the 7x7 stem, widths the library's kernels do not take)
+            for q, (t, g_) in enumerate(zip(wrt, grads)):
+                if g_ is not None and isinstance(t, nn.Parameter) and (g_.stride() != t.stride() or g_.dtype != t.dtype):
+                    grads[q] = torch.empty_like(t).copy_(g_)
+        n_in = len(wrt) - len(ps)
+        return grads[:n_in], list(grads[n_in:]), g, cap.records
+
+    def _capture_wgrad(self, name, records):
+        """The weight gradients a chain's capture recorded, as a graph of the side stream's pool (None without any).  The
+        recorded operands (dY, X) are kept alive for the plan's lifetime -- the chain of the next segment must not reuse their
+        memory while the side stream reads it."""
+        if not records:
+            return None
+        gw = SafeGraph()
+        with gw.capture(pool=self.pool_s), _capture_scope():
+            for rec in records:
+                _wgrad_launch(rec)
+        self.keep.setdefault(name, []).extend(records)
+        return gw
+
+    def _capture_backward(self, levels):
+        """The backward captures, reverse order.  Gradients that arrive from outside: one static buffer per head output that
+        requires grad.  Gradients between segments: the tensors autograd.grad returned in the successor's capture.
+
+        Weight gradients on a side stream (``overlap_wgrad``): a segment's backward is captured as TWO graphs -- the chain
+        (BatchNorm backward, data gradients, everything the next layer down waits for) and, from the launches recorded while
+        that capture ran, the weight gradients.  On replay the second graph runs on a side stream beside the NEXT segment's
+        chain."""
+        enc, chain, heads, hin = self.enc, self.enc._chain, self.heads, self.ins["heads"]
+        self.gout = [torch.zeros_like(o) if o.requires_grad else None for o in heads]
+        self.bwd, self.pgrads, self.wgrad, self.keep = {}, {}, {}, {}
         self.ev_chain = {n: torch.cuda.Event() for n in enc.segments}
         self.ev_wgrad = {n: torch.cuda.Event() for n in enc.segments}
-
-        def capture_bwd(name, outs, make_gouts, inputs, ps, chain_pool):
-            """-> (gradients of ``inputs``, gradients of ``ps``, chain graph, recorded weight-gradient launches or None).
-            ``make_gouts``: called INSIDE the capture (sums of gradient buffers of two consumers are part of the graph)."""
-            global _DEFER
-            wrt = [t for t in inputs if t.requires_grad] + ps
-            g = SafeGraph()
-            _DEFER = [] if overlap else None
-            try:
-                with g.capture(pool=chain_pool), _arena_scope(new_arena(enc._arena_floats(name, True))):
-                    grads = list(torch.autograd.grad(outs, wrt, make_gouts(), allow_unused=True))
-                    # a gradient is handed over in its PARAMETER's layout (the multi-tensor optimisers refuse anything else:
-                    # "params, grads ... must have same dtype, device, and layout"): the stock convolutions' weight gradients
-                    # come back channels-last strided (the 7x7 stem, widths the library's kernels do not take)
-                    for q, (t, g_) in enumerate(zip(wrt, grads)):
-                        if g_ is not None and isinstance(t, nn.Parameter) and (g_.stride() != t.stride() or g_.dtype != t.dtype):
-                            grads[q] = torch.empty_like(t).copy_(g_)
-                records = _DEFER
-            finally:
-                _DEFER = None
-            n_in = len(wrt) - len(ps)
-            return grads[:n_in], list(grads[n_in:]), g, records
-
-        def capture_wgrad(name, records):
-            if not records:
-                return None
-            gw = SafeGraph()
-            with gw.capture(pool=pool_s):
-                for rec in records:
-                    _wgrad_launch(rec)
-            self.keep.setdefault(name, []).extend(records)
-            return gw
         # the heads, level by level, deepest first (the order the body's backward needs their tap gradients in)
         self.bwd_head, self.ev_bh = [None] * 4, [torch.cuda.Event() for _ in range(4)]
         gh, hgrads, hrec = [None] * 4, {}, []
         where = {id(o): n for n, o in enumerate(heads)}
         for tap in (3, 2, 1, 0):
-            prop, skip = lv[tap]
-            outs_ = [o for o in (prop, skip) if o.requires_grad]
+            outs_ = [o for o in levels[tap] if o.requires_grad]
             gbuf = [self.gout[where[id(o)]] for o in outs_]
             ps = enc._head_params(tap + 2)
-            (gin,), pg, g, records = capture_bwd("heads", outs_, lambda gbuf=gbuf: list(gbuf), (hin[tap],), ps, pool_s)
+            (gin,), pg, g, records = self._capture_bwd("heads", outs_, lambda gbuf=gbuf: list(gbuf), (hin[tap],), ps, self.pool_s)
             gh[tap], self.bwd_head[tap] = gin, g
             hgrads.update({id(p_): g_ for p_, g_ in zip(ps, pg)})
             hrec.append(records)
         self.pgrads["heads"] = [hgrads.get(id(p_)) for p_ in self.params["heads"]]
         # (captured in the order they replay on the side stream -- the four chains, then the four weight-gradient graphs: graphs
         # that share a pool replay in their capture order)
-        hw = [g for g in (capture_wgrad("heads", r) for r in hrec) if g is not None]
+        hw = [g for g in (self._capture_wgrad("heads", r) for r in hrec) if g is not None]
         if hw:
             self.wgrad["heads"] = hw
         # a tap feeds the next body segment AND the heads: its gradient is the sum of the two static buffers (one add, captured
@@ -1133,36 +1192,30 @@ class _Plan:
             name, _, tap = chain[k_]
             terms = [t for t in (g_next, gh[tap] if tap is not None else None) if t is not None]
             make = (lambda terms=terms: [terms[0] + terms[1]]) if len(terms) == 2 else (lambda terms=terms: [terms[0]])
-            gin, pg, g, records = capture_bwd(name, list(self.outs[name]), make, self.ins[name] if k_ > 0 else (),
-                                              self.params[name], pool)
+            gin, pg, g, records = self._capture_bwd(name, list(self.outs[name]), make, self.ins[name] if k_ > 0 else (),
+                                                    self.params[name], self.pool)
             self.bwd[name], self.pgrads[name] = g, pg
-            gw = capture_wgrad(name, records)
+            gw = self._capture_wgrad(name, records)
             if gw is not None:
                 self.wgrad[name] = [gw]
             g_next = gin[0] if k_ > 0 else None
-        self.tap_of = {name: tap for name, _, tap in chain}
-        self.result = TrainEncoder._pack(taps, heads)
-        self.heads = heads
-        self.token = torch.zeros((), device=dev)           # what the segment nodes hand each other (autograd ordering only)
-        self.zero = torch.zeros((), device=dev)            # their gradient: the data moves in the static buffers
-        self.busy = False
-        self.aliased = False                               # some p.grad may still BE one of this plan's static buffers
-        # what the rewrite found: {segment: (memset nodes, memcpy nodes) turned into kernel nodes} per direction
-        tot = lambda gs: tuple(sum(g.rewritten[q] for g in gs) for q in (0, 1))
-        self.rewritten = {"fwd": {"body": tot(self.fwd_body), "heads": tot(self.fwd_head)},
-                          "bwd": dict({k: g.rewritten for k, g in self.bwd.items()}, heads=tot(self.bwd_head)),
-                          "wgrad": {k: tot(gs) for k, gs in self.wgrad.items()}}
+
+    def _unalias(self, names):
+        """A ``p.grad`` that still IS one of this plan's static gradient buffers of the segments ``names`` moves into a tensor
+        of its own (gradient accumulation: the usual flow, gradients set to None or re-pointed at bucket views between steps,
+        never finds one)."""
+        for name in names:
+            for p, g in zip(self.params[name], self.pgrads[name]):
+                if g is not None and p.grad is not None and p.grad.data_ptr() == g.data_ptr():
+                    p.grad = p.grad.clone()
 
     def run(self, img):
         enc = self.enc
         if self.aliased:
             # the last backward handed this plan's static gradient buffers out as ``p.grad``.  The pool reuses that memory for
             # activations of the FORWARD graphs (a replayed step needs the two at different times), so a gradient that is still
-            # in place now -- gradient accumulation: no zero_grad / optimiser step in between -- moves into its own tensor first
-            for name in enc.segments:
-                for p, g in zip(self.params[name], self.pgrads[name]):
-                    if g is not None and p.grad is not None and p.grad.data_ptr() == g.data_ptr():
-                        p.grad = p.grad.clone()
+            # in place now -- no zero_grad / optimiser step in between -- moves out first
+            self._unalias(enc.segments)
             self.aliased = False
         self.static_img.copy_(img)
         main = torch.cuda.current_stream(img.device)
@@ -1186,8 +1239,7 @@ class _Plan:
         outs = _SegFn.apply(self, "heads", token, hubs["heads"])
         # (the body's own levels are handed out detached: inside the graphs they are inputs of the heads, not autograd leaves
         # of the caller)
-        return {"backbone_feature": tuple(outs[:4]), "refine_input_feat": tuple(outs[4:]),
-                "body_feature": tuple(t.detach() for t in self.result["body_feature"])}
+        return enc._pack([t.detach() for t in self.taps], outs)
 
     def backward_segment(self, name: str, grads: Sequence[Optional[torch.Tensor]] = ()):
         if name == "heads":
@@ -1202,21 +1254,23 @@ class _Plan:
                     g.copy_(gi)
                 k += 1
         # gradient accumulation (a second backward before zero_grad): a gradient that still IS this graph's static buffer
-        # would be overwritten by the replay -- it moves into its own tensor first (the usual flow, gradients set to None or
-        # re-pointed at bucket views between steps, never takes this path)
-        for p, g in zip(self.params[name], self.pgrads[name]):
-            if g is not None and p.grad is not None and p.grad.data_ptr() == g.data_ptr():
-                p.grad = p.grad.clone()
-        main = torch.cuda.current_stream(self.static_img.device)
-        side = self.side
-        if name == "heads":
-            # the heads' backward, deepest level first, on the side stream: the body's chain only waits for the level whose tap
-            # gradient it needs next
+        # would be overwritten by the replay
+        self._unalias((name,))
+        main, side, heads = torch.cuda.current_stream(self.dev), self.side, name == "heads"
+        if not heads:
+            tap = self.tap_of[name]
+            if side is not None and tap is not None:
+                main.wait_event(self.ev_bh[tap])
+            self.bwd[name].replay()
+        if heads or name in self.wgrad:
+            # what runs on the side stream: a segment's weight-gradient graphs, beside the next segment's chain -- and in front of
+            # them the heads' whole backward, deepest level first (the body's chain only waits for the level whose tap gradient
+            # it needs next)
             if side is not None:
-                self.ev_chain[name].record(main)           # (the incoming gradients are in their static buffers)
+                self.ev_chain[name].record(main)           # (heads: the incoming gradients are in their static buffers)
                 side.wait_event(self.ev_chain[name])
             with (torch.cuda.stream(side) if side is not None else _NO_CTX):
-                for tap in (3, 2, 1, 0):
+                for tap in ((3, 2, 1, 0) if heads else ()):
                     self.bwd_head[tap].replay()
                     if side is not None:
                         self.ev_bh[tap].record(side)
@@ -1224,28 +1278,12 @@ class _Plan:
                     gw.replay()
                 if side is not None:
                     self.ev_wgrad[name].record(side)
-        else:
-            tap = self.tap_of[name]
-            if side is not None and tap is not None:
-                main.wait_event(self.ev_bh[tap])
-            self.bwd[name].replay()
-            if name in self.wgrad:
-                if side is None:
-                    for gw in self.wgrad[name]:
-                        gw.replay()
-                else:
-                    self.ev_chain[name].record(main)
-                    side.wait_event(self.ev_chain[name])
-                    with torch.cuda.stream(side):
-                        for gw in self.wgrad[name]:
-                            gw.replay()
-                        self.ev_wgrad[name].record(side)
-        self.enc.__dict__["_pending"].setdefault(name, []).append(self)
+        self.enc._pending.setdefault(name, []).append(self)
 
     def wait_wgrad(self, name: str):
         """The current stream waits for this plan's weight-gradient graph of ``name`` (a no-op without one)."""
         if self.side is not None and (name in self.wgrad or name == "heads"):
-            torch.cuda.current_stream(self.static_img.device).wait_event(self.ev_wgrad[name])
+            torch.cuda.current_stream(self.dev).wait_event(self.ev_wgrad[name])
 
 
 def _deliver(params, grads):

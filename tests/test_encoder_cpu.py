@@ -166,6 +166,10 @@ def test_train_encoder_segments_compute_the_encoder_on_the_cpu():
     te = TrainEncoder(enc, dtype=torch.float32)
     img = torch.randn(2, 3, 64, 96)
     o, r = te(img), ref(img)
+    # the wrapper's own state (plans, caches, the running call) is no module state: only the wrapped encoder's is
+    assert (list(te.state_dict()), [id(p) for p in te.parameters()], [id(b) for b in te.buffers()], list(te.modules())) == \
+        (["src." + k for k in enc.state_dict()], [id(p) for p in enc.parameters()], [id(b) for b in enc.buffers()],
+         [te] + list(enc.modules()))
     outs = lambda f: f["backbone_feature"] + f["refine_input_feat"]
     for a, b in zip(outs(o), outs(r)):
         assert a.shape == b.shape and float((a.float() - b).abs().max()) <= 2e-3 * float(b.abs().max())

@@ -258,7 +258,7 @@ def _seg_run(te, name, x, cots, det):
     params, bufs = _seg_names(te, name)
     before = {n: enc.get_buffer(n).clone() for n in bufs}
     enc.zero_grad(set_to_none=True)
-    te.__dict__["_ticked"].clear()
+    te._ticked.clear()
     xg = x.clone().requires_grad_(True)
     with _modes(det):
         outs = te._head_level(int(name[5:]), xg) if name.startswith("heads") else te._seg_body(name, xg)
