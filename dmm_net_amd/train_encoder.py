@@ -750,7 +750,7 @@ class TrainEncoder(nn.Module):
                 t[id(m)] = w
             self._cast_1x1(convs, dst)
         convs = [m for m, r in routes if r in ("3x3", "narrow")]
-        if convs:                                            # (the narrow heads share the segment's one wprep launch)
+        if convs:                                            # (the narrow heads share their level's one wprep launch)
             self._prep_3x3(convs, t)
 
     def _cast_1x1(self, convs, dst):
@@ -789,7 +789,12 @@ class TrainEncoder(nn.Module):
         got = memo.get(key)
         if got is None or got[0] != ptrs:
             if torch.cuda.is_current_stream_capturing():
-                return                                   # (no table yet and no upload inside a capture: per-convolution copies)
+                # no table yet and no upload inside a capture: per-convolution copies.  Copies an earlier tick of these
+                # modules left in ``t`` (the warm-up's) go: nothing in THIS graph would refresh them, and its replays would
+                # read the weights of the day of the capture
+                for m in convs:
+                    t.pop(id(m), None)
+                return
             dev = convs[0].weight.device
             rec, pairs, tile = [], [], 0
             for m in convs:
@@ -846,12 +851,13 @@ class TrainEncoder(nn.Module):
         out = self._cbr(x, head[0], head[1], True)                       # base.py:43-54: conv -> BN -> ReLU -> conv -> BN
         return self._cbr(out, head[3], head[4], False)
 
-    def _head_level(self, k: int, x, tick: bool = True):
+    def _head_level(self, k: int, x):
         """The heads of ONE pyramid level (k = 2..5) on that level's tap: ``prop_k`` (-> fp32 NCHW: what the ROI feature kernel,
-        forward and backward, works on) and the decoder's skip projection ``bn_k(sk_k(x))``.  -> (prop, skip)"""
+        forward and backward, works on) and the decoder's skip projection ``bn_k(sk_k(x))``.  -> (prop, skip).  The level ticks
+        for itself, eagerly and in a plan's capture alike: the warm-up of a plan then makes the weight tables the level's
+        captured graph launches from (``_prep_3x3`` uploads none inside a capture)."""
         s = self.src
-        if tick:
-            self._tick("heads", x, mods=self._head_modules(k))
+        self._tick("heads", x, mods=self._head_modules(k))
         prop = self._head(x, getattr(s, f"prop{k}"))
         with (torch.enable_grad() if self.skips_need_grad else torch.no_grad()):
             skip = self._cbr(x, getattr(s, f"sk{k}"), getattr(s, f"bn{k}"), False)
@@ -868,8 +874,7 @@ class TrainEncoder(nn.Module):
         return [p for m in mods for p in m.parameters() if p.requires_grad]
 
     def _seg_heads(self, x2, x3, x4, x5):
-        self._tick("heads", x2)
-        lv = [self._head_level(k, x, tick=False) for k, x in ((2, x2), (3, x3), (4, x4), (5, x5))]
+        lv = [self._head_level(k, x) for k, x in ((2, x2), (3, x3), (4, x4), (5, x5))]
         return self._heads_order(lv)
 
     @staticmethod

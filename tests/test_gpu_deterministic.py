@@ -354,28 +354,75 @@ def test_train_encoder_same_checksum_in_two_processes():
 
 
 # ---- a config-4 style step through DMM_Model ---------------------------------------------------------------------------
-def _cfg4_run(steps=3):
+def _cfg4_run(steps=3, data_seed=4, backend="nccl", world=1):
     """ResNet-50 TrainEncoder, 2 videos x clip 2 at 128 x 224 -> ROI features -> DMM_Model with targets -> soft IoU + match
-    loss; GradBucketer at world 1; Adam.  -> (losses, parameter checksum bytes as hex).  Run under the deterministic mode."""
+    loss; GradBucketer; Adam.  -> (losses, parameter checksum bytes as hex, parameters).  Run under the deterministic mode.
+    ``world`` = 1: a process group of one RCCL rank, made here unless there is one.  ``world`` > 1: this process is one rank of
+    a launcher's group (``backend``: gloo when the ranks share a device); ``data_seed`` is the rank's own."""
     import socket
     import torch.distributed as dist
-    from dmm_net_amd.distributed import GradBucketer, init_from_env
+    from dmm_net_amd.distributed import init_from_env
+    own_pg = not dist.is_initialized()
+    if own_pg:
+        torch.cuda.set_device(0)
+        if world == 1:
+            sk = socket.socket()
+            sk.bind(("127.0.0.1", 0))
+            port = sk.getsockname()[1]
+            sk.close()
+            os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1")
+        init_from_env(backend, torch.device(DEV))
+    assert dist.get_world_size() == world, (dist.get_world_size(), world)
+    try:
+        gen = _cfg4_steps(steps, data_seed, True)
+        try:
+            while True:
+                next(gen)
+        except StopIteration as done:
+            return done.value
+    finally:
+        if own_pg:
+            dist.destroy_process_group()
+
+
+def _cfg4_reference(steps, data_seeds):
+    """The step of ``_cfg4_run`` for ``len(data_seeds)`` ranks in ONE process without a process group: one copy per rank on its
+    own data, in lockstep; after every backward the gradients are replaced by their mean under GradBucketer's contract
+    (``dist_step.mean_of``: None everywhere stays None, None somewhere counts as zeros, (g0 + g1) / 2 in fp32), then every
+    copy takes its Adam step.  Every copy keeps a random-number state of its own.  -> [``_cfg4_run``'s result per rank]."""
+    from dist_step import mean_of
+    gens = [_cfg4_steps(steps, seed, False) for seed in data_seeds]
+    rng, results = [None] * len(gens), [None] * len(gens)
+    while any(r is None for r in results):
+        waiting = []
+        for k, gen in enumerate(gens):
+            if rng[k] is not None:
+                torch.set_rng_state(rng[k][0]), torch.cuda.set_rng_state(rng[k][1], DEV)
+            try:
+                waiting.append(next(gen))
+            except StopIteration as done:
+                results[k] = done.value
+            rng[k] = (torch.get_rng_state(), torch.cuda.get_rng_state(DEV))
+        assert len(waiting) in (0, len(gens))
+        for ps in zip(*waiting):
+            mean = mean_of([p.grad for p in ps])
+            for p in ps:
+                p.grad = None if mean is None else mean.clone()
+    return results
+
+
+def _cfg4_steps(steps, data_seed, bucketer):
+    """The step itself, as a generator.  ``bucketer``: the gradients go through ``GradBucketer(overlap=True)`` + ``finish()`` and
+    nothing is yielded; otherwise the parameter list is yielded after every backward and the caller puts the reduced gradients
+    into ``p.grad`` before the Adam step.  Returns ``_cfg4_run``'s result."""
+    from dmm_net_amd.distributed import GradBucketer
     from dmm_net_amd.dmm_model import DMM_Model
     from dmm_net_amd.encoder import FeatureEncoder
     from dmm_net_amd.proposals import SimpleBoxList
     from dmm_net_amd.roi_features import FeatureExtractor
-    own_pg = not dist.is_initialized()
-    if own_pg:
-        sk = socket.socket()
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
-        sk.close()
-        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1")
-        torch.cuda.set_device(0)
-        init_from_env("nccl", torch.device(DEV))
     NV, T, F, P, H, W = 2, 2, 4, 30, 128, 224
     torch.manual_seed(31)
-    g = torch.Generator(device=DEV).manual_seed(4)
+    g = torch.Generator(device=DEV).manual_seed(data_seed)
     enc = FeatureEncoder("resnet50").to(DEV).train()
     run_enc = TrainEncoder(enc, skips_need_grad=False)
     cfgs = {"matching": {"algo": "relax"}, "relax_max_iter": 10, "relax_proj_iter": 5, "relax_learning_rate": 0.1,
@@ -383,7 +430,7 @@ def _cfg4_run(steps=3):
     model = DMM_Model(cfgs, is_test=0, feature_extractor=FeatureExtractor())
     params = list(enc.get_skip_params()) + list(enc.get_backbone_para())
     opt = torch.optim.Adam(params, lr=1e-4)
-    gb = GradBucketer(params, bucket_mb=64.0, overlap=True)
+    gb = GradBucketer(params, bucket_mb=64.0, overlap=True) if bucketer else None
     frames = torch.randn(NV, T, 3, H, W, generator=g, device=DEV)
     valid = torch.zeros(NV, F, device=DEV)
     valid[0, :3], valid[1, :2] = 1, 1
@@ -422,16 +469,18 @@ def _cfg4_run(steps=3):
                 mask_last = last.detach()
             loss = total / T
             loss.backward()
-            gb.finish()
+            if gb is not None:
+                gb.finish()
+            else:
+                yield params
             opt.step()
             losses.append(float(loss))
         torch.cuda.synchronize()
         chk = torch.stack([p.detach().double().sum() for p in enc.parameters()] + [b.double().sum() for b in enc.buffers()])
         return losses, chk.cpu().numpy().tobytes().hex(), [p.detach().clone() for p in enc.parameters()]
     finally:
-        gb.remove_hooks()
-        if own_pg:
-            dist.destroy_process_group()
+        if gb is not None:
+            gb.remove_hooks()
 
 
 _CHILD_CFG4 = r"""
