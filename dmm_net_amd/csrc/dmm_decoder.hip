@@ -7,6 +7,7 @@
 // evaluations of a level share one pre-activation; each mask plane's share is a 36-weight stencil per hidden channel),
 // the align-corners bilinear upsample written into a channel range of the next level's convolution input, and the
 // finish (upsample to image size, sigmoid, the valid-gated history write and the zero rows of the padded output).
+// For training on the fused form: the backward of the cell (12e), which recomputes the gates, and its fixed-order fold.
 #include "dmm_common.h"
 
 #include <math.h>
@@ -146,6 +147,200 @@ __global__ __launch_bounds__(256) void clstm_gates_kernel(
     }
 }
 
+// ---- (12e) backward of the fused LSTM cell -----------------------------------------------------------------------------
+// The forward's geometry: a lane owns one position and the kGateCh channels of its group.  Nothing of the forward is saved:
+// the gates are recomputed with the forward's expressions in the forward's order.  ds[e][q] is the gradient of the gate
+// pre-activation q of evaluation e = 0, 1, 2 (mask planes 0, 2, 1).  d_pre and d_cell_prev are per lane.  The two reductions
+// go through the workspace and are folded in a fixed order by clstm_gates_bwd_fold_kernel (no atomics):
+//   d_masks   each lane leaves its 27 tap sums  tap[k][j] = sum over (q, channels of the group) ds_{q,k} * w_mask[q, ch, j]
+//             in ws_m [groups][B][3][9][h * w]; the fold gathers them from the nine source positions, groups ascending;
+//   d_w_mask  36 sums per channel over the workgroup's 256 positions (planes in evaluation order inside the lane, the
+//             64-lane tree of wave_sum_rows, the four waves in order through LDS) go to ws_w [position blocks][4 * Hd * 9];
+//             the fold adds the position blocks in ascending order.
+// Lanes past the last position hold ds = 0 and take part in the wave sums.
+__device__ __forceinline__ int eval_plane(int e) { return e == 0 ? 0 : (e == 1 ? 2 : 1); }
+
+template <bool WANT_M, bool WANT_W>
+__global__ __launch_bounds__(256) void clstm_gates_bwd_kernel(
+    const float *__restrict__ pre0, const float *__restrict__ pre1, const float *__restrict__ pre2, int64_t sb0, int64_t sb1,
+    int64_t sb2, const float *__restrict__ masks, int64_t sb_m, const float *__restrict__ wm, const float *__restrict__ c_prev,
+    const float *__restrict__ d_hidden, const float *__restrict__ d_cell, int B, int Hd, int h, int w,
+    float *__restrict__ d_pre, float *__restrict__ d_cprev, float *__restrict__ ws_m, float *__restrict__ ws_w) {
+    __shared__ float s_w[WANT_W ? kGateCh * 4 * 36 : 1];
+    __shared__ float s_wm[kGateCh * 36];               // the group's stencil weights: read as vector operands (36 wave-uniform
+    const int hw = h * w;                              // scalars per channel, on top of twelve pointers, do not fit the SGPRs)
+    const int ch0 = blockIdx.y * kGateCh;
+    if (threadIdx.x < kGateCh * 36) {
+        const int c = threadIdx.x / 36, i = threadIdx.x - c * 36;
+        s_wm[threadIdx.x] = ch0 + c < Hd ? wm[(int64_t)((i / 9) * Hd + ch0 + c) * 9 + (i % 9)] : 0.0f;
+    }
+    __syncthreads();
+    const int pos = blockIdx.x * 256 + threadIdx.x;
+    const bool valid = pos < B * hw;
+    const int b = valid ? pos / hw : 0, p = valid ? pos - b * hw : 0, y = p / w, x = p - y * w;
+    float mk[3][9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float *mp = masks + (int64_t)b * sb_m + (int64_t)k * hw;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int yy = y + dy - 1, xx = x + dx - 1;
+                mk[k][dy * 3 + dx] = (valid && yy >= 0 && yy < h && xx >= 0 && xx < w) ? mp[yy * w + xx] : 0.0f;
+            }
+    }
+    float tap[3][9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int j = 0; j < 9; ++j) tap[k][j] = 0.0f;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c = 0; c < kGateCh && ch0 + c < Hd; ++c) {
+        const int ch = ch0 + c;
+        float ds[3][4];
+#pragma unroll
+        for (int e = 0; e < 3; ++e)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) ds[e][q] = 0.0f;
+        if (valid) {
+            float g[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int64_t off = (int64_t)(q * Hd + ch) * hw + p;
+                float v = pre0[(int64_t)b * sb0 + off];
+                if (pre1) v = v + pre1[(int64_t)b * sb1 + off];
+                if (pre2) v = v + pre2[(int64_t)b * sb2 + off];
+                g[q] = v;
+            }
+            const int64_t so = ((int64_t)b * Hd + ch) * hw + p;
+            const float cp = c_prev ? c_prev[so] : 0.0f;
+            const float u = d_hidden ? d_hidden[so] / 3.0f : 0.0f;
+            const float v = d_cell ? d_cell[so] / 3.0f : 0.0f;
+            float dcr[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) {
+                const int k = eval_plane(e);
+                float s[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float *wq = s_wm + c * 36 + q * 9;
+                    float a = 0.0f;
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) a = __builtin_fmaf(wq[j], mk[k][j], a);
+                    s[q] = g[q] + a;
+                }
+                const float gi = sigmoid_f32(s[0]), gr = sigmoid_f32(s[1]), go = sigmoid_f32(s[2]), gc = tanhf(s[3]);
+                const float ck = (gr * cp) + (gi * gc);
+                const float tk = tanhf(ck);
+                const float dc = v + (u * go) * (1.0f - tk * tk);
+                ds[e][0] = ((dc * gc) * gi) * (1.0f - gi);
+                ds[e][1] = c_prev ? ((dc * cp) * gr) * (1.0f - gr) : 0.0f;
+                ds[e][2] = ((u * tk) * go) * (1.0f - go);
+                ds[e][3] = (dc * gi) * (1.0f - gc * gc);
+                dcr[e] = dc * gr;
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                d_pre[((int64_t)b * 4 * Hd + (int64_t)(q * Hd + ch)) * hw + p] = (ds[0][q] + ds[1][q]) + ds[2][q];
+            if (d_cprev) d_cprev[so] = (dcr[0] + dcr[1]) + dcr[2];
+        }
+        if (WANT_M) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float *wq = s_wm + c * 36 + q * 9;
+#pragma unroll
+                for (int e = 0; e < 3; ++e)
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) tap[eval_plane(e)][j] = __builtin_fmaf(ds[e][q], wq[j], tap[eval_plane(e)][j]);
+            }
+        }
+        if (WANT_W) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                float r[9];
+#pragma unroll
+                for (int j = 0; j < 9; ++j) {
+                    float a = ds[0][q] * mk[0][j];
+                    a = __builtin_fmaf(ds[1][q], mk[2][j], a);
+                    r[j] = __builtin_fmaf(ds[2][q], mk[1][j], a);
+                }
+                wave_sum_rows<9>(r);
+                if (lane == 0) {
+#pragma unroll
+                    for (int j = 0; j < 9; ++j) s_w[(c * 4 + wave) * 36 + q * 9 + j] = r[j];
+                }
+            }
+        }
+    }
+    if (WANT_M && valid) {
+        float *t = ws_m + ((int64_t)blockIdx.y * B + b) * 27 * hw + p;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int j = 0; j < 9; ++j) t[(int64_t)(k * 9 + j) * hw] = tap[k][j];
+    }
+    if (WANT_W) {
+        __syncthreads();
+        const int c = threadIdx.x / 36, i = threadIdx.x - c * 36;
+        if (c < kGateCh && ch0 + c < Hd) {
+            const float *sp = s_w + c * 4 * 36 + i;
+            const float a = ((sp[0] + sp[36]) + sp[72]) + sp[108];
+            ws_w[(int64_t)blockIdx.x * 36 * Hd + (int64_t)((i / 9) * Hd + ch0 + c) * 9 + (i % 9)] = a;
+        }
+    }
+}
+
+// Workgroups 0 .. blocks_m - 1: one lane per element of d_masks; the rest: one lane per element of d_w_mask.
+__global__ __launch_bounds__(256) void clstm_gates_bwd_fold_kernel(const float *__restrict__ ws_m, const float *__restrict__ ws_w,
+                                                                   int B, int Hd, int h, int w, int groups, int pos_blocks,
+                                                                   unsigned blocks_m, float *__restrict__ d_masks,
+                                                                   float *__restrict__ d_wm) {
+    const int hw = h * w;
+    if (blockIdx.x < blocks_m) {
+        const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+        if (i >= (int64_t)B * 3 * hw) return;
+        const int p = (int)(i % hw), y = p / w, x = p - y * w;
+        const int64_t bk = i / hw;                     // b * 3 + k
+        // tap j's source position; a tap whose source lies outside the plane reads the lane's own position and counts as 0,
+        // so the loads of a group do not hang on a branch and the next group's are issued under this group's adds
+        int off[9];
+        bool in[9];
+#pragma unroll
+        for (int j = 0; j < 9; ++j) {
+            const int yy = y - j / 3 + 1, xx = x - j % 3 + 1;
+            in[j] = yy >= 0 && yy < h && xx >= 0 && xx < w;
+            off[j] = j * hw + (in[j] ? yy * w + xx : p);
+        }
+        float acc = 0.0f;
+#pragma unroll 2
+        for (int g = 0; g < groups; ++g) {
+            const float *t = ws_m + (((int64_t)g * B * 3 + bk) * 9) * hw;
+            float v[9];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) v[j] = t[off[j]];
+#pragma unroll
+            for (int j = 0; j < 9; ++j) acc = acc + (in[j] ? v[j] : 0.0f);
+        }
+        d_masks[i] = acc;
+    } else {
+        const int i = (int)(blockIdx.x - blocks_m) * 256 + threadIdx.x;
+        const int n = 36 * Hd;
+        if (i >= n) return;
+        float acc = 0.0f;
+        int k = 0;
+        for (; k + 8 <= pos_blocks; k += 8) {          // eight loads in flight, added in ascending order
+            float v[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = ws_w[(int64_t)(k + j) * n + i];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) acc = acc + v[j];
+        }
+        for (; k < pos_blocks; ++k) acc = acc + ws_w[(int64_t)k * n + i];
+        d_wm[i] = acc;
+    }
+}
+
 // ---- (12c) / (12d) align-corners bilinear -----------------------------------------------------------------------------
 // ATen's upsample_bilinear2d with align_corners = True: scale = (in - 1) / (out - 1) (0 for out == 1), src = scale * dst,
 // lower index by truncation, lambda1 = src - lower, lambda0 = 1 - lambda1.
@@ -254,6 +449,49 @@ extern "C" int dmm_clstm_gates_f32(const float *pre0, const float *pre1, const f
     hipLaunchKernelGGL(dmm::clstm_gates_kernel, dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0, (hipStream_t)stream, pre0,
                        pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, B, hidden_size, h, w, hidden, cell,
                        hidden_copy, sb_copy);
+    return dmm::check_launch();
+}
+
+// ws_m [groups][B][27][h * w] then ws_w [position blocks][36 * hidden_size]; 0 for sizes the entry refuses or has no work for
+extern "C" size_t dmm_clstm_gates_bwd_workspace_bytes(int B, int hidden_size, int h, int w) {
+    if (B <= 0 || hidden_size <= 0 || h <= 0 || w <= 0) return 0;
+    const int64_t hw = (int64_t)h * w, groups = (hidden_size + dmm::kGateCh - 1) / dmm::kGateCh;
+    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return 0;
+    const int64_t blocks = ((int64_t)B * hw + 255) / 256;
+    return (size_t)(groups * B * 27 * hw + blocks * 36 * hidden_size) * sizeof(float);
+}
+
+extern "C" int dmm_clstm_gates_bwd_f32(const float *pre0, const float *pre1, const float *pre2, int64_t sb0, int64_t sb1,
+                                       int64_t sb2, const float *masks, int64_t sb_masks, const float *w_mask,
+                                       const float *cell_prev, int B, int hidden_size, int h, int w, const float *d_hidden,
+                                       const float *d_cell, float *d_pre, float *d_cell_prev, float *d_masks, float *d_w_mask,
+                                       void *ws, size_t ws_bytes, dmm_stream_t stream) {
+    if (B < 0 || hidden_size <= 0 || h <= 0 || w <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0) return DMM_OK;
+    if (!pre0 || !masks || !w_mask || !d_pre || (!d_hidden && !d_cell) || (d_cell_prev && !cell_prev)) return DMM_ERR_BAD_ARG;
+    const int64_t hw = (int64_t)h * w;
+    if (sb0 < 0 || sb1 < 0 || sb2 < 0 || sb_masks < 3 * hw) return DMM_ERR_BAD_ARG;
+    const bool reduce = d_masks || d_w_mask;
+    if (reduce && !ws) return DMM_ERR_BAD_ARG;
+    const int64_t blocks = ((int64_t)B * hw + 255) / 256, groups = (hidden_size + dmm::kGateCh - 1) / dmm::kGateCh;
+    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return DMM_ERR_UNSUPPORTED;
+    if (reduce && ws_bytes < dmm_clstm_gates_bwd_workspace_bytes(B, hidden_size, h, w)) return DMM_ERR_WORKSPACE;
+    float *ws_m = (float *)ws, *ws_w = reduce ? ws_m + groups * B * 27 * hw : nullptr;
+#define DMM_GATES_BWD(M_, W_)                                                                                              \
+    hipLaunchKernelGGL((dmm::clstm_gates_bwd_kernel<M_, W_>), dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,      \
+                       (hipStream_t)stream, pre0, pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, d_hidden, \
+                       d_cell, B, hidden_size, h, w, d_pre, d_cell_prev, ws_m, ws_w)
+    if (d_masks && d_w_mask) DMM_GATES_BWD(true, true);
+    else if (d_masks) DMM_GATES_BWD(true, false);
+    else if (d_w_mask) DMM_GATES_BWD(false, true);
+    else DMM_GATES_BWD(false, false);
+#undef DMM_GATES_BWD
+    int rc = dmm::check_launch();
+    if (rc != DMM_OK || !reduce) return rc;
+    const unsigned blocks_m = d_masks ? (unsigned)(((int64_t)B * 3 * hw + 255) / 256) : 0u;
+    const unsigned blocks_w = d_w_mask ? (unsigned)((36 * hidden_size + 255) / 256) : 0u;
+    hipLaunchKernelGGL(dmm::clstm_gates_bwd_fold_kernel, dim3(blocks_m + blocks_w), dim3(256), 0, (hipStream_t)stream, ws_m, ws_w,
+                       B, hidden_size, h, w, (int)groups, (int)blocks, blocks_m, d_masks, d_w_mask);
     return dmm::check_launch();
 }
 

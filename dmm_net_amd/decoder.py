@@ -9,11 +9,18 @@ Counterparts in the reference:
 * ``RefineStep``  -- the object loop of ``Evaler.inference_timestep`` (``dmm/modules/evaluator.py:179-212``) behind the
   ``refine`` contract of ``video.FrameLoop``.
 
-Two execution forms behind the one ``forward``:
+Three execution forms behind the one ``forward``:
 
 * the STOCK form: the reference's arithmetic op for op in torch.  Runs wherever torch runs and under autograd; taken when
-  gradients are required, in ``train()`` mode with ``dropout > 0``, for ``kernel_size == 1``, ``prev_mask_d != 1``,
-  non-fp32 or CPU tensors.  Training through the decoder works this way and is not accelerated.
+  gradients are required (unless ``fused_train`` is set, below), in ``train()`` mode with ``dropout > 0``, for
+  ``kernel_size == 1``, ``prev_mask_d != 1``, non-fp32 or CPU tensors.  With the default ``fused_train = False`` training
+  through the decoder works this way and is not accelerated.
+* the FUSED TRAINING form (``decoder.fused_train = True``, opt-in; HIP tensors, fp32, 3x3, a gradient required, no active
+  dropout): the algebra of the fused form below under autograd.  The convolutions (on differentiable slices of
+  ``Gates.weight``), the bilinear upsample, ``cat`` and the 'mul' product are torch ops; the cell is ``clstm_gates_fn``:
+  ``dmm_clstm_gates_f32`` forward, ``dmm_clstm_gates_bwd_f32`` backward, which recomputes the gates from the cell's inputs
+  instead of keeping the forward's intermediates.  One shared convolution share per level and direction instead of three
+  full ones, one pointwise launch per level instead of about thirty.
 * the FUSED form (HIP tensors, fp32, no grad, 3x3): the three cell evaluations of a level get the same input, the same
   spatial state and the same temporal hidden and differ in the one-channel mask plane only; a convolution is linear in
   its input channels, so
@@ -126,6 +133,116 @@ def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev,
     return hidden, cell
 
 
+def clstm_gates_bwd(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev, d_hidden, d_cell,
+                    need=(True, True, True)):
+    """``dmm_clstm_gates_bwd_f32``: the inputs of ``clstm_gates`` and the upstream gradients ``d_hidden`` / ``d_cell``
+    ([B, Hd, h, w]; either may be None = zeros, not both) -> ``(d_pre, d_cell_prev, d_masks, d_w_mask)``.  ``d_pre``
+    [B, 4*Hd, h, w] is the gradient of the sum of the addends, so of each of them; ``need`` says which of ``d_cell_prev``,
+    ``d_masks`` [B, 3, h, w], ``d_w_mask`` [4*Hd, 9] are wanted (the others are None and cost nothing).  The gates are
+    recomputed from the inputs; bit-reproducible."""
+    _need_device(masks)
+    pre = [p for p in pre if p is not None]
+    assert 1 <= len(pre) <= 3
+    B, C4, h, w = pre[0].shape
+    Hd = C4 // 4
+    need_cell, need_masks, need_w = (bool(n) for n in need)
+    assert not need_cell or cell_prev is not None, "d_cell_prev without cell_prev"
+    ptrs, strides, keep = [], [], []
+    for p in pre:
+        assert tuple(p.shape) == (B, 4 * Hd, h, w) and p.dtype == torch.float32, (p.shape, pre[0].shape)
+        p, sb = _dense_batch(p)
+        keep.append(p)
+        ptrs.append(p.data_ptr())
+        strides.append(sb)
+    ptrs += [None] * (3 - len(ptrs))
+    strides += [0] * (3 - len(strides))
+    masks, sbm = _dense_batch(masks)
+    w_mask = w_mask.contiguous()
+    assert tuple(masks.shape) == (B, 3, h, w) and tuple(w_mask.shape) == (4 * Hd, 9)
+    state = []
+    for t in (cell_prev, d_hidden, d_cell):
+        if t is not None:
+            assert tuple(t.shape) == (B, Hd, h, w) and t.dtype == torch.float32, (t.shape, (B, Hd, h, w))
+            t = t.contiguous()
+        state.append(t)
+    cell_prev, d_hidden, d_cell = state
+    assert d_hidden is not None or d_cell is not None
+    new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=masks.device)
+    d_pre = new(B, 4 * Hd, h, w)
+    d_cell_prev = new(B, Hd, h, w) if need_cell else None
+    d_masks = new(B, 3, h, w) if need_masks else None
+    d_w_mask = new(4 * Hd, 9) if need_w else None
+    ws, ws_bytes = None, 0
+    if need_masks or need_w:
+        ws_bytes = int(_lib.load().dmm_clstm_gates_bwd_workspace_bytes(B, Hd, h, w))
+        ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.float32, device=masks.device)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    _lib.call("dmm_clstm_gates_bwd_f32", masks.device, *ptrs, *strides, masks.data_ptr(), sbm, w_mask.data_ptr(), ptr(cell_prev),
+              B, Hd, h, w, ptr(d_hidden), ptr(d_cell), d_pre.data_ptr(), ptr(d_cell_prev), ptr(d_masks), ptr(d_w_mask), ptr(ws),
+              ws_bytes, _stream(masks))
+    return d_pre, d_cell_prev, d_masks, d_w_mask
+
+
+class ClstmGatesFn(torch.autograd.Function):
+    """The fused cell under autograd: ``apply(pre0, pre1, pre2, masks, w_mask, cell_prev) -> (hidden, cell)`` (``pre1``,
+    ``pre2``, ``cell_prev`` may be None).  Forward: ``clstm_gates`` into fresh tensors; backward: ``clstm_gates_bwd``.
+    Saves its inputs only: the backward recomputes the gates."""
+
+    @staticmethod
+    def forward(ctx, pre0, pre1, pre2, masks, w_mask, cell_prev):
+        B, C4, h, w = pre0.shape
+        hidden, cell = pre0.new_empty((B, C4 // 4, h, w)), pre0.new_empty((B, C4 // 4, h, w))
+        clstm_gates([pre0, pre1, pre2], masks, w_mask.contiguous(), cell_prev, hidden, cell)
+        ctx.save_for_backward(pre0, pre1, pre2, masks, w_mask, cell_prev)
+        ctx.set_materialize_grads(False)
+        return hidden, cell
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_hidden, d_cell):
+        pre0, pre1, pre2, masks, w_mask, cell_prev = ctx.saved_tensors
+        if d_hidden is None and d_cell is None:
+            return (None,) * 6
+        g = ctx.needs_input_grad
+        d_pre, d_cell_prev, d_masks, d_w_mask = clstm_gates_bwd([pre0, pre1, pre2], masks, w_mask, cell_prev, d_hidden, d_cell,
+                                                                need=(g[5], g[3], g[4]))
+        pre_grads = tuple(d_pre if (p is not None and g[n]) else None for n, p in enumerate((pre0, pre1, pre2)))
+        return pre_grads + (d_masks, d_w_mask, d_cell_prev)
+
+
+def clstm_gates_fn(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev):
+    """``ClstmGatesFn`` with the addends as a sequence (up to three, None entries skipped) -> ``(hidden, cell)``.  Every
+    addend that requires a gradient receives the same ``d_pre`` tensor; ``w_mask``'s gradient has its shape [4*Hd, 9]."""
+    pre = [p for p in pre if p is not None]
+    assert 1 <= len(pre) <= 3
+    pre += [None] * (3 - len(pre))
+    return ClstmGatesFn.apply(pre[0], pre[1], pre[2], masks, w_mask, cell_prev)
+
+
+class _WeightSlices(torch.autograd.Function):
+    """``apply(weight, bounds) -> contiguous weight[:, bounds[k]:bounds[k + 1]]`` for every k.  Its backward assembles the
+    weight's gradient with ONE ``cat`` of the slices' gradients (zeros for a slice the call did not use) where one
+    differentiable slice each would cost a zero-filled tensor of the whole weight's size and an add per slice (a tenth of the
+    fused training step at config 4's sizes, profiles/r11_decoder_train.md).  The slices are disjoint, so every element of
+    the gradient is the same single value (or sum of two, where a slice is used twice) either way."""
+
+    @staticmethod
+    def forward(ctx, weight, bounds):
+        ctx.bounds, ctx.rest = bounds, tuple(weight.shape[2:])
+        ctx.set_materialize_grads(False)
+        return tuple(weight[:, a:b].contiguous() for a, b in zip(bounds[:-1], bounds[1:]))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        ref = next((g for g in grads if g is not None), None)
+        if ref is None:
+            return None, None
+        parts = [g if g is not None else ref.new_zeros((ref.shape[0], b - a) + ctx.rest)
+                 for g, a, b in zip(grads, ctx.bounds[:-1], ctx.bounds[1:])]
+        return torch.cat(parts, 1), None
+
+
 def upsample_bilinear_into(src, dst, c0: int = 0, mode: str = "write"):
     """``dmm_upsample_bilinear_into_f32``: UpsamplingBilinear2d(src [B,C,h,w]) to dst's size, combined into
     dst[:, c0:c0+C] ([B, C', H, W] dense) by ``mode`` ('write' | 'add' | 'mul')."""
@@ -206,20 +323,29 @@ class RSISMask(nn.Module):
             self.clstm_list.append(ConvLSTMCellMask(args, in_dim, out_dim, self.kernel_size, padding))
         self.conv_out = nn.Conv2d(self.skip_dims_out[-1], 1, self.kernel_size, padding=padding)
         self.fused = True                    # False: always the stock form (A/B timing, tests)
+        self.fused_train = False             # True: calls that require a gradient take the fused training form
         self._slices = None                  # (key, per-level weight slices) of the fused form
         self.conv_calls = 0                  # convolutions issued by the fused form (diagnostic, like dmm_launch_count)
 
     # ---- dispatch ------------------------------------------------------------------------------------------------
-    def fused_ok(self, tensors: Sequence[torch.Tensor]) -> bool:
-        """Does the fused form cover this call?  (Anything else is the stock form -- same results, torch ops.)"""
+    def _route(self, tensors: Sequence[torch.Tensor]) -> str:
+        """'fused' (no gradient), 'train' (a gradient is required and ``fused_train`` is on) or 'stock'."""
         if not self.fused or self.skip_mode not in _SKIP_MODES or int(self.kernel_size) != 3 or self.prev_mask_d != 1:
-            return False
+            return "stock"
         if self.training and self.dropout > 0:
-            return False
+            return "stock"
         params = list(self.parameters())
-        if torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + params):
-            return False
-        return all(t.is_cuda and t.dtype == torch.float32 for t in list(tensors) + params)
+        grad = torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + params)
+        if grad and not self.fused_train:
+            return "stock"
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in list(tensors) + params):
+            return "stock"
+        return "train" if grad else "fused"
+
+    def fused_ok(self, tensors: Sequence[torch.Tensor]) -> bool:
+        """Does the fused inference form cover this call?  (Anything else is the stock form -- same results, torch ops --
+        or, with ``fused_train``, the fused training form.)"""
+        return self._route(tensors) == "fused"
 
     def forward(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
         ts = list(skip_feats) + list(prev_mask_list)
@@ -227,8 +353,11 @@ class RSISMask(nn.Module):
             ts += [t for st in prev_state_spatial for t in st]
         if prev_hidden_temporal is not None:
             ts += list(prev_hidden_temporal)
-        if self.fused_ok(ts):
+        route = self._route(ts)
+        if route == "fused":
             return self._forward_fused(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
+        if route == "train":
+            return self._forward_fused_train(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
         return self.forward_stock(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
 
     # ---- stock form: base.py:115-188 op for op ----------------------------------------------------------------------
@@ -366,6 +495,47 @@ class RSISMask(nn.Module):
         h, w = up_src.shape[-2:]
         top = up_src.new_empty((up_src.shape[0], self.skip_dims_out[-1], 2 * h, 2 * w))
         upsample_bilinear_into(up_src, top, 0, "write")
+        return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
+
+    # ---- fused training form ---------------------------------------------------------------------------------------------
+    def _forward_fused_train(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
+        """The fused algebra under autograd: per level the addends (skip term with the bias, temporal term, chain term on
+        cat[up, h_s] / up / h_s) are library convolutions on differentiable slices of ``Gates.weight``, the upsample, ``cat``
+        and the 'mul' product are torch ops, and the cell is ``clstm_gates_fn`` (HIP forward and backward)."""
+        bilinear = lambda x, size: F.interpolate(x, size=size, mode="bilinear", align_corners=True)
+        hidden_list, up = [], None
+        for i, cell in enumerate(self.clstm_list):
+            Wt, bias, Hd, cin = cell.Gates.weight, cell.Gates.bias, cell.hidden_size, cell.input_size
+            f = skip_feats[i]
+            st = None if prev_state_spatial is None else prev_state_spatial[i]
+            # input channels in the order x (= [up | skip] under 'concat' above level 0), mask, h_s, h_t
+            cup = cin if i == 0 or self.skip_mode != "concat" else self.skip_dims_out[i - 1]
+            w_x, w_x2, w_m, w_hs, w_ht = _WeightSlices.apply(Wt, (0, cup, cin, cin + 1, cin + 1 + Hd, cin + 1 + 2 * Hd))
+            w_m = w_m.reshape(4 * Hd, 9)
+            if i == 0:
+                w_up, w_skip = None, w_x
+            else:
+                w_up = w_x
+                w_skip = w_x2 if self.skip_mode == "concat" else w_up if self.skip_mode == "sum" else None
+            skip_term = None if w_skip is None else self._conv(f, w_skip, bias)
+            temporal_term = None if prev_hidden_temporal is None else self._conv(prev_hidden_temporal[i], w_ht)
+            chain_bias = None if skip_term is not None else bias
+            chain = None
+            if i == 0:
+                if st is not None:
+                    chain = self._conv(st[0], w_hs)
+            else:
+                x = bilinear(up, tuple(f.shape[-2:]))
+                if self.skip_mode == "mul":
+                    x = f * x
+                if st is None:
+                    chain = self._conv(x, w_up, chain_bias)
+                else:
+                    chain = self._conv(torch.cat([x, st[0]], 1), torch.cat([w_up, w_hs], 1), chain_bias)
+            hidden, c = clstm_gates_fn([skip_term, temporal_term, chain], prev_mask_list[i], w_m, None if st is None else st[1])
+            hidden_list.append([hidden, c])
+            up = hidden
+        top = bilinear(up, (up.shape[-2] * 2, up.shape[-1] * 2))
         return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
 
 

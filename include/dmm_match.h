@@ -856,7 +856,9 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  * (12) The ConvLSTM refine decoder (dmm/modules/base.py:71-188 RSISMask, dmm/modules/clstm.py:68-131 ConvLSTMCellMask, driven
  * per object by dmm/modules/evaluator.py:179-212): everything BETWEEN its convolutions.  fp32, dense planes (row stride =
  * width, channel stride = plane), batch / object strides in elements; nothing allocates, no memset nodes.  Used by
- * dmm_net_amd/decoder.py, which keeps the convolutions on the library.
+ * dmm_net_amd/decoder.py, which keeps the convolutions on the library.  (12a)-(12d) are the forward; (12e) is the backward of
+ * the cell (12b), the one kernel between the convolutions that training on the fused form needs -- the upsample, the pyramid
+ * and the finish have no backward here (the training form keeps them on torch autograd).
  *
  * (12a) dmm_mask_pyramid_f32 -- evaluator.py:188-195: MaxPool2d((2,2), ceil_mode=True) applied 5, 4, 3 and 2 times to the planes
  *   prev_mask[b, t], y_mask[b, t], init_pred[b, t] (each H x W at base + b * sb + t * so), b < B, t < n_obj, in ONE launch and
@@ -882,6 +884,23 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  *   b * sb_logits + t * so_logits, conv_out's output) -> bilinear (align_corners = True) to H x W -> sigmoid -> outs[b, t]; the
  *   same value into mask_hist[b, t] where valid[b * O + t] != 0 (int32, read on the device; mask_hist may be null); rows
  *   n_obj <= t < O of outs are zeroed.  outs / mask_hist [B, O, H, W] dense.
+ *
+ * (12e) dmm_clstm_gates_bwd_f32 -- the backward of (12b).  Reads what the forward read (pre0..2, masks, w_mask, cell_prev, the
+ *   same strides and null meanings) and the upstream gradients d_hidden / d_cell [B, hidden_size, h, w] dense (either may be
+ *   null = zeros, not both).  Nothing of the forward is saved: the gates are recomputed with the forward's expressions in the
+ *   forward's order.  With u = d_hidden / 3, v = d_cell / 3 and, per plane k, the activated gates i, r, o, g, c_k and
+ *   t_k = tanh(c_k):  dc_k = v + u o (1 - t_k^2);  the pre-activation gradients are  in: dc_k g i (1 - i),  remember:
+ *   dc_k cell_prev r (1 - r) (0 without cell_prev),  out: u t_k o (1 - o),  cell: dc_k i (1 - g^2)  -- ds_{q,k} below.
+ *   Outputs (a null pointer = not wanted, and no work is done for it; d_pre is required):
+ *     d_pre       [B, 4 * hidden_size, h, w] dense = (ds_{q,0} + ds_{q,2}) + ds_{q,1}: the gradient of the sum, so of every addend
+ *     d_cell_prev [B, hidden_size, h, w] dense = (dc_0 r_0 + dc_2 r_2) + dc_1 r_1; must be null when cell_prev is null
+ *     d_masks     [B, 3, h, w] dense, the input's plane order: the transposed stencil of ds_{.,k} (sources outside the plane: none)
+ *     d_w_mask    [4 * hidden_size, 9] = sum over (b, y, x, k) of ds_{q,k} * m_k at the tap (taps outside the plane: 0)
+ *   One launch for d_pre / d_cell_prev alone; two when d_masks or d_w_mask is wanted (the second folds the workspace).  No float
+ *   atomics: d_masks sums the channel groups' partials in ascending order, d_w_mask the 64-lane tree, the four waves and then
+ *   the position blocks in ascending order -- every output's bits are a function of the inputs and (B, hidden_size, h, w).
+ *   ws: dmm_clstm_gates_bwd_workspace_bytes(B, hidden_size, h, w) bytes (0 for sizes the entry refuses or has no work for),
+ *   4-byte aligned, written before it is read (no zeroing); needed only when d_masks or d_w_mask is wanted (else may be null).
  * ------------------------------------------------------------------------------------------- */
 DMM_API int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
                                  int64_t so_prev, int64_t sb_y, int64_t so_y, int64_t sb_init, int64_t so_init, int B, int n_obj,
@@ -890,6 +909,12 @@ DMM_API int dmm_clstm_gates_f32(const float *pre0, const float *pre1, const floa
                                 const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
                                 int hidden_size, int h, int w, float *hidden, float *cell, float *hidden_copy, int64_t sb_copy,
                                 dmm_stream_t stream);
+DMM_API size_t dmm_clstm_gates_bwd_workspace_bytes(int B, int hidden_size, int h, int w);
+DMM_API int dmm_clstm_gates_bwd_f32(const float *pre0, const float *pre1, const float *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                    const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                    int hidden_size, int h, int w, const float *d_hidden, const float *d_cell, float *d_pre,
+                                    float *d_cell_prev, float *d_masks, float *d_w_mask, void *ws, size_t ws_bytes,
+                                    dmm_stream_t stream);
 DMM_API int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int B, int C, int h, int w, float *dst,
                                            int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream);
 DMM_API int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
