@@ -55,7 +55,7 @@ def use_shipped_miopen_db(develop: bool = False, enable: bool = True):
 
 def __getattr__(name):
     # the refine decoder (decoder.py), exported lazily: importing the package stays as light as it was
-    if name in ("RSISMask", "RefineStep"):
+    if name in ("RSISMask", "RefineStep", "RefineTrainStep", "RefineState"):
         from . import decoder
         return getattr(decoder, name)
     # the fused mask losses (losses.py), lazily too

@@ -7,7 +7,9 @@
 // evaluations of a level share one pre-activation; each mask plane's share is a 36-weight stencil per hidden channel),
 // the align-corners bilinear upsample written into a channel range of the next level's convolution input, and the
 // finish (upsample to image size, sigmoid, the valid-gated history write and the zero rows of the padded output).
-// For training on the fused form: the backward of the cell (12e), which recomputes the gates, and its fixed-order fold.
+// For training on the fused form: the backward of the cell (12e), which recomputes the gates, and its fixed-order fold; and
+// what the refine step of training (dmm/modules/trainer.py:236-306) runs around the decoder: the backward of the pyramid (12f),
+// the backward of the upsample in 'write' mode (12g), the trainer's nearest / sigmoid / pad finish and its backward (12h).
 #include "dmm_common.h"
 
 #include <math.h>
@@ -415,6 +417,207 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const float *__restr
     }
 }
 
+// ---- (12f) backward of the mask pyramid -------------------------------------------------------------------------------
+// One workgroup = one 32 x 32 tile of one wanted plane (video b, object t, prev_mask or init_pred), as in the forward.  The
+// chain of 2x2 pools is replayed on (value, position) pairs in LDS: 16 x 16 winners of the first pool, then 8 x 8, 4 x 4,
+// 2 x 2 and 1 (the outputs' levels 2 .. 5).  Every pool scans its four children in row-major order and replaces the winner
+// on a strict '>' only -- ATen's rule, so among equal maxima of a composite window the smallest Z-order code wins.  Pixels
+// outside the plane count as -inf and never win (inputs are finite; the tile's first pixel lies inside the plane).  The
+// gradients then descend into an LDS tile of 1024 floats, level 2, 3, 4, 5 in this order, a barrier between two levels
+// (windows of one level are disjoint, so no two lanes meet), and the whole tile is stored: every pixel is written.
+__device__ __forceinline__ void pool_winner(const float *__restrict__ cv, const short *__restrict__ cp, int n, int i,
+                                            float *__restrict__ pv, short *__restrict__ pp) {
+    const int half = n >> 1, py = i / half, px = i - py * half;
+    const int c = (2 * py) * n + 2 * px;
+    float v = cv[c];
+    short p = cp[c];
+    if (cv[c + 1] > v) { v = cv[c + 1]; p = cp[c + 1]; }
+    if (cv[c + n] > v) { v = cv[c + n]; p = cp[c + n]; }
+    if (cv[c + n + 1] > v) { v = cv[c + n + 1]; p = cp[c + n + 1]; }
+    pv[i] = v;
+    pp[i] = p;
+}
+
+__global__ __launch_bounds__(256) void mask_pyramid_bwd_kernel(
+    const float *__restrict__ prev, const float *__restrict__ init, int64_t sb_prev, int64_t so_prev, int64_t sb_i, int64_t so_i,
+    int B, int H, int W, int tiles_x, const float *__restrict__ d5, const float *__restrict__ d4, const float *__restrict__ d3,
+    const float *__restrict__ d2, float *__restrict__ d_prev, int64_t sb_dp, int64_t so_dp, float *__restrict__ d_init,
+    int64_t sb_di, int64_t so_di) {
+    __shared__ float s_v[1024];                        // the tile's values, then its gradients
+    __shared__ float v1[256], v2[64], v3[16], v4[4], v5[1];
+    __shared__ short p1[256], p2[64], p3[16], p4[4], p5[1];
+    const int wanted = (d_prev ? 1 : 0) + (d_init ? 1 : 0);
+    const int which = blockIdx.y % wanted, tb = blockIdx.y / wanted, b = tb % B, t = tb / B;
+    const bool is_prev = d_prev && which == 0;
+    const float *src = is_prev ? prev + (int64_t)b * sb_prev + (int64_t)t * so_prev : init + (int64_t)b * sb_i + (int64_t)t * so_i;
+    float *dst = is_prev ? d_prev + (int64_t)b * sb_dp + (int64_t)t * so_dp : d_init + (int64_t)b * sb_di + (int64_t)t * so_di;
+    const int c = is_prev ? 0 : 2;                     // the plane's channel in the forward's outputs
+    const int64_t plane = ((int64_t)t * B + b) * 3 + c;
+    const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+    const int l = threadIdx.x;
+    const int y0 = ty * 32, x0 = tx * 32;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = k * 256 + l, row = y0 + (i >> 5), col = x0 + (i & 31);
+        s_v[i] = (row < H && col < W) ? src[(int64_t)row * W + col] : -INFINITY;
+    }
+    __syncthreads();
+    {                                                  // the first pool: 2 x 2 pixels, positions = indices into the tile
+        const int py = l >> 4, px = l & 15, q = (2 * py) * 32 + 2 * px;
+        float v = s_v[q];
+        int p = q;
+        if (s_v[q + 1] > v) { v = s_v[q + 1]; p = q + 1; }
+        if (s_v[q + 32] > v) { v = s_v[q + 32]; p = q + 32; }
+        if (s_v[q + 33] > v) { v = s_v[q + 33]; p = q + 33; }
+        v1[l] = v;
+        p1[l] = (short)p;
+    }
+    __syncthreads();
+    if (l < 64) pool_winner(v1, p1, 16, l, v2, p2);
+    __syncthreads();
+    if (l < 16) pool_winner(v2, p2, 8, l, v3, p3);
+    __syncthreads();
+    if (l < 4) pool_winner(v3, p3, 4, l, v4, p4);
+    __syncthreads();
+    if (l == 0) pool_winner(v4, p4, 2, 0, v5, p5);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s_v[k * 256 + l] = 0.0f;   // (the values were last read by the first pool)
+    __syncthreads();
+    const int h2 = (H + 3) >> 2, w2 = (W + 3) >> 2, h3 = (H + 7) >> 3, w3 = (W + 7) >> 3;
+    const int h4 = (H + 15) >> 4, w4 = (W + 15) >> 4, h5 = (H + 31) >> 5, w5 = (W + 31) >> 5;
+    if (d2 && l < 64) {
+        const int y = ty * 8 + (l >> 3), x = tx * 8 + (l & 7);
+        if (y < h2 && x < w2) s_v[p2[l]] = s_v[p2[l]] + d2[(plane * h2 + y) * w2 + x];
+    }
+    __syncthreads();
+    if (d3 && l < 16) {
+        const int y = ty * 4 + (l >> 2), x = tx * 4 + (l & 3);
+        if (y < h3 && x < w3) s_v[p3[l]] = s_v[p3[l]] + d3[(plane * h3 + y) * w3 + x];
+    }
+    __syncthreads();
+    if (d4 && l < 4) {
+        const int y = ty * 2 + (l >> 1), x = tx * 2 + (l & 1);
+        if (y < h4 && x < w4) s_v[p4[l]] = s_v[p4[l]] + d4[(plane * h4 + y) * w4 + x];
+    }
+    __syncthreads();
+    if (d5 && l == 0 && ty < h5 && tx < w5) s_v[p5[0]] = s_v[p5[0]] + d5[(plane * h5 + ty) * w5 + tx];
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = k * 256 + l, row = y0 + (i >> 5), col = x0 + (i & 31);
+        if (row < H && col < W) dst[(int64_t)row * W + col] = s_v[i];
+    }
+}
+
+// ---- (12g) backward of the bilinear upsample ('write' mode) ------------------------------------------------------------
+// Gather form: one lane per source element.  The destination rows (columns) whose lerp_of can touch source row y lie in
+// [(y - 1) / scale, (y + 1) / scale); that range is widened by one and clipped, and every candidate is then classified with
+// the forward's own lerp_of, so the indices and weights are the forward's, bit for bit.  Y ascending, then X ascending.
+__device__ __forceinline__ void touch_range(int i, float scale, int out, int &lo, int &hi) {
+    lo = 0;
+    hi = out - 1;
+    if (scale > 0.0f) {                                // (scale == 0: in == 1, every destination index reads source 0)
+        const float a = floorf((float)(i - 1) / scale) - 1.0f, b = ceilf((float)(i + 1) / scale) + 1.0f;
+        if (a > 0.0f) lo = a < (float)(out - 1) ? (int)a : out - 1;
+        if (b < (float)(out - 1)) hi = b > 0.0f ? (int)b : 0;
+    }
+}
+__device__ __forceinline__ float touch_weight(const Lerp &r, int i) {
+    float wgt = r.i0 == i ? r.l0 : 0.0f;
+    if (r.i0 + r.step == i) wgt = r.i0 == i ? wgt + r.l1 : r.l1;   // (step == 0: the forward reads the row twice)
+    return wgt;
+}
+
+__global__ __launch_bounds__(256) void upsample_bwd_kernel(const float *__restrict__ d_dst, int64_t sb_dst, int C, int H, int W,
+                                                           int c0, float *__restrict__ d_src, int64_t sb_src, int h, int w,
+                                                           float sy, float sx, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i % w);
+    int64_t r = i / w;
+    const int y = (int)(r % h);
+    r /= h;
+    const int c = (int)(r % C), b = (int)(r / C);
+    int Y0, Y1, X0, X1;
+    touch_range(y, sy, H, Y0, Y1);
+    touch_range(x, sx, W, X0, X1);
+    const float *g = d_dst + (int64_t)b * sb_dst + (int64_t)(c0 + c) * H * W;
+    float acc = 0.0f;
+    for (int Y = Y0; Y <= Y1; ++Y) {
+        const Lerp ly = lerp_of(Y, sy, h);
+        if (ly.i0 != y && ly.i0 + ly.step != y) continue;
+        const float wy = touch_weight(ly, y);
+        const float *row = g + (int64_t)Y * W;
+        for (int X = X0; X <= X1; ++X) {
+            const Lerp lx = lerp_of(X, sx, w);
+            if (lx.i0 != x && lx.i0 + lx.step != x) continue;
+            acc = acc + (wy * touch_weight(lx, x)) * row[X];
+        }
+    }
+    d_src[(int64_t)b * sb_src + ((int64_t)c * h + y) * w + x] = acc;
+}
+
+// ---- (12h) the finish of the training step -------------------------------------------------------------------------------
+// torch's default NEAREST interpolation: source index = min((int)floorf(dst * scale), in - 1), scale = (float)in / out.
+__host__ __device__ __forceinline__ float nn_scale(int in, int out) { return (float)in / (float)out; }
+__device__ __forceinline__ int nn_index(int dst, float scale, int in) {
+    const int i = (int)floorf((float)dst * scale);
+    return i < in - 1 ? i : in - 1;
+}
+
+__global__ __launch_bounds__(256) void refine_train_finish_kernel(const float *__restrict__ logits, int64_t sb_l, int64_t so_l,
+                                                                  int h, int w, int O, int n_obj, int H, int W, float sy, float sx,
+                                                                  float *__restrict__ outs, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int X = (int)(i % W);
+    int64_t r = i / W;
+    const int Y = (int)(r % H);
+    r /= H;
+    const int t = (int)(r % O), b = (int)(r / O);
+    float v = 0.0f;
+    if (t < n_obj) {
+        const float *p = logits + (int64_t)b * sb_l + (int64_t)t * so_l;
+        v = sigmoid_f32(p[(int64_t)nn_index(Y, sy, h) * w + nn_index(X, sx, w)]);
+    }
+    outs[i] = v;
+}
+
+// The destination indices that read source index i form a contiguous block inside [i * out / in - 1, (i + 1) * out / in + 1]
+// (integer arithmetic, one index of room each way); the block is found by classifying with nn_index itself.
+__device__ __forceinline__ void nn_block(int i, float scale, int in, int out, int &lo, int &hi) {
+    int64_t a = ((int64_t)i * out) / in - 1, z = ((int64_t)(i + 1) * out + in - 1) / in + 1;
+    if (a < 0) a = 0;
+    if (z > out - 1) z = out - 1;
+    lo = (int)a;
+    hi = (int)z;
+    while (lo <= hi && nn_index(lo, scale, in) != i) ++lo;
+    while (hi >= lo && nn_index(hi, scale, in) != i) --hi;
+}
+
+__global__ __launch_bounds__(256) void refine_train_finish_bwd_kernel(const float *__restrict__ logits, int64_t sb_l, int64_t so_l,
+                                                                      int h, int w, const float *__restrict__ d_outs, int O,
+                                                                      int n_obj, int H, int W, float sy, float sx,
+                                                                      float *__restrict__ d_logits, int64_t sb_d, int64_t so_d,
+                                                                      int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int x = (int)(i % w);
+    int64_t r = i / w;
+    const int y = (int)(r % h);
+    r /= h;
+    const int t = (int)(r % n_obj), b = (int)(r / n_obj);
+    int Y0, Y1, X0, X1;
+    nn_block(y, sy, h, H, Y0, Y1);
+    nn_block(x, sx, w, W, X0, X1);
+    const float *g = d_outs + ((int64_t)b * O + t) * H * W;
+    float acc = 0.0f;
+    for (int Y = Y0; Y <= Y1; ++Y)
+        for (int X = X0; X <= X1; ++X) acc = acc + g[(int64_t)Y * W + X];
+    const float p = sigmoid_f32(logits[(int64_t)b * sb_l + (int64_t)t * so_l + (int64_t)y * w + x]);
+    d_logits[(int64_t)b * sb_d + (int64_t)t * so_d + (int64_t)y * w + x] = (p * (1.0f - p)) * acc;
+}
+
 }  // namespace dmm
 
 extern "C" int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
@@ -527,5 +730,68 @@ extern "C" int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int
     if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(dmm::refine_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, sb_logits,
                        so_logits, h, w, valid, B, O, n_obj, H, W, Wq, dmm::ac_scale(h, H), dmm::ac_scale(w, W), outs, mask_hist, n);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_mask_pyramid_bwd_f32(const float *prev_mask, const float *init_pred, int64_t sb_prev, int64_t so_prev,
+                                        int64_t sb_init, int64_t so_init, int B, int n_obj, int H, int W, const float *d_out5,
+                                        const float *d_out4, const float *d_out3, const float *d_out2, float *d_prev,
+                                        int64_t sb_dprev, int64_t so_dprev, float *d_init, int64_t sb_dinit, int64_t so_dinit,
+                                        dmm_stream_t stream) {
+    if (B < 0 || n_obj < 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || n_obj == 0 || (!d_prev && !d_init)) return DMM_OK;
+    if ((d_prev && !prev_mask) || (d_init && !init_pred)) return DMM_ERR_BAD_ARG;
+    if (sb_prev < 0 || so_prev < 0 || sb_init < 0 || so_init < 0) return DMM_ERR_BAD_ARG;
+    const int64_t hw = (int64_t)H * W;
+    if ((d_prev && (so_dprev < hw || sb_dprev < 0)) || (d_init && (so_dinit < hw || sb_dinit < 0))) return DMM_ERR_BAD_ARG;
+    const int tiles_x = (W + 31) / 32, tiles_y = (H + 31) / 32;
+    const int64_t planes = (int64_t)B * n_obj * ((d_prev ? 1 : 0) + (d_init ? 1 : 0));
+    if ((int64_t)B * n_obj * 3 > 65535 || (int64_t)tiles_x * tiles_y > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::mask_pyramid_bwd_kernel, dim3((unsigned)(tiles_x * tiles_y), (unsigned)planes), dim3(256), 0,
+                       (hipStream_t)stream, prev_mask, init_pred, sb_prev, so_prev, sb_init, so_init, B, H, W, tiles_x, d_out5,
+                       d_out4, d_out3, d_out2, d_prev, sb_dprev, so_dprev, d_init, sb_dinit, so_dinit);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_upsample_bilinear_bwd_f32(const float *d_dst, int64_t sb_dst, int B, int C, int H, int W, int C_dst, int c0,
+                                             float *d_src, int64_t sb_src, int h, int w, dmm_stream_t stream) {
+    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C_dst <= 0) return DMM_ERR_BAD_ARG;
+    if (c0 < 0 || c0 + C > C_dst) return DMM_ERR_BAD_ARG;                            // the channel range lies inside d_dst
+    if (H < h || W < w) return DMM_ERR_UNSUPPORTED;                                  // the gather ranges assume out >= in
+    if (B == 0) return DMM_OK;
+    if (!d_dst || !d_src) return DMM_ERR_BAD_ARG;
+    if (sb_src < (int64_t)C * h * w || sb_dst < (int64_t)C_dst * H * W) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * C * h * w, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::upsample_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_dst, sb_dst, C, H, W,
+                       c0, d_src, sb_src, h, w, dmm::ac_scale(h, H), dmm::ac_scale(w, W), n);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_refine_train_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, int B, int O,
+                                           int n_obj, int H, int W, float *outs, dmm_stream_t stream) {
+    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || O == 0) return DMM_OK;
+    if (!outs || (n_obj > 0 && !logits)) return DMM_ERR_BAD_ARG;
+    if (sb_logits < 0 || so_logits < 0) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * O * H * W, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::refine_train_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
+                       sb_logits, so_logits, h, w, O, n_obj, H, W, dmm::nn_scale(h, H), dmm::nn_scale(w, W), outs, n);
+    return dmm::check_launch();
+}
+
+extern "C" int dmm_refine_train_finish_bwd_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w,
+                                               const float *d_outs, int B, int O, int n_obj, int H, int W, float *d_logits,
+                                               int64_t sb_d, int64_t so_d, dmm_stream_t stream) {
+    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || n_obj == 0) return DMM_OK;
+    if (!logits || !d_outs || !d_logits) return DMM_ERR_BAD_ARG;
+    if (sb_logits < 0 || so_logits < 0 || sb_d < 0 || so_d < (int64_t)h * w) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * n_obj * h * w, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(dmm::refine_train_finish_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
+                       sb_logits, so_logits, h, w, d_outs, O, n_obj, H, W, dmm::nn_scale(h, H), dmm::nn_scale(w, W), d_logits,
+                       sb_d, so_d, n);
     return dmm::check_launch();
 }

@@ -8,6 +8,9 @@ Counterparts in the reference:
   ``forward(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal) -> (out_mask, hidden_list)``.
 * ``RefineStep``  -- the object loop of ``Evaler.inference_timestep`` (``dmm/modules/evaluator.py:179-212``) behind the
   ``refine`` contract of ``video.FrameLoop``.
+* ``RefineTrainStep``  -- the object loop of ``Trainer.refine`` with its loss (``dmm/modules/trainer.py:236-306``): the
+  training counterpart of ``RefineStep``, on ``mask_pyramid_fn`` / ``upsample_bilinear_fn`` / ``refine_train_finish_fn``
+  (HIP forward and backward, include/dmm_match.h (12f)-(12h)) around the fused training form below.
 
 Three execution forms behind the one ``forward``:
 
@@ -243,6 +246,40 @@ class _WeightSlices(torch.autograd.Function):
         return torch.cat(parts, 1), None
 
 
+class _ConvStacked(torch.autograd.Function):
+    """``apply(x, weight, bias, chunks)``: ONE 3x3 / padding 1 convolution of ``x`` = ``chunks`` equal groups of samples
+    stacked along the batch (the objects of a frame), and one data-gradient call for all of them; the gradients of ``weight``
+    and ``bias`` are taken group by group and added in group order.  Summed in a single library call over every group's
+    pixels, conv_out's weight gradient came out 2 - 3 times further from fp64 than the trainer's per-object convolutions
+    leave it (profiles/r12_refine_train.md); this way it carries their error."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, chunks):
+        ctx.save_for_backward(x, weight)
+        ctx.chunks, ctx.has_bias = int(chunks), bias is not None
+        return F.conv2d(x, weight, bias, padding=1)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2]
+        bias_sizes = [weight.shape[0]] if ctx.has_bias else None
+        bwd = lambda g, inp, mask: torch.ops.aten.convolution_backward(g, inp, weight, bias_sizes, [1, 1], [1, 1], [1, 1],
+                                                                       False, [0, 0], 1, mask)
+        dy = dy.contiguous()
+        dx = bwd(dy, x, [True, False, False])[0] if need_x else None
+        dw = db = None
+        if need_w or need_b:
+            for xc, dc in zip(x.chunk(ctx.chunks, 0), dy.chunk(ctx.chunks, 0)):
+                _, a, c = bwd(dc, xc, [False, need_w, need_b])
+                if need_w:
+                    dw = a if dw is None else dw + a
+                if need_b:
+                    db = c if db is None else db + c
+        return dx, dw, db, None
+
+
 def upsample_bilinear_into(src, dst, c0: int = 0, mode: str = "write"):
     """``dmm_upsample_bilinear_into_f32``: UpsamplingBilinear2d(src [B,C,h,w]) to dst's size, combined into
     dst[:, c0:c0+C] ([B, C', H, W] dense) by ``mode`` ('write' | 'add' | 'mul')."""
@@ -273,6 +310,197 @@ def refine_finish(logits, valid_i32, outs, mask_hist, n_obj: int):
     _lib.call("dmm_refine_finish_f32", outs.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w,
               None if valid_i32 is None else valid_i32.data_ptr(), B, O, int(n_obj), H, W, outs.data_ptr(),
               None if mask_hist is None else mask_hist.data_ptr(), _stream(outs))
+    return outs
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# what the refine step of training runs around the decoder (include/dmm_match.h (12f)-(12h)): launchers, the autograd
+# functions over them, and for each its torch-op twin -- the same function in the ops the trainer uses
+# ------------------------------------------------------------------------------------------------------------------
+_ptr = lambda t: None if t is None else t.data_ptr()
+
+
+def mask_pyramid_bwd(prev_mask, init_pred, d_outs, n_obj: int, H: int, W: int, need=(True, True), out=None):
+    """``dmm_mask_pyramid_bwd_f32``: the planes the forward read and the gradients of its four outputs (coarsest first,
+    [n_obj, B, 3, h_l, w_l]; None = zeros) -> ``(d_prev, d_init)`` in the inputs' shapes; ``need`` says which is wanted (the
+    other is None).  Rows of objects >= n_obj are zero.  ``out``: a pair of tensors to write into instead of fresh ones
+    ([B, >= n_obj, H*W | H, W], dense planes, any batch / object strides; rows >= n_obj are then left alone)."""
+    _need_device(prev_mask)
+    prev_c, sbp, sop = _plane_strides(prev_mask, H, W)
+    init_c, sbi, soi = _plane_strides(init_pred, H, W)
+    B = prev_c.shape[0]
+    assert n_obj <= min(prev_c.shape[1], init_c.shape[1])
+    ds = []
+    for d, (h, w) in zip(d_outs, pyramid_sizes(H, W)):
+        if d is not None:
+            assert tuple(d.shape) == (n_obj, B, 3, h, w) and d.dtype == torch.float32, (d.shape, (n_obj, B, 3, h, w))
+            d = d.contiguous()
+        ds.append(d)
+    res = []
+    for k, like in enumerate((prev_mask, init_pred)):
+        g = None
+        if need[k] and out is not None:
+            g = out[k]
+            assert g.dtype == torch.float32 and g.shape[0] == B and g.shape[1] >= n_obj and g.stride(-1) == 1 and \
+                (g.dim() == 3 or g.stride(2) == W) and g[0, 0].numel() == H * W, (g.shape, g.stride())
+        elif need[k]:
+            g = torch.empty((B, like.shape[1], H * W), dtype=torch.float32, device=like.device)
+            if like.shape[1] > n_obj:
+                g[:, n_obj:].zero_()
+        res.append(g)
+    strides = lambda g: (0, H * W) if g is None else (g.stride(0), max(g.stride(1), H * W))
+    _lib.call("dmm_mask_pyramid_bwd_f32", prev_c.device, prev_c.data_ptr(), init_c.data_ptr(), sbp, sop, sbi, soi, B, int(n_obj),
+              H, W, *[_ptr(d) for d in ds], _ptr(res[0]), *strides(res[0]), _ptr(res[1]), *strides(res[1]), _stream(prev_c))
+    if out is None:
+        res = [None if g is None else g.view(like.shape) for g, like in zip(res, (prev_mask, init_pred))]
+    return tuple(res)
+
+
+class MaskPyramidFn(torch.autograd.Function):
+    """``mask_pyramid`` under autograd: ``apply(prev_mask, y_mask, init_pred, n_obj, H, W)`` -> the four levels.  Gradients
+    go to ``prev_mask`` and ``init_pred`` (``mask_pyramid_bwd``); the reference mask is data."""
+
+    @staticmethod
+    def forward(ctx, prev_mask, y_mask, init_pred, n_obj, H, W):
+        outs = mask_pyramid(prev_mask, y_mask, init_pred, n_obj, H, W)
+        ctx.save_for_backward(prev_mask, init_pred)
+        ctx.dims = (int(n_obj), int(H), int(W))
+        ctx.set_materialize_grads(False)
+        return tuple(outs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *d_outs):
+        g = ctx.needs_input_grad
+        if all(d is None for d in d_outs) or not (g[0] or g[2]):
+            return (None,) * 6
+        prev_mask, init_pred = ctx.saved_tensors
+        d_prev, d_init = mask_pyramid_bwd(prev_mask, init_pred, d_outs, *ctx.dims, need=(g[0], g[2]))
+        return d_prev, None, d_init, None, None, None
+
+
+def mask_pyramid_fn(prev_mask, y_mask, init_pred, n_obj: int, H: int, W: int):
+    """trainer.py:256-265 for objects 0..n_obj-1 in one launch, differentiable in ``prev_mask`` and ``init_pred`` -> 4 tensors
+    [n_obj, B, 3, h_l, w_l], coarsest first."""
+    return list(MaskPyramidFn.apply(prev_mask, y_mask, init_pred, n_obj, H, W))
+
+
+def mask_pyramid_torch(prev_mask, y_mask, init_pred, n_obj: int, H: int, W: int):
+    """The twin of ``mask_pyramid_fn``: the trainer's nested ``max_pool2d`` calls on all objects at once (any device, dtype)."""
+    B = prev_mask.shape[0]
+    m = torch.stack([t[:, :n_obj].reshape(B, n_obj, H, W) for t in (prev_mask, y_mask, init_pred)], 2)
+    m = m.transpose(0, 1).reshape(n_obj * B, 3, H, W)
+    pool = lambda x: F.max_pool2d(x, (2, 2), ceil_mode=True)
+    m = pool(m)
+    pyr = []
+    for _ in range(4):
+        m = pool(m)
+        pyr.append(m.view(n_obj, B, 3, *m.shape[-2:]))
+    return pyr[::-1]
+
+
+def upsample_bilinear_bwd(d_dst, c0: int, C: int, h: int, w: int):
+    """``dmm_upsample_bilinear_bwd_f32``: the gradient of channels c0 .. c0 + C of d_dst [B, C', H, W] (what 'write' mode of
+    ``upsample_bilinear_into`` wrote) -> d_src [B, C, h, w].  H >= h and W >= w; anything else raises."""
+    _need_device(d_dst)
+    assert d_dst.dtype == torch.float32
+    d_dst, sbd = _dense_batch(d_dst)
+    B, Cd, H, W = d_dst.shape
+    d_src = torch.empty((B, C, h, w), dtype=torch.float32, device=d_dst.device)
+    _lib.call("dmm_upsample_bilinear_bwd_f32", d_dst.device, d_dst.data_ptr(), sbd, B, int(C), H, W, Cd, int(c0),
+              d_src.data_ptr(), C * h * w, int(h), int(w), _stream(d_dst))
+    return d_src
+
+
+class UpsampleBilinearFn(torch.autograd.Function):
+    """``apply(src, size)``: ``upsample_bilinear_into`` ('write') into a fresh tensor; backward ``upsample_bilinear_bwd``."""
+
+    @staticmethod
+    def forward(ctx, src, size):
+        B, C, h, w = src.shape
+        H, W = int(size[0]), int(size[1])
+        if H < h or W < w:
+            raise _lib.DmmError(f"upsample_bilinear_fn: {h}x{w} -> {H}x{W} is not an upsample (its backward covers H >= h, W >= w)")
+        dst = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+        upsample_bilinear_into(src, dst, 0, "write")
+        ctx.src_size = (h, w)
+        return dst
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_dst):
+        return upsample_bilinear_bwd(d_dst, 0, d_dst.shape[1], *ctx.src_size), None
+
+
+def upsample_bilinear_fn(src, size):
+    """UpsamplingBilinear2d (align_corners = True) of src [B, C, h, w] to ``size``, HIP forward and backward (no atomics)."""
+    return UpsampleBilinearFn.apply(src, tuple(size))
+
+
+def upsample_bilinear_torch(src, size):
+    """The twin of ``upsample_bilinear_fn``."""
+    return F.interpolate(src, size=tuple(size), mode="bilinear", align_corners=True)
+
+
+def _logit_planes(logits):
+    h, w = logits.shape[-2:]
+    if not (logits.stride(3) == 1 and logits.stride(2) == w):
+        logits = logits.contiguous()
+    return logits
+
+
+def refine_train_finish(logits, O: int, H: int, W: int):
+    """``dmm_refine_train_finish_f32``: logits [B, n_obj, h, w] (any batch / object strides, dense planes) -> outs [B, O, H, W]
+    = sigmoid of the NEAREST interpolation (torch's default mode, trainer.py:275), zero rows beyond n_obj."""
+    _need_device(logits)
+    assert logits.dtype == torch.float32 and logits.dim() == 4 and logits.shape[1] <= O
+    logits = _logit_planes(logits)
+    B, n_obj, h, w = logits.shape
+    outs = torch.empty((B, O, H, W), dtype=torch.float32, device=logits.device)
+    _lib.call("dmm_refine_train_finish_f32", logits.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w, B, int(O),
+              n_obj, int(H), int(W), outs.data_ptr(), _stream(logits))
+    return outs
+
+
+def refine_train_finish_bwd(logits, d_outs):
+    """``dmm_refine_train_finish_bwd_f32``: the forward's logits and d_outs [B, O, H, W] -> d_logits [B, n_obj, h, w]."""
+    _need_device(logits)
+    logits = _logit_planes(logits)
+    B, n_obj, h, w = logits.shape
+    assert d_outs.dtype == torch.float32 and d_outs.dim() == 4 and d_outs.shape[0] == B and d_outs.shape[1] >= n_obj
+    d_outs = d_outs.contiguous()
+    O, H, W = d_outs.shape[1:]
+    d_logits = torch.empty((B, n_obj, h, w), dtype=torch.float32, device=logits.device)
+    _lib.call("dmm_refine_train_finish_bwd_f32", logits.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w,
+              d_outs.data_ptr(), B, O, n_obj, H, W, d_logits.data_ptr(), n_obj * h * w, h * w, _stream(logits))
+    return d_logits
+
+
+class RefineTrainFinishFn(torch.autograd.Function):
+    """``apply(logits, O, H, W)``: ``refine_train_finish``; backward ``refine_train_finish_bwd`` (recomputes the sigmoid)."""
+
+    @staticmethod
+    def forward(ctx, logits, O, H, W):
+        ctx.save_for_backward(logits)
+        return refine_train_finish(logits, O, H, W)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_outs):
+        (logits,) = ctx.saved_tensors
+        return refine_train_finish_bwd(logits, d_outs), None, None, None
+
+
+def refine_train_finish_fn(logits, O: int, H: int, W: int):
+    """trainer.py:275-287, 302-304 for all objects: logits [B, n_obj, h, w] -> padded probabilities [B, O, H, W]."""
+    return RefineTrainFinishFn.apply(logits, int(O), int(H), int(W))
+
+
+def refine_train_finish_torch(logits, O: int, H: int, W: int):
+    """The twin of ``refine_train_finish_fn``."""
+    p = torch.sigmoid(F.interpolate(logits, (H, W)))
+    outs = p.new_zeros((p.shape[0], O, H, W))
+    outs[:, :p.shape[1]] = p
     return outs
 
 
@@ -498,27 +726,53 @@ class RSISMask(nn.Module):
         return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
 
     # ---- fused training form ---------------------------------------------------------------------------------------------
-    def _forward_fused_train(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
-        """The fused algebra under autograd: per level the addends (skip term with the bias, temporal term, chain term on
-        cat[up, h_s] / up / h_s) are library convolutions on differentiable slices of ``Gates.weight``, the upsample, ``cat``
-        and the 'mul' product are torch ops, and the cell is ``clstm_gates_fn`` (HIP forward and backward)."""
-        bilinear = lambda x, size: F.interpolate(x, size=size, mode="bilinear", align_corners=True)
-        hidden_list, up = [], None
+    def train_slices(self):
+        """Per level the differentiable slices of ``Gates.weight`` the fused training form convolves with: ``up``, ``skip``
+        (as in ``weight_slices``), ``m`` [4*Hd, 9], ``hs``, ``ht`` and ``bias``.  One ``_WeightSlices`` node per level: a
+        caller that evaluates several objects of a frame on the same slices (``RefineTrainStep``) pays the assembly of the
+        weight's gradient once per frame."""
+        out = []
         for i, cell in enumerate(self.clstm_list):
-            Wt, bias, Hd, cin = cell.Gates.weight, cell.Gates.bias, cell.hidden_size, cell.input_size
-            f = skip_feats[i]
-            st = None if prev_state_spatial is None else prev_state_spatial[i]
+            Wt, Hd, cin = cell.Gates.weight, cell.hidden_size, cell.input_size
             # input channels in the order x (= [up | skip] under 'concat' above level 0), mask, h_s, h_t
             cup = cin if i == 0 or self.skip_mode != "concat" else self.skip_dims_out[i - 1]
             w_x, w_x2, w_m, w_hs, w_ht = _WeightSlices.apply(Wt, (0, cup, cin, cin + 1, cin + 1 + Hd, cin + 1 + 2 * Hd))
-            w_m = w_m.reshape(4 * Hd, 9)
-            if i == 0:
-                w_up, w_skip = None, w_x
+            d = {"m": w_m.reshape(4 * Hd, 9), "hs": w_hs, "ht": w_ht, "bias": cell.Gates.bias, "up": None, "skip": w_x}
+            if i > 0:
+                d["up"] = w_x
+                d["skip"] = w_x2 if self.skip_mode == "concat" else w_x if self.skip_mode == "sum" else None
+            out.append(d)
+        return out
+
+    def _forward_fused_train(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal, slices=None,
+                             skip_terms=None, temporal_terms=None, bilinear=None, head=True):
+        """The fused algebra under autograd: per level the addends (skip term with the bias, temporal term, chain term on
+        cat[up, h_s] / up / h_s) are library convolutions on differentiable slices of ``Gates.weight``, the upsample, ``cat``
+        and the 'mul' product are torch ops, and the cell is ``clstm_gates_fn`` (HIP forward and backward).
+
+        The optional arguments let a driver hand over what does not depend on the object (``RefineTrainStep``); the defaults
+        compute everything here.  ``slices``: ``train_slices()`` taken once per frame; ``skip_terms``: per level
+        conv(skip map, W_skip) + bias (None where the level has no such term) -- ``skip_feats`` is then read for the sizes
+        and the 'mul' product only; ``temporal_terms``: per level conv(h_t, W_ht) of this object, used INSTEAD of
+        ``prev_hidden_temporal``; ``bilinear(x, size)``: the upsample; ``head=False``: return the last level's hidden in
+        place of ``conv_out`` of its upsample (the driver runs both once for all objects)."""
+        if bilinear is None:
+            bilinear = lambda x, size: F.interpolate(x, size=size, mode="bilinear", align_corners=True)
+        if slices is None:
+            slices = self.train_slices()
+        hidden_list, up = [], None
+        for i, d in enumerate(slices):
+            bias, w_up, w_skip, w_hs = d["bias"], d["up"], d["skip"], d["hs"]
+            f = skip_feats[i]
+            st = None if prev_state_spatial is None else prev_state_spatial[i]
+            if skip_terms is not None:
+                skip_term = skip_terms[i]
             else:
-                w_up = w_x
-                w_skip = w_x2 if self.skip_mode == "concat" else w_up if self.skip_mode == "sum" else None
-            skip_term = None if w_skip is None else self._conv(f, w_skip, bias)
-            temporal_term = None if prev_hidden_temporal is None else self._conv(prev_hidden_temporal[i], w_ht)
+                skip_term = None if w_skip is None else self._conv(f, w_skip, bias)
+            if temporal_terms is not None:
+                temporal_term = temporal_terms[i]
+            else:
+                temporal_term = None if prev_hidden_temporal is None else self._conv(prev_hidden_temporal[i], d["ht"])
             chain_bias = None if skip_term is not None else bias
             chain = None
             if i == 0:
@@ -531,10 +785,14 @@ class RSISMask(nn.Module):
                 if st is None:
                     chain = self._conv(x, w_up, chain_bias)
                 else:
-                    chain = self._conv(torch.cat([x, st[0]], 1), torch.cat([w_up, w_hs], 1), chain_bias)
-            hidden, c = clstm_gates_fn([skip_term, temporal_term, chain], prev_mask_list[i], w_m, None if st is None else st[1])
+                    if "cat" not in d:
+                        d["cat"] = torch.cat([w_up, w_hs], 1)
+                    chain = self._conv(torch.cat([x, st[0]], 1), d["cat"], chain_bias)
+            hidden, c = clstm_gates_fn([skip_term, temporal_term, chain], prev_mask_list[i], d["m"], None if st is None else st[1])
             hidden_list.append([hidden, c])
             up = hidden
+        if not head:
+            return up, hidden_list
         top = bilinear(up, (up.shape[-2] * 2, up.shape[-1] * 2))
         return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
 
@@ -693,3 +951,121 @@ class RefineStep:
         else:
             thid = [[bufs["hid"][i][t] for i in range(4)] for t in range(n_obj)]
         return bufs["outs"].view(B, O, H * W), mask_hist_new, RefineState(state.n_obj, thid)
+
+
+class RefineTrainStep:
+    """The refine step of TRAINING: the object loop of ``Trainer.refine`` (``dmm/modules/trainer.py:236-306``) with its loss.
+
+    ``step(features, prev_mask, ref_mask, init_pred, y_mask, sw_mask, valid, state)
+        -> (loss, {'hard_iou', 'loss_miou'}, outs_pad [B,O,HW], state)``
+
+    ``features``: the encoder's dict (its ``'refine_input_feat'`` is read) or the four skip maps themselves; ``prev_mask`` /
+    ``ref_mask`` / ``y_mask`` [B,O,HW], ``init_pred`` [B,O,H,W], ``sw_mask`` / ``valid`` [B,O].  ``loss`` is ``iou_weight`` *
+    the soft-IoU loss of the first ``n_obj`` planes, ``hard_iou`` the trainer's ``hard_iou0`` (``hard_all`` of
+    ``losses.mask_step_losses``, which computes both).  ``state`` is a ``RefineState``: ``n_obj`` is the trainer's
+    ``valid_num_obj`` -- the number of columns of ``valid`` with any entry set -- read ONCE per clip, when ``state is None``
+    (one host read); a caller that runs with ``skip_empty_starting_frame = False`` passes ``RefineState(O)`` of its own.
+    ``thid`` carries the temporal hiddens WITH their graph: gradients cross frames through them and through
+    ``prev_mask = outs``, so the step keeps no persistent buffers (unlike ``RefineStep``).  The trainer's
+    ``num_template_not_empty == 0`` branch (trainer.py:213-216: no refine at all, zero loss terms) stays the caller's.
+
+    Two routes, decided once per call with the decoder's ``_route``:
+
+    * ``_stock``: the trainer's loop op for op on ``decoder.forward`` -- CPU tensors, active dropout, any dtype, and every
+      decoder that cannot train on its fused form (``fused_train`` off, 1x1 kernels, ...).
+    * ``_fused`` (``decoder.fused_train = True``, HIP fp32 tensors): one ``mask_pyramid_fn`` for all objects, the skip terms
+      once per frame, one batched temporal convolution per level for all objects, per object the chain convolutions,
+      ``clstm_gates_fn`` and ``upsample_bilinear_fn``, then one upsample, one ``conv_out`` and one ``refine_train_finish_fn``
+      for all objects.  ``kernels`` names which of the three pieces run on their HIP functions; setting one to False routes
+      that piece alone through its torch twin (the same function in torch ops).
+    """
+
+    def __init__(self, decoder: RSISMask, only_temporal: bool = False, iou_weight: float = 1.0):
+        self.decoder, self.only_temporal, self.iou_weight = decoder, bool(only_temporal), float(iou_weight)
+        self.kernels = {"pyramid": True, "upsample": True, "finish": True}
+        self.last_route = None                                    # 'fused' | 'stock': the route of the last call (diagnostic)
+
+    def __call__(self, features, prev_mask, ref_mask, init_pred, y_mask, sw_mask, valid, state):
+        feats = list(features["refine_input_feat"] if isinstance(features, dict) else features)
+        B, O = init_pred.shape[:2]
+        H, W = init_pred.shape[-2:]
+        if state is None:
+            state = RefineState(int((valid.sum(0) > 0).sum()))    # valid_num_obj (trainer.py:146): the clip's one host read
+        n_obj = min(state.n_obj, O)
+        if n_obj <= 0:
+            raise ValueError("RefineTrainStep: no valid object (the trainer's num_template_not_empty == 0 branch is the caller's)")
+        dec = self.decoder
+        ts = feats + [prev_mask, ref_mask, init_pred]
+        if state.thid is not None:
+            ts += [h for hs in state.thid for h in hs]
+        fused = dec.fused_train and dec._route(ts) in ("train", "fused")
+        self.last_route = "fused" if fused else "stock"
+        run = self._fused if fused else self._stock
+        probs, thid = run(feats, prev_mask, ref_mask, init_pred, state.thid, n_obj, B, O, H, W)      # [B, O, HW]
+        from .losses import mask_step_losses
+        loss_miou, _, hard_all, _, _ = mask_step_losses(y_mask, probs, sw_mask, valid, n_obj)
+        return self.iou_weight * loss_miou, {"hard_iou": hard_all, "loss_miou": loss_miou}, probs, RefineState(state.n_obj, thid)
+
+    # ---- trainer.py:245-287, 302-304 in torch ---------------------------------------------------------------------------
+    def _stock(self, feats, prev_mask, ref_mask, init_pred, prev_thid, n_obj, B, O, H, W):
+        dec = self.decoder
+        dtype = feats[0].dtype
+        hidden_spatial, thid, out_masks = None, [], []
+        pool = lambda x: F.max_pool2d(x, (2, 2), ceil_mode=True)
+        for t in range(n_obj):
+            hidden_temporal = None
+            if prev_thid is not None:
+                assert len(prev_thid) == n_obj, (len(prev_thid), n_obj)
+                hidden_temporal = prev_thid[t]
+                if self.only_temporal:
+                    hidden_spatial = None
+            m = torch.cat([prev_mask[:, t].reshape(B, 1, H * W).to(dtype), ref_mask[:, t].reshape(B, 1, H * W).to(dtype),
+                           init_pred[:, t].reshape(B, 1, H * W).to(dtype)], 2).view(B, 3, H, W)
+            m = pool(m)
+            mask_lstm = []
+            for _ in range(len(feats)):
+                m = pool(m)
+                mask_lstm.append(m)
+            out_mask, hidden = dec(feats, mask_lstm[::-1], hidden_spatial, hidden_temporal)
+            thid.append([hc[0] for hc in hidden])
+            hidden_spatial = hidden
+            out_masks.append(F.interpolate(out_mask, (H, W)).view(B, -1))
+        probs = torch.sigmoid(torch.cat(out_masks, 1).view(B, n_obj, -1))
+        outs_pad = probs.new_zeros((B, O, H * W))
+        outs_pad[:, :n_obj] = probs
+        return outs_pad, thid
+
+    # ---- the fused step --------------------------------------------------------------------------------------------------
+    def _fused(self, feats, prev_mask, ref_mask, init_pred, prev_thid, n_obj, B, O, H, W):
+        dec, k = self.decoder, self.kernels
+        for f, s in zip(feats, pyramid_sizes(H, W)):
+            assert tuple(f.shape[-2:]) == s, ("refine_input_feat does not sit on the mask pyramid", f.shape, s)
+        pyramid = mask_pyramid_fn if k["pyramid"] else mask_pyramid_torch
+        bilinear = upsample_bilinear_fn if k["upsample"] else upsample_bilinear_torch
+        finish = refine_train_finish_fn if k["finish"] else refine_train_finish_torch
+        pyr = pyramid(prev_mask, ref_mask, init_pred, n_obj, H, W)
+        sl = dec.train_slices()
+        skip_terms = [None if d["skip"] is None else dec._conv(f, d["skip"], d["bias"]) for d, f in zip(sl, feats)]
+        temporal = None
+        if prev_thid is not None:
+            assert len(prev_thid) == n_obj, (len(prev_thid), n_obj)
+            # one convolution per level over the hiddens of every object, stacked along the batch
+            temporal = [dec._conv(torch.cat([prev_thid[t][i] for t in range(n_obj)], 0), d["ht"]) for i, d in enumerate(sl)]
+        hidden_spatial, thid, tops = None, [], []
+        for t in range(n_obj):
+            tt = None
+            if temporal is not None:
+                tt = [x[t * B:(t + 1) * B] for x in temporal]
+                if self.only_temporal:
+                    hidden_spatial = None
+            up, hidden = dec._forward_fused_train(feats, [p[t] for p in pyr], hidden_spatial, None, slices=sl,
+                                                  skip_terms=skip_terms, temporal_terms=tt, bilinear=bilinear, head=False)
+            thid.append([hc[0] for hc in hidden])
+            hidden_spatial = hidden
+            tops.append(up)
+        top = torch.cat(tops, 0)                                                    # [n_obj * B, Hd / 8, h, w]
+        top = bilinear(top, (top.shape[-2] * 2, top.shape[-1] * 2))
+        dec.conv_calls += 1
+        logits = _ConvStacked.apply(top, dec.conv_out.weight, dec.conv_out.bias, n_obj)   # [n_obj * B, 1, 2h, 2w]
+        logits = logits.view(n_obj, B, *logits.shape[-2:]).transpose(0, 1)          # [B, n_obj, 2h, 2w] (strided view)
+        return finish(logits, O, H, W).view(B, O, H * W), thid

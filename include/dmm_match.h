@@ -857,8 +857,9 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  * per object by dmm/modules/evaluator.py:179-212): everything BETWEEN its convolutions.  fp32, dense planes (row stride =
  * width, channel stride = plane), batch / object strides in elements; nothing allocates, no memset nodes.  Used by
  * dmm_net_amd/decoder.py, which keeps the convolutions on the library.  (12a)-(12d) are the forward; (12e) is the backward of
- * the cell (12b), the one kernel between the convolutions that training on the fused form needs -- the upsample, the pyramid
- * and the finish have no backward here (the training form keeps them on torch autograd).
+ * the cell (12b); (12f)-(12h) are what the refine step of TRAINING (dmm/modules/trainer.py:236-306) runs around the decoder:
+ * the backward of the pyramid (12a), the backward of the upsample (12c) in 'write' mode, and the trainer's own finish
+ * (nearest interpolation, sigmoid, pad) with its backward.  None of (12f)-(12h) uses an atomic or a workspace.
  *
  * (12a) dmm_mask_pyramid_f32 -- evaluator.py:188-195: MaxPool2d((2,2), ceil_mode=True) applied 5, 4, 3 and 2 times to the planes
  *   prev_mask[b, t], y_mask[b, t], init_pred[b, t] (each H x W at base + b * sb + t * so), b < B, t < n_obj, in ONE launch and
@@ -901,6 +902,43 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  *   the position blocks in ascending order -- every output's bits are a function of the inputs and (B, hidden_size, h, w).
  *   ws: dmm_clstm_gates_bwd_workspace_bytes(B, hidden_size, h, w) bytes (0 for sizes the entry refuses or has no work for),
  *   4-byte aligned, written before it is read (no zeroing); needed only when d_masks or d_w_mask is wanted (else may be null).
+ *
+ * (12f) dmm_mask_pyramid_bwd_f32 -- the backward of (12a) for the planes that carry a gradient in training: prev_mask (last
+ *   frame's outs, trainer.py:124-125) and init_pred (the matching layer's output).  Reads the planes the forward read (same
+ *   strides) and the gradients of its four outputs, d_out_k [n_obj, B, 3, ceil(H / 2^k), ceil(W / 2^k)] dense, k = 5, 4, 3, 2
+ *   (a null d_out_k = zeros); channel 1 of them, the reference mask's, is ignored.  Writes d_prev / d_init: plane (b, t) at
+ *   base + b * sb + t * so, H x W dense, so >= H * W; either may be null = not wanted (no work is done for it; both null: DMM_OK,
+ *   nothing launched).  EVERY pixel of every wanted plane is written: the caller does not pre-zero.
+ *   The four levels share one chain of pools: one pool, then four more, outputs after the 2nd to 5th.  The gradient of a level-k
+ *   output descends to the ONE pixel that wins its clipped 2^k x 2^k window under ATen's rule applied pool by pool: a 2 x 2 pool
+ *   scans its (clipped) window in row-major order and a later element wins on a strict '>' only, so the first maximum wins.
+ *   For the composite window: among equal maxima the pixel with the smallest Z-order code wins -- the code interleaves the bits
+ *   of (y, x) inside the window, the y bit above the x bit at every level.  This is NOT the first maximum in row-major order
+ *   (in the 4 x 4 window, pixel (1, 0) has code 2 and beats pixel (0, 2), code 4).  Masks are full of exact zeros and ones: ties
+ *   are the normal case.  A pixel's gradient is (((0 + g_2) + g_3) + g_4) + g_5 over the levels it wins, in this fixed order.
+ *   Inputs are taken as finite.  B * n_obj * 3 <= 65535 as in (12a).
+ *
+ * (12g) dmm_upsample_bilinear_bwd_f32 -- the backward of (12c) in mode 0 (write).  d_dst: channels c0 .. c0 + C of a
+ *   [B, C_dst, H, W] tensor (batch stride sb_dst), as the forward writes one; d_src [B, C, h, w] (batch stride sb_src), every
+ *   element written.  Gather form: d_src[b, c, y, x] = sum over Y ascending, then X ascending, of (wy(Y) * wx(X)) * d_dst[b,
+ *   c0 + c, Y, X] over the destination pixels whose interpolation touches (y, x); with (i0, step, l0, l1) = the forward's own
+ *   fp32 index rule for Y (src = scale * Y, scale = (h - 1) / (H - 1) in fp32 or 0 for H == 1, i0 = trunc(src) clipped to
+ *   h - 1, step = (i0 < h - 1), l1 = src - i0, l0 = 1 - l1):  wy(Y) = l0 if i0 == y, plus l1 if i0 + step == y.  The kernel
+ *   classifies its candidates with the very function the forward uses, so both agree on every index and weight, h == 1 and
+ *   H == 1 included.  H >= h >= 1 and W >= w >= 1; anything else: DMM_ERR_UNSUPPORTED.
+ *
+ * (12h) dmm_refine_train_finish_f32 / dmm_refine_train_finish_bwd_f32 -- trainer.py:275-287, 302-304 for every object of the
+ *   frame in one launch.  Forward: outs[b, t, Y, X] = sigmoid(logits[b, t, iy(Y), ix(X)]) for t < n_obj, zero rows for
+ *   n_obj <= t < O; outs [B, O, H, W] dense; logits strided as (12d)'s.  The interpolation is torch's default NEAREST, not the
+ *   evaluator's bilinear: i(dst) = min((int)floorf(dst * scale), in - 1), scale = (float)in / (float)out in fp32.  Backward:
+ *   d_logits[b, t, y, x] = p (1 - p) * sum of d_outs[b, t, Y, X] over the destination pixels that read (y, x) -- a contiguous
+ *   block, summed Y then X ascending; a logit nobody reads (out < in) gets 0; p is recomputed from the logit.  d_outs
+ *   [B, O, H, W] dense (rows t >= n_obj are not read); d_logits: plane (b, t), t < n_obj, at base + b * sb_d + t * so_d.
+ *
+ * Answers of (12f)-(12h) before any launch, in this order: DMM_ERR_BAD_ARG for a negative B / O / n_obj, n_obj > O, a size
+ * <= 0, a channel range outside d_dst; (12g) DMM_ERR_UNSUPPORTED for H < h or W < w; DMM_OK when there is nothing to do
+ * (B == 0, no object, no wanted plane); DMM_ERR_BAD_ARG for a needed null pointer, a negative stride, an output plane stride
+ * below the plane, a batch stride below the sample ((12g)); DMM_ERR_UNSUPPORTED for a grid beyond the launch limits.
  * ------------------------------------------------------------------------------------------- */
 DMM_API int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
                                  int64_t so_prev, int64_t sb_y, int64_t so_y, int64_t sb_init, int64_t so_init, int B, int n_obj,
@@ -919,6 +957,18 @@ DMM_API int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int
                                            int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream);
 DMM_API int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
                                   int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist, dmm_stream_t stream);
+DMM_API int dmm_mask_pyramid_bwd_f32(const float *prev_mask, const float *init_pred, int64_t sb_prev, int64_t so_prev,
+                                     int64_t sb_init, int64_t so_init, int B, int n_obj, int H, int W, const float *d_out5,
+                                     const float *d_out4, const float *d_out3, const float *d_out2, float *d_prev,
+                                     int64_t sb_dprev, int64_t so_dprev, float *d_init, int64_t sb_dinit, int64_t so_dinit,
+                                     dmm_stream_t stream);
+DMM_API int dmm_upsample_bilinear_bwd_f32(const float *d_dst, int64_t sb_dst, int B, int C, int H, int W, int C_dst, int c0,
+                                          float *d_src, int64_t sb_src, int h, int w, dmm_stream_t stream);
+DMM_API int dmm_refine_train_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, int B, int O,
+                                        int n_obj, int H, int W, float *outs, dmm_stream_t stream);
+DMM_API int dmm_refine_train_finish_bwd_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w,
+                                            const float *d_outs, int B, int O, int n_obj, int H, int W, float *d_logits,
+                                            int64_t sb_d, int64_t so_d, dmm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (13) The soft-IoU mask loss of the trainer's frame step, forward and backward, with the logged hard IoU riding along.
