@@ -63,7 +63,7 @@ def __getattr__(name):
         from . import losses
         return getattr(losses, name)
     # the DAVIS J / F scores (measures.py), lazily too
-    if name in ("clip_counts", "scores_from_counts", "sequence_results", "ClipScorer"):
+    if name in ("clip_counts", "scores_from_counts", "sequence_results", "dataset_results", "ClipScorer"):
         from . import measures
         return getattr(measures, name)
     # the clip augmentation (augment.py), lazily too

@@ -9,6 +9,10 @@
 // v(dx) = floor(sqrt(r^2 - dx^2)).  v grows as |dx| falls from r to 0, so one walk adds each row to U once and shifts U once
 // per dx: 2 r + 1 rows and r + 1 shifted pairs per word instead of a full footprint.  All outputs are integers and integer
 // addition commutes: the atomics below give the same bytes on every run.
+// (14b), (14d): the reference's nearest resize of a prediction whose size is not the annotation's (jaccard.py:28-32,
+// f_boundary.py:34-38; PIL's ImagingScaleAffine) as two index tables walked by sequential double additions and one gather
+// pass into a frame of the annotation's size, which (14) then scores.  (A gather inside stage 1 instead -- (14c) -- was built
+// and measured slower than these two steps: every object's workgroups repeat it.  profiles/r13_davis_resized.md.)
 #include "dmm_launchers.h"
 
 namespace dmm {
@@ -173,6 +177,56 @@ __global__ __launch_bounds__(kMeasThreads) void davis_counts_kernel(
     if (threadIdx.x < 6 && cnt_s[threadIdx.x]) atomicAdd(&counts[((int64_t)f * n_obj + o) * 6 + threadIdx.x], cnt_s[threadIdx.x]);
 }
 
+// (14b) one lane per axis walks the source coordinate by the sequential double additions of the rule; block 0 the rows,
+// block 1 the columns.  `a` comes from the launcher's own division.
+__global__ __launch_bounds__(kWave) void nearest_tables_kernel(int H, int W, double ay, double ax, int32_t *__restrict__ tab) {
+    if (threadIdx.x != 0) return;
+    const int n = blockIdx.x ? W : H;
+    const double a = blockIdx.x ? ax : ay;
+    int32_t *t = tab + (blockIdx.x ? H : 0);
+    double o = a * 0.5;
+    for (int i = 0; i < n; ++i) {
+        t[i] = o < 0 ? -1 : (int)o;
+        o += a;
+    }
+}
+
+// (14d) four consecutive bytes of a frame per thread, counted from the 4-byte boundary at or below the frame's first byte,
+// so that every full group is one aligned 32-bit store whatever W and the frame stride are.
+constexpr int kResizeThreads = 256;
+__global__ __launch_bounds__(kResizeThreads) void resize_labels_kernel(
+    const uint8_t *__restrict__ srcp, int Hs, int Ws, int64_t fs_src, uint8_t *__restrict__ dst, int H, int W, int64_t fs_dst,
+    const int32_t *__restrict__ tab, unsigned blocks_per_frame) {
+    const int f = blockIdx.x / blocks_per_frame;
+    const int64_t HW = (int64_t)H * W;
+    const uint8_t *s = srcp + (int64_t)f * fs_src;
+    uint8_t *d = dst + (int64_t)f * fs_dst;
+    const int lead = (int)((uintptr_t)d & 3);
+    const int64_t i0 = ((int64_t)(blockIdx.x % blocks_per_frame) * kResizeThreads + threadIdx.x) * 4 - lead;
+    if (i0 >= HW) return;
+    int y = (int)((i0 < 0 ? 0 : i0) / W), x = (int)((i0 < 0 ? 0 : i0) - (int64_t)y * W);
+    uint32_t v = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int64_t i = i0 + k;
+        if (i < 0 || i >= HW) continue;
+        const int ty = tab[y], tx = tab[H + x];
+        const uint32_t l = ty >= 0 && ty < Hs && tx >= 0 && tx < Ws ? s[(int64_t)ty * Ws + tx] : 0;
+        v |= l << (8 * k);
+        if (++x == W) {
+            x = 0;
+            ++y;
+        }
+    }
+    if (i0 >= 0 && i0 + 4 <= HW) {
+        *(uint32_t *)(d + i0) = v;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i0 + k >= 0 && i0 + k < HW) d[i0 + k] = (uint8_t)(v >> (8 * k));
+    }
+}
+
 // The answers of the entry, in the order include/dmm_match.h (14) lists.  *go = true: launch.
 static int davis_counts_check(const void *pred, const void *gt, int frames, int n_obj, int H, int W, int64_t fs_pred,
                               int64_t fs_gt, int radius, const void *counts, const void *workspace, size_t workspace_bytes,
@@ -216,5 +270,36 @@ extern "C" int dmm_davis_counts_u8(const uint8_t *pred, const uint8_t *gt, int f
     const unsigned grid = (unsigned)((int64_t)frames * n_obj * t.bands * t.xtiles);
     hipLaunchKernelGGL(davis_counts_kernel, dim3(grid), dim3(kMeasThreads), 0, (hipStream_t)stream, pred, gt, n_obj, H, W,
                        frame_stride_pred, frame_stride_gt, radius, t.bh, t.tw, t.bands, t.xtiles, counts);
+    return check_launch();
+}
+
+extern "C" int dmm_nearest_index_tables_i32(int Hs, int Ws, int H, int W, int32_t *tables, dmm_stream_t stream) {
+    using namespace dmm;
+    if (Hs < 0 || Ws < 0 || H < 0 || W < 0) return DMM_ERR_BAD_ARG;
+    if (H + W == 0) return DMM_OK;
+    if (!tables) return DMM_ERR_BAD_ARG;
+    if (Hs > DMM_NEAREST_MAX_AXIS || Ws > DMM_NEAREST_MAX_AXIS || H > DMM_NEAREST_MAX_AXIS || W > DMM_NEAREST_MAX_AXIS)
+        return DMM_ERR_UNSUPPORTED;
+    const double ay = H ? (double)Hs / (double)H : 0.0, ax = W ? (double)Ws / (double)W : 0.0;    // the rule's plain division
+    hipLaunchKernelGGL(nearest_tables_kernel, dim3(2), dim3(kWave), 0, (hipStream_t)stream, H, W, ay, ax, tables);
+    return check_launch();
+}
+
+extern "C" int dmm_resize_labels_nearest_u8(const uint8_t *src, int Hs, int Ws, int64_t frame_stride_src, uint8_t *dst, int H,
+                                            int W, int64_t frame_stride_dst, const int32_t *tables, int frames,
+                                            dmm_stream_t stream) {
+    using namespace dmm;
+    if (frames < 0 || Hs < 0 || Ws < 0 || H < 0 || W < 0) return DMM_ERR_BAD_ARG;
+    const int64_t HW = (int64_t)H * W, HWs = (int64_t)Hs * Ws;
+    if (frame_stride_src < HWs || frame_stride_dst < HW) return DMM_ERR_BAD_ARG;
+    if (frames == 0 || HW == 0) return DMM_OK;
+    if (!src || !dst || !tables || (const void *)src == (const void *)dst) return DMM_ERR_BAD_ARG;
+    if (HW >= ((int64_t)1 << 31) || HWs >= ((int64_t)1 << 31)) return DMM_ERR_UNSUPPORTED;
+    const int64_t per_frame = ((HW + 3) / 4 + 1 + kResizeThreads - 1) / kResizeThreads;      // (+ 1: the group the lead splits)
+    // the grid stays below 2^32 THREADS (HIP runtimes have refused gridDim.x * blockDim.x past 32 bits): 2^24 workgroups,
+    // 16 GiB of output in one call
+    if (per_frame * frames >= DMM_RESIZE_MAX_WORKGROUPS) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(resize_labels_kernel, dim3((unsigned)(per_frame * frames)), dim3(kResizeThreads), 0, (hipStream_t)stream,
+                       src, Hs, Ws, frame_stride_src, dst, H, W, frame_stride_dst, tables, (unsigned)per_frame);
     return check_launch();
 }

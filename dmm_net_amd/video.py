@@ -85,6 +85,24 @@ def merge_labels(outs: torch.Tensor, tplt_valid_batch: Optional[torch.Tensor] = 
     return labels.view(B, *shape[2:])
 
 
+def resize_labels(labels, size, tables=None):
+    """Label maps [..,Hs,Ws] -> [..,H,W] (``size`` = (H, W)) by the reference's resize of a prediction, PIL's
+    ``Image.resize((W, H), Image.NEAREST)`` (jaccard.py:28-32; the index rule of ``measures.nearest_table``): for PNGs at the
+    annotation's size.  uint8 device tensors go through ``dmm_resize_labels_nearest_u8`` (include/dmm_match.h (14d)) on the
+    current stream; ``tables`` = ``measures.nearest_tables((Hs, Ws), size, device)`` when the caller keeps them, else they are
+    built here (one more launch).  numpy arrays take the host form."""
+    from . import measures
+    H, W = (int(v) for v in size)
+    if not isinstance(labels, torch.Tensor):
+        return measures.resize_labels_host(labels, (H, W))
+    if not labels.is_cuda:
+        raise _lib.DmmError("dmm_net_amd.video needs tensors on an MI355X device (no CPU fallback)")
+    if labels.dtype != torch.uint8 or labels.dim() < 2:
+        raise ValueError(f"labels are uint8 [..,Hs,Ws], not {labels.dtype} {tuple(labels.shape)}")
+    out = measures.resize_labels_device(labels.reshape(-1, *labels.shape[-2:]), (H, W), tables)
+    return out.view(*labels.shape[:-2], H, W)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # output format: indexed PNG with the DAVIS palette
 # ------------------------------------------------------------------------------------------------------------------

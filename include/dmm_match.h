@@ -1057,6 +1057,48 @@ DMM_API int dmm_davis_counts_u8(const uint8_t *pred, const uint8_t *gt, int fram
                                 size_t workspace_bytes, dmm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * (14b), (14d) The nearest resize of a prediction whose size Hs x Ws is not the annotation's H x W, so that (14) can score it.
+ * Replaces the resize both measures make first -- Image.resize((w, h), Image.NEAREST) of the prediction at
+ * dmm/measures/jaccard.py:28-32 and dmm/measures/f_boundary.py:34-38 -- which is PIL's ImagingScaleAffine: per axis a source
+ * coordinate walked by repeated double additions, NOT floor((i + 0.5) * n_in / n_out) (the two differ on 448 -> 854).
+ * The index rule, for one axis of n_in source and n_out destination samples:
+ *   a = (double)n_in / (double)n_out;  o = a * 0.5;
+ *   for i in 0 .. n_out - 1:  tab[i] = (o < 0 ? -1 : (int)o);  o += a;          (sequential double additions)
+ * Destination pixel (y, x) reads source pixel (tab_y[y], tab_x[x]); an index outside [0, n_in) reads as label 0 (PIL leaves
+ * that pixel of its zeroed output unset).  `a` is formed on the host, in the launcher, by exactly that C division; the
+ * additions run on the device, one after the other, in IEEE double (the library is built without contraction or fast-math).
+ * The radius of (14) stays the caller's: the reference takes bound_pix from the prediction's shape BEFORE the resize
+ * (f_boundary.py:30-31), which dmm_net_amd/measures.py follows.
+ *
+ * (14b) dmm_nearest_index_tables_i32 writes tables[0 .. H) = tab_y (Hs -> H) and tables[H .. H + W) = tab_x (Ws -> W).  One
+ * launch; one lane per axis does the walk.  The tables belong to the caller, who builds them once per size pair and reuses
+ * them: a scorer resizes once per frame.  Capturable.  What the entry answers, in this order:
+ *   1. DMM_ERR_BAD_ARG      Hs, Ws, H or W negative
+ *   2. DMM_OK               H + W == 0: nothing to do, nothing launched, pointer not looked at
+ *   3. DMM_ERR_BAD_ARG      tables null
+ *   4. DMM_ERR_UNSUPPORTED  Hs, Ws, H or W above DMM_NEAREST_MAX_AXIS
+ *
+ * (14c) is not there: dmm_davis_counts_resized_u8, (14) with its prediction load a gather through the tables, was built and
+ * measured against (14d) followed by (14) and was the slower of the two (profiles/r13_davis_resized.md: each object's
+ * workgroups repeat the gather that (14d) makes once).  Resized scoring is (14d) into a buffer, then (14).
+ *
+ * (14d) dmm_resize_labels_nearest_u8 is the resize: dst[f, y, x] = src[f, tab_y[y], tab_x[x]], frame f at
+ * src + f * frame_stride_src and dst + f * frame_stride_dst, dense rows; `tables` is read as it stands (any int32 values: an
+ * entry outside the source reads as label 0).  One launch, no host read, no allocation: capturable.  What it answers, in order:
+ *   1. DMM_ERR_BAD_ARG      frames, Hs, Ws, H or W negative, frame_stride_src below Hs * Ws or frame_stride_dst below H * W
+ *   2. DMM_OK               frames == 0, H == 0 or W == 0: nothing to do, nothing launched, pointers not looked at
+ *   3. DMM_ERR_BAD_ARG      src, dst or tables null, or dst == src (a gather cannot run in place)
+ *   4. DMM_ERR_UNSUPPORTED  H * W or Hs * Ws >= 2^31, or DMM_RESIZE_MAX_WORKGROUPS or more workgroups, where a workgroup writes
+ *                           1024 bytes and a frame takes ceil((ceil(H * W / 4) + 1) / 256) of them (the grid stays below
+ *                           2^32 threads: split a larger clip into several calls)
+ * ------------------------------------------------------------------------------------------- */
+#define DMM_RESIZE_MAX_WORKGROUPS 16777216 /* 2^24 workgroups of 256 threads: 16 GiB of labels in one call */
+#define DMM_NEAREST_MAX_AXIS 16384 /* one lane walks an axis, one dependent double addition per sample: the cap bounds (14b) */
+DMM_API int dmm_nearest_index_tables_i32(int Hs, int Ws, int H, int W, int32_t *tables, dmm_stream_t stream);
+DMM_API int dmm_resize_labels_nearest_u8(const uint8_t *src, int Hs, int Ws, int64_t frame_stride_src, uint8_t *dst, int H, int W,
+                                         int64_t frame_stride_dst, const int32_t *tables, int frames, dmm_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * (15) The augmentation of training clips: one nearest-neighbour affine warp per frame, applied to the image planes, the
  * annotation and every pasted proposal mask, with the proposals' boxes and the target planes out of the same pass.  Replaces
  * the per-plane Python loop of dmm/dataloader/dataset.py:222-258 -- the clip's flip, Affine(tf_matrix, interp='nearest')

@@ -1,6 +1,6 @@
 """Times the DAVIS counts of one clip on the GPU against the host yardstick, and prints ONE JSON line.
 
-    python tools/measures_timing.py [--out FILE] [--repeats 5] [--iters 10] [--host-frames 4]
+    python tools/measures_timing.py [--out FILE] [--repeats 5] [--iters 10] [--host-frames 4] [--pred-size 255x448]
 
 36 frames x 3 objects at 480 x 854 and at 255 x 448 (blob annotations, predictions a few pixels off), the radius the
 reference takes for the size (8 and 5).  Per size:
@@ -11,7 +11,16 @@ reference takes for the size (8 and 5).  Per size:
   bytes    what the kernel must read: 2 * T * H * W label bytes, times the passes it makes over them (one per object, times
            the halo rows and words a band re-reads: the tiling rule of include/dmm_match.h (14) evaluated here), against the
            median time
-The device counts of the timed frames are compared with the host's before anything is reported."""
+The device counts of the timed frames are compared with the host's before anything is reported.
+
+``--pred-size HsxWs`` adds "resized": the same clip's predictions at Hs x Ws scored against the 480 x 854 annotations
+(include/dmm_match.h (14b), (14d), (14)), tables prebuilt, the radius the reference takes for the prediction's size:
+  resize     (14d) ``dmm_resize_labels_nearest_u8`` alone, into a 480 x 854 buffer
+  two_step   (14d), then (14) on the buffer (resize + clear + counts), tables prebuilt: what ``ClipScorer(pred_size=...)`` runs
+  public     ``measures.clip_counts(pred, gt, n_obj, resize=True)`` itself: (14b) on every call as well (it keeps no tables)
+each once over the whole clip and once frame by frame (36 calls, the way ``ClipScorer`` makes them), in us per clip; the counts
+are compared with the host yardstick on the numpy-resized prediction first.  (The fused route this was measured against, the
+counts kernel with its prediction load a gather, is not in the library: profiles/r13_davis_resized.md.)"""
 import argparse
 import json
 import os
@@ -27,6 +36,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import measures_ref  # noqa: E402
 from dmm_net_amd import measures  # noqa: E402
+from dmm_net_amd import video  # noqa: E402
 
 LDS_WORDS = 1280          # csrc/dmm_measures.hip kMeasCap
 
@@ -71,8 +81,53 @@ def passes(H, W, radius, n_obj):
     return n_obj * (row_reads / H) * (word_reads / wpr)
 
 
+def resized(a, T, n_obj, pred_size, size=(480, 854)):
+    """The shipped route of a (Hs, Ws) clip against ``size`` annotations, and its resize alone."""
+    (Hs, Ws), (H, W) = pred_size, size
+    pred, _ = blobs(np.random.default_rng(Hs), T, Hs, Ws, n_obj)
+    _, gt = blobs(np.random.default_rng(H), T, H, W, n_obj)
+    radius = measures.boundary_radius((Hs, Ws))
+    dp, dg = torch.from_numpy(pred).to("cuda:0"), torch.from_numpy(gt).to("cuda:0")
+    tables = measures.nearest_tables((Hs, Ws), (H, W), dp.device)
+    counts = torch.empty((T, n_obj, measures.N_COUNTS), dtype=torch.int32, device=dp.device)
+
+    def resize():
+        video.resize_labels(dp, (H, W), tables=tables)
+
+    def two_step():
+        measures._counts_into(video.resize_labels(dp, (H, W), tables=tables), dg, n_obj, radius, counts)
+
+    def public():
+        measures.clip_counts(dp, dg, n_obj, resize=True)
+
+    def resize_frames():
+        for t in range(T):
+            video.resize_labels(dp[t:t + 1], (H, W), tables=tables)
+
+    def two_step_frames():
+        for t in range(T):
+            measures._counts_into(video.resize_labels(dp[t:t + 1], (H, W), tables=tables), dg[t:t + 1], n_obj, radius,
+                                  counts[t:t + 1])
+
+    k = a.host_frames
+    host_resized = measures.resize_labels_host(pred[:k], (H, W))
+    want = measures_ref.counts(host_resized, gt[:k], n_obj, radius)
+    assert np.array_equal(video.resize_labels(dp[:k], (H, W), tables=tables).cpu().numpy(), host_resized)
+    out = {"pred_size": f"{Hs}x{Ws}", "size": f"{H}x{W}", "radius": radius}
+    for name, fn in (("two_step", two_step), ("two_step_frames", two_step_frames)):
+        counts.fill_(-1)
+        fn()
+        assert np.array_equal(counts[:k].cpu().numpy(), want), name + ": device counts differ from the host yardstick"
+    assert np.array_equal(measures.clip_counts(dp[:k], dg[:k], n_obj, resize=True).cpu().numpy(), want)
+    for name, fn in (("resize", resize), ("two_step", two_step), ("public", public), ("resize_frames", resize_frames),
+                     ("two_step_frames", two_step_frames)):
+        out[name + "_us"] = windows(fn, a.repeats, a.iters)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--pred-size", default=None, help="HsxWs: also time the resized routes against 480x854 annotations")
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
@@ -100,6 +155,8 @@ def main():
         res["sizes"][f"{H}x{W}"] = {"radius": radius, "device_us": dev_us, "host_one_thread_s": host_s,
                                     "label_bytes": 2 * T * H * W, "passes": p, "bytes_read": nbytes,
                                     "bytes_per_s": nbytes / (dev_us["median"] * 1e-6)}
+    if a.pred_size:
+        res["resized"] = resized(a, T, n_obj, tuple(int(v) for v in a.pred_size.lower().split("x")))
     line = json.dumps(res)
     print(line)
     if a.out:
