@@ -70,6 +70,10 @@ def __getattr__(name):
     if name in ("affine_matrix", "draw_clip_params", "augment_clip", "AugmentedClip"):
         from . import augment
         return getattr(augment, name)
+    # the frame preparation (frames.py), lazily too
+    if name in ("resample_tables", "normalise_lut", "resize_frames_host", "prepare_frames", "ClipPreparer", "FrameTables"):
+        from . import frames
+        return getattr(frames, name)
     raise AttributeError(f"module 'dmm_net_amd' has no attribute '{name}'")
 
 

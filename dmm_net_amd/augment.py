@@ -10,8 +10,10 @@ the dataset with ``augment=False``, upload the raw clip, and call ``augment_clip
 Deviation from the reference: label 0 is ALWAYS background here.  On a frame with no background pixel at all the reference's
 ``np.unique(annot)[1:]`` (dataset.py:311) drops the smallest object id instead; that quirk is not reproduced.
 
-Out of scope: the transform library's bilinear mode (the reference's datasets always pass ``interp='nearest'``), image decode,
-resize and normalisation, and ``random_select_frames``.
+The frames it takes -- resized, ``ToTensor``'d and normalised -- come from ``frames.ClipPreparer`` (include/dmm_match.h (16)).
+
+Out of scope: the transform library's bilinear mode (the reference's datasets always pass ``interp='nearest'``), image decode
+and ``random_select_frames``.
 """
 from __future__ import annotations
 

@@ -1153,6 +1153,77 @@ DMM_API int dmm_augment_clip_f32(const float *frames_in, int64_t fs_frames_in, i
                                  const float *matrices, const int32_t *flips, int n, int C, int P, int F, int H, int W,
                                  void *workspace, size_t workspace_bytes, dmm_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * (16) Frames as the encoders take them, from decoded images: PIL's resize of an 8-bit RGB image, then ToTensor and Normalize.
+ * Replaces what the reference's dataset workers do per frame -- Image.open(jpg).resize((W, H)) at dmm/dataloader/dataset.py:
+ * 202-219, then transforms.ToTensor() and transforms.Normalize(mean, std), composed at train.py:76-77 and eval.py:51-52.
+ * Everything is an integer or a table look-up: the result equals the host pipeline bit for bit.
+ *
+ * A source frame is uint8 [Hs, Ws, 3], pixel-interleaved (np.array(Image.open(...))): frame f at src + f * fs_src, row y at
+ * + y * rs_src, 3 * Ws dense bytes per row.  The destination is H x W.
+ *
+ * Coefficient tables (dmm_prepare_frames_u8).  Per axis with n_in -> n_out the caller forms, on the host in IEEE double and in
+ * exactly this order (PIL's precompute_coeffs and normalize_coeffs_8bpc; dmm_net_amd/frames.py resample_tables):
+ *   scale = n_in / n_out;  fs = max(scale, 1.0);  support = filter_support * fs;  ksize = (int)ceil(support) * 2 + 1
+ *   for i in 0 .. n_out - 1:
+ *     center = (i + 0.5) * scale;  ss = 1.0 / fs
+ *     lo  = max((int)(center - support + 0.5), 0)
+ *     cnt = min((int)(center + support + 0.5), n_in) - lo
+ *     w[k] = filter((k + lo - center + 0.5) * ss)  for k in 0 .. cnt - 1
+ *     ww   = w[0] + w[1] + ...                                              (left to right)
+ *     if ww != 0: w[k] /= ww
+ *     coef[i][k] = (int)(w[k] * 2^22 + 0.5) if w[k] >= 0 else (int)(w[k] * 2^22 - 0.5)      ((int) truncates toward zero)
+ *     coef[i][cnt ..] = 0;  bounds[i] = (lo, cnt)
+ *   bilinear(x) (support 1):          x = |x|;  x < 1 ? 1 - x : 0
+ *   bicubic(x)  (support 2, a = -0.5): x = |x|;  x < 1 ? ((a + 2) * x - (a + 3)) * x * x + 1 : x < 2 ? (((x - 5) * x + 8) * x - 4) * a : 0
+ * bounds is int32 [n_out, 2], coef int32 [n_out, ksize], both dense.  One pass along an axis, per channel:
+ *   acc = 2^21 + sum_k coef[i][k] * src[lo + k]          (int32, wrapping)
+ *   out = clamp(acc >> 22, 0, 255)                       (arithmetic shift)
+ * The horizontal pass runs first into a uint8 intermediate [Hs, W, 3], the vertical pass follows into [H, W, 3]; the uint8
+ * rounding between them is part of the result.  A pass whose axis does not change size is skipped: no table, no launch, the
+ * same bytes.  The tables are read as they stand: lo is clamped into [0, n_in] and cnt into [0, min(ksize, n_in - lo)], so
+ * no values in them make a kernel read outside the source.
+ *
+ * Nearest (dmm_prepare_frames_nearest_u8).  PIL's affine walk, i.e. the index tables of (14b) as dmm_nearest_index_tables_i32
+ * writes them (tab_y [H], then tab_x [W]): dst[y, x, :] = src[tab_y[y], tab_x[x], :]; an index outside the source reads as 0.
+ *
+ * Normalisation.  out[c, y, x] = lut[c * 256 + u8], lut fp32 [3, 256] formed by the caller with the reference's own operations
+ * (dmm_net_amd/frames.py normalise_lut), so no device rounding enters.  out_f32: plane c of frame f at
+ * out_f32 + f * fs_out + c * ps_out, H dense rows of W floats (a slice of a larger batch is addressable).  out_u8: the resized
+ * image itself, what PIL returns, frame f at out_u8 + f * fs_u8, interleaved and dense.  Either may be null, not both; lut is
+ * needed with out_f32.  Strides are in elements.
+ *
+ * Launches: one per pass that runs -- at most two; one when one axis keeps its size, when both do (a copy through the look-up)
+ * and for nearest.  The last launch writes both outputs.  The horizontal kernel stages the span of each source row its columns
+ * need in LDS and writes the intermediate into the workspace with a row pitch of 3 * W rounded up to 16 bytes;
+ * dmm_prepare_frames_workspace_bytes is that, n * Hs rows of it, when both axes change and 0 otherwise (and for nearest).
+ * No allocation, no host read: capturable.
+ *
+ * What the entries answer, in this order (where two faults coincide, the earlier one is named):
+ *   1. DMM_ERR_BAD_ARG      n, C, Hs, Ws, H, W or a ksize negative; rs_src below 3 * Ws, fs_src below Hs * 3 * Ws; with out_f32
+ *                           given ps_out or fs_out below H * W; with out_u8 given fs_u8 below H * W * 3
+ *   2. DMM_OK               n == 0, H == 0 or W == 0: nothing to do, nothing launched, pointers not looked at
+ *   3. DMM_ERR_BAD_ARG      src null (unless Hs * Ws == 0 under nearest, where nothing is read); out_f32 and out_u8 both null;
+ *                           lut null with out_f32 given; bounds_x or coef_x null, or ksize_x == 0, when Ws != W, and likewise
+ *                           for y when Hs != H (a table is required exactly when its axis changes size); tables null (nearest)
+ *   4. DMM_ERR_UNSUPPORTED  C != 3 (other modes are out of scope); Hs, Ws, H or W above DMM_NEAREST_MAX_AXIS; Hs or Ws == 0 with a table pass (PIL refuses an empty
+ *                           image); a required ksize above DMM_RESAMPLE_MAX_TAPS; Hs * Ws * 3, H * W * 3 or Hs * W * 3 >= 2^31,
+ *                           or DMM_RESIZE_MAX_WORKGROUPS or more workgroups in a launch (a grid stays below 2^32 threads: split
+ *                           a larger clip set into several calls)
+ *   5. DMM_ERR_WORKSPACE    the workspace is null, shorter than dmm_prepare_frames_workspace_bytes or not 16-byte aligned
+ *                           (when that size is not 0)
+ * ------------------------------------------------------------------------------------------- */
+#define DMM_RESAMPLE_MAX_TAPS 257 /* ksize of a 64-fold bicubic (128-fold bilinear) reduction */
+DMM_API size_t dmm_prepare_frames_workspace_bytes(int n, int Hs, int Ws, int H, int W);
+DMM_API int dmm_prepare_frames_u8(const uint8_t *src, int64_t fs_src, int64_t rs_src, int n, int C, int Hs, int Ws, int H,
+                                  int W, const int32_t *bounds_x, const int32_t *coef_x, int ksize_x, const int32_t *bounds_y,
+                                  const int32_t *coef_y, int ksize_y, const float *lut, float *out_f32, int64_t fs_out,
+                                  int64_t ps_out, uint8_t *out_u8, int64_t fs_u8, void *workspace, size_t workspace_bytes,
+                                  dmm_stream_t stream);
+DMM_API int dmm_prepare_frames_nearest_u8(const uint8_t *src, int64_t fs_src, int64_t rs_src, int n, int C, int Hs, int Ws, int H,
+                                          int W, const int32_t *tables, const float *lut, float *out_f32, int64_t fs_out, int64_t ps_out,
+                                          uint8_t *out_u8, int64_t fs_u8, dmm_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
