@@ -40,6 +40,7 @@ Three execution forms behind the one ``forward``:
 """
 from __future__ import annotations
 
+import math
 from typing import List, Optional, Sequence
 
 import torch
@@ -64,6 +65,16 @@ def _stream(t: torch.Tensor):
     return torch.cuda.current_stream(t.device).cuda_stream
 
 
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _batch_stride(t: torch.Tensor):
+    """The batch stride the entries are handed: torch may report anything for a dimension of size 1, so the batch stride of
+    a B == 1 tensor is the sample size."""
+    return t.stride(0) if t.shape[0] > 1 else math.prod(t.shape[1:])
+
+
 def _plane_strides(t: torch.Tensor, H: int, W: int):
     """[B, O, H*W] or [B, O, H, W] fp32 with dense planes -> (tensor, batch stride, object stride)."""
     assert t.dtype == torch.float32 and t.dim() in (3, 4), (t.shape, t.dtype)
@@ -78,6 +89,11 @@ def pyramid_sizes(H: int, W: int):
     return [(-(-H // (1 << k)), -(-W // (1 << k))) for k in (5, 4, 3, 2)]
 
 
+def _check_on_pyramid(feats, H: int, W: int):
+    for f, s in zip(feats, pyramid_sizes(H, W)):
+        assert tuple(f.shape[-2:]) == s, ("refine_input_feat does not sit on the mask pyramid", f.shape, s)
+
+
 def mask_pyramid(prev_mask, y_mask, init_pred, n_obj: int, H: int, W: int, out: Optional[Sequence[torch.Tensor]] = None):
     """evaluator.py:188-195 for objects 0..n_obj-1 in one launch -> 4 tensors [n_obj, B, 3, h_l, w_l], coarsest first."""
     _need_device(prev_mask)
@@ -88,17 +104,40 @@ def mask_pyramid(prev_mask, y_mask, init_pred, n_obj: int, H: int, W: int, out: 
     assert n_obj <= min(prev_mask.shape[1], y_mask.shape[1], init_pred.shape[1])
     if out is None:
         out = [torch.empty((n_obj, B, 3, h, w), dtype=torch.float32, device=prev_mask.device) for h, w in pyramid_sizes(H, W)]
-    _lib.call("dmm_mask_pyramid_f32", prev_mask.device, prev_mask.data_ptr(), y_mask.data_ptr(), init_pred.data_ptr(),
-              sbp, sop, sby, soy, sbi, soi, B, n_obj, H, W, *[o.data_ptr() for o in out], _stream(prev_mask))
+    _lib.call("dmm_mask_pyramid_f32", prev_mask.device, _ptr(prev_mask), _ptr(y_mask), _ptr(init_pred),
+              sbp, sop, sby, soy, sbi, soi, B, n_obj, H, W, *[_ptr(o) for o in out], _stream(prev_mask))
     return list(out)
+
+
+def _dense_samples(t: torch.Tensor):
+    """Is every [C, h, w] sample of t [B, C, h, w] dense (whatever the batch stride)?"""
+    h, w = t.shape[2:]
+    return t.stride(3) == 1 and t.stride(2) == w and t.stride(1) == h * w
 
 
 def _dense_batch(t: torch.Tensor):
     """[B, C, h, w] with dense [C, h, w] samples -> (tensor, batch stride)."""
-    C, h, w = t.shape[1:]
-    if not (t.stride(3) == 1 and t.stride(2) == w and t.stride(1) == h * w):
+    if not _dense_samples(t):
         t = t.contiguous()
-    return t, (t.stride(0) if t.shape[0] > 1 else C * h * w)
+    return t, _batch_stride(t)
+
+
+def _addends(pre: Sequence[Optional[torch.Tensor]], shape=None):
+    """The up to three addends of the cell's pre-activation (None entries skipped), each fp32 of ``shape`` = [B, 4*Hd, h, w]
+    (default: the first one's) -> (pointers, batch strides, the tensors behind the pointers), the first two padded to three."""
+    pre = [p for p in pre if p is not None]
+    assert 1 <= len(pre) <= 3
+    shape = tuple(pre[0].shape if shape is None else shape)
+    ptrs, strides, keep = [], [], []
+    for p in pre:
+        assert tuple(p.shape) == shape and p.dtype == torch.float32, (p.shape, shape)
+        p, sb = _dense_batch(p)
+        keep.append(p)
+        ptrs.append(p.data_ptr())
+        strides.append(sb)
+    ptrs += [None] * (3 - len(ptrs))
+    strides += [0] * (3 - len(strides))
+    return ptrs, strides, keep
 
 
 def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev, hidden, cell, hidden_copy=None):
@@ -106,19 +145,8 @@ def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev,
     [B, Hd, h, w] or None; writes ``hidden`` / ``cell`` (dense) and, when given, ``hidden_copy`` (a channel slice of the
     next evaluation's convolution input)."""
     _need_device(masks)
-    pre = [p for p in pre if p is not None]
-    assert 1 <= len(pre) <= 3
     B, Hd, h, w = hidden.shape
-    ptrs, strides = [], []
-    keep = []
-    for p in pre:
-        assert tuple(p.shape) == (B, 4 * Hd, h, w) and p.dtype == torch.float32, (p.shape, hidden.shape)
-        p, sb = _dense_batch(p)
-        keep.append(p)
-        ptrs.append(p.data_ptr())
-        strides.append(sb)
-    ptrs += [None] * (3 - len(ptrs))
-    strides += [0] * (3 - len(strides))
+    ptrs, strides, keep = _addends(pre, (B, 4 * Hd, h, w))
     masks, sbm = _dense_batch(masks)
     assert tuple(masks.shape) == (B, 3, h, w) and w_mask.is_contiguous() and tuple(w_mask.shape) == (4 * Hd, 9)
     assert hidden.is_contiguous() and cell.is_contiguous() and tuple(cell.shape) == (B, Hd, h, w)
@@ -127,12 +155,10 @@ def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev,
         assert tuple(cell_prev.shape) == (B, Hd, h, w)
     sbc = 0
     if hidden_copy is not None:
-        assert tuple(hidden_copy.shape) == (B, Hd, h, w) and hidden_copy.stride(3) == 1 and hidden_copy.stride(2) == w \
-            and hidden_copy.stride(1) == h * w
-        sbc = hidden_copy.stride(0) if B > 1 else max(hidden_copy.stride(0), Hd * h * w)
-    _lib.call("dmm_clstm_gates_f32", masks.device, *ptrs, *strides, masks.data_ptr(), sbm, w_mask.data_ptr(),
-              None if cell_prev is None else cell_prev.data_ptr(), B, Hd, h, w, hidden.data_ptr(), cell.data_ptr(),
-              None if hidden_copy is None else hidden_copy.data_ptr(), sbc, _stream(masks))
+        assert tuple(hidden_copy.shape) == (B, Hd, h, w) and _dense_samples(hidden_copy)
+        sbc = _batch_stride(hidden_copy)
+    _lib.call("dmm_clstm_gates_f32", masks.device, *ptrs, *strides, _ptr(masks), sbm, _ptr(w_mask), _ptr(cell_prev),
+              B, Hd, h, w, _ptr(hidden), _ptr(cell), _ptr(hidden_copy), sbc, _stream(masks))
     return hidden, cell
 
 
@@ -144,21 +170,12 @@ def clstm_gates_bwd(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_p
     ``d_masks`` [B, 3, h, w], ``d_w_mask`` [4*Hd, 9] are wanted (the others are None and cost nothing).  The gates are
     recomputed from the inputs; bit-reproducible."""
     _need_device(masks)
-    pre = [p for p in pre if p is not None]
-    assert 1 <= len(pre) <= 3
-    B, C4, h, w = pre[0].shape
+    ptrs, strides, keep = _addends(pre)
+    B, C4, h, w = keep[0].shape
     Hd = C4 // 4
+    assert C4 == 4 * Hd, keep[0].shape
     need_cell, need_masks, need_w = (bool(n) for n in need)
     assert not need_cell or cell_prev is not None, "d_cell_prev without cell_prev"
-    ptrs, strides, keep = [], [], []
-    for p in pre:
-        assert tuple(p.shape) == (B, 4 * Hd, h, w) and p.dtype == torch.float32, (p.shape, pre[0].shape)
-        p, sb = _dense_batch(p)
-        keep.append(p)
-        ptrs.append(p.data_ptr())
-        strides.append(sb)
-    ptrs += [None] * (3 - len(ptrs))
-    strides += [0] * (3 - len(strides))
     masks, sbm = _dense_batch(masks)
     w_mask = w_mask.contiguous()
     assert tuple(masks.shape) == (B, 3, h, w) and tuple(w_mask.shape) == (4 * Hd, 9)
@@ -179,9 +196,8 @@ def clstm_gates_bwd(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_p
     if need_masks or need_w:
         ws_bytes = int(_lib.load().dmm_clstm_gates_bwd_workspace_bytes(B, Hd, h, w))
         ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.float32, device=masks.device)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    _lib.call("dmm_clstm_gates_bwd_f32", masks.device, *ptrs, *strides, masks.data_ptr(), sbm, w_mask.data_ptr(), ptr(cell_prev),
-              B, Hd, h, w, ptr(d_hidden), ptr(d_cell), d_pre.data_ptr(), ptr(d_cell_prev), ptr(d_masks), ptr(d_w_mask), ptr(ws),
+    _lib.call("dmm_clstm_gates_bwd_f32", masks.device, *ptrs, *strides, _ptr(masks), sbm, _ptr(w_mask), _ptr(cell_prev),
+              B, Hd, h, w, _ptr(d_hidden), _ptr(d_cell), _ptr(d_pre), _ptr(d_cell_prev), _ptr(d_masks), _ptr(d_w_mask), _ptr(ws),
               ws_bytes, _stream(masks))
     return d_pre, d_cell_prev, d_masks, d_w_mask
 
@@ -246,6 +262,14 @@ class _WeightSlices(torch.autograd.Function):
         return torch.cat(parts, 1), None
 
 
+def _chain_weight(d):
+    """``cat`` = [up | hs] of one level's slices (``RSISMask._cut_slices``; levels >= 1), made on first use and kept with them:
+    the training form needs it only once an object has a spatial state, and then once for every object of the frame."""
+    if d["cat"] is None:
+        d["cat"] = torch.cat([d["up"], d["hs"]], 1)
+    return d["cat"]
+
+
 class _ConvStacked(torch.autograd.Function):
     """``apply(x, weight, bias, chunks)``: ONE 3x3 / padding 1 convolution of ``x`` = ``chunks`` equal groups of samples
     stacked along the batch (the objects of a frame), and one data-gradient call for all of them; the gradients of ``weight``
@@ -287,10 +311,8 @@ def upsample_bilinear_into(src, dst, c0: int = 0, mode: str = "write"):
     src, sbs = _dense_batch(src)
     B, C, h, w = src.shape
     Bd, Cd, H, W = dst.shape
-    assert Bd == B and dst.dtype == src.dtype == torch.float32 and dst.stride(3) == 1 and dst.stride(2) == W and \
-        dst.stride(1) == H * W, (src.shape, dst.shape, dst.stride())
-    sbd = dst.stride(0) if B > 1 else max(dst.stride(0), Cd * H * W)
-    _lib.call("dmm_upsample_bilinear_into_f32", src.device, src.data_ptr(), sbs, B, C, h, w, dst.data_ptr(), sbd, Cd, int(c0),
+    assert Bd == B and dst.dtype == src.dtype == torch.float32 and _dense_samples(dst), (src.shape, dst.shape, dst.stride())
+    _lib.call("dmm_upsample_bilinear_into_f32", src.device, _ptr(src), sbs, B, C, h, w, _ptr(dst), _batch_stride(dst), Cd, int(c0),
               H, W, _UP_MODE[mode], _stream(src))
     return dst
 
@@ -307,9 +329,8 @@ def refine_finish(logits, valid_i32, outs, mask_hist, n_obj: int):
                                  tuple(valid_i32.shape) == (B, O))
     h, w = logits.shape[-2:]
     assert logits.shape[0] == B and logits.shape[1] >= n_obj and logits.stride(3) == 1 and logits.stride(2) == w
-    _lib.call("dmm_refine_finish_f32", outs.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w,
-              None if valid_i32 is None else valid_i32.data_ptr(), B, O, int(n_obj), H, W, outs.data_ptr(),
-              None if mask_hist is None else mask_hist.data_ptr(), _stream(outs))
+    _lib.call("dmm_refine_finish_f32", outs.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w, _ptr(valid_i32),
+              B, O, int(n_obj), H, W, _ptr(outs), _ptr(mask_hist), _stream(outs))
     return outs
 
 
@@ -317,9 +338,6 @@ def refine_finish(logits, valid_i32, outs, mask_hist, n_obj: int):
 # what the refine step of training runs around the decoder (include/dmm_match.h (12f)-(12h)): launchers, the autograd
 # functions over them, and for each its torch-op twin -- the same function in the ops the trainer uses
 # ------------------------------------------------------------------------------------------------------------------
-_ptr = lambda t: None if t is None else t.data_ptr()
-
-
 def mask_pyramid_bwd(prev_mask, init_pred, d_outs, n_obj: int, H: int, W: int, need=(True, True), out=None):
     """``dmm_mask_pyramid_bwd_f32``: the planes the forward read and the gradients of its four outputs (coarsest first,
     [n_obj, B, 3, h_l, w_l]; None = zeros) -> ``(d_prev, d_init)`` in the inputs' shapes; ``need`` says which is wanted (the
@@ -349,7 +367,7 @@ def mask_pyramid_bwd(prev_mask, init_pred, d_outs, n_obj: int, H: int, W: int, n
                 g[:, n_obj:].zero_()
         res.append(g)
     strides = lambda g: (0, H * W) if g is None else (g.stride(0), max(g.stride(1), H * W))
-    _lib.call("dmm_mask_pyramid_bwd_f32", prev_c.device, prev_c.data_ptr(), init_c.data_ptr(), sbp, sop, sbi, soi, B, int(n_obj),
+    _lib.call("dmm_mask_pyramid_bwd_f32", prev_c.device, _ptr(prev_c), _ptr(init_c), sbp, sop, sbi, soi, B, int(n_obj),
               H, W, *[_ptr(d) for d in ds], _ptr(res[0]), *strides(res[0]), _ptr(res[1]), *strides(res[1]), _stream(prev_c))
     if out is None:
         res = [None if g is None else g.view(like.shape) for g, like in zip(res, (prev_mask, init_pred))]
@@ -407,8 +425,8 @@ def upsample_bilinear_bwd(d_dst, c0: int, C: int, h: int, w: int):
     d_dst, sbd = _dense_batch(d_dst)
     B, Cd, H, W = d_dst.shape
     d_src = torch.empty((B, C, h, w), dtype=torch.float32, device=d_dst.device)
-    _lib.call("dmm_upsample_bilinear_bwd_f32", d_dst.device, d_dst.data_ptr(), sbd, B, int(C), H, W, Cd, int(c0),
-              d_src.data_ptr(), C * h * w, int(h), int(w), _stream(d_dst))
+    _lib.call("dmm_upsample_bilinear_bwd_f32", d_dst.device, _ptr(d_dst), sbd, B, int(C), H, W, Cd, int(c0),
+              _ptr(d_src), C * h * w, int(h), int(w), _stream(d_dst))
     return d_src
 
 
@@ -457,8 +475,8 @@ def refine_train_finish(logits, O: int, H: int, W: int):
     logits = _logit_planes(logits)
     B, n_obj, h, w = logits.shape
     outs = torch.empty((B, O, H, W), dtype=torch.float32, device=logits.device)
-    _lib.call("dmm_refine_train_finish_f32", logits.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w, B, int(O),
-              n_obj, int(H), int(W), outs.data_ptr(), _stream(logits))
+    _lib.call("dmm_refine_train_finish_f32", logits.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w, B, int(O),
+              n_obj, int(H), int(W), _ptr(outs), _stream(logits))
     return outs
 
 
@@ -471,8 +489,8 @@ def refine_train_finish_bwd(logits, d_outs):
     d_outs = d_outs.contiguous()
     O, H, W = d_outs.shape[1:]
     d_logits = torch.empty((B, n_obj, h, w), dtype=torch.float32, device=logits.device)
-    _lib.call("dmm_refine_train_finish_bwd_f32", logits.device, logits.data_ptr(), logits.stride(0), logits.stride(1), h, w,
-              d_outs.data_ptr(), B, O, n_obj, H, W, d_logits.data_ptr(), n_obj * h * w, h * w, _stream(logits))
+    _lib.call("dmm_refine_train_finish_bwd_f32", logits.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w,
+              _ptr(d_outs), B, O, n_obj, H, W, _ptr(d_logits), n_obj * h * w, h * w, _stream(logits))
     return d_logits
 
 
@@ -624,57 +642,66 @@ class RSISMask(nn.Module):
         return self.conv_out(clstm_in), hidden_list
 
     # ---- fused form ------------------------------------------------------------------------------------------------------
-    def weight_slices(self):
-        """Per level the contiguous slices of ``Gates.weight`` ([4*Hd, Cin + 1 + 2*Hd, 3, 3], input channels in the order
-        x, mask, h_s, h_t): ``up`` = the share of the upsampled hidden of the level above (levels >= 1), ``skip`` = the skip
-        map's share (all of x at level 0; levels >= 1: the second half under 'concat', all of x under 'sum', none under
-        'mul' / 'none'), ``m`` [4*Hd, 9], ``hs``, ``ht``, ``cat`` = [up | hs] (one chain convolution).  Made once and kept
-        against the parameters' versions and storages."""
-        key = tuple((p.data_ptr(), p._version, p.device) for p in self.parameters())
-        if self._slices is not None and self._slices[0] == key:
-            return self._slices[1]
+    def _cut_slices(self, train: bool):
+        """The slice layout of ``Gates.weight`` ([4*Hd, Cin + 1 + 2*Hd, 3, 3], input channels in the order x, mask, h_s,
+        h_t), per level a dict: ``up`` = the share of the upsampled hidden of the level above (levels >= 1), ``skip`` = the
+        skip map's share (all of x at level 0; levels >= 1: the second half of x = [up | skip] under 'concat', all of x
+        under 'sum', none under 'mul' / 'none'), ``m`` [4*Hd, 9], ``hs``, ``ht``, ``bias`` and ``cat`` = [up | hs] (one chain
+        convolution on cat[x, h_s]; None at level 0).  ``train``: cut from the parameters themselves, so the slices carry
+        one ``_WeightSlices`` node per level, and ``cat`` is left to ``_chain_weight``; otherwise from the detached
+        parameters, ``cat`` included."""
         out = []
-        with torch.no_grad():
-            for i, cell in enumerate(self.clstm_list):
-                Wt, Hd = cell.Gates.weight, cell.hidden_size
-                cin = cell.input_size
-                x, m = Wt[:, :cin], Wt[:, cin:cin + 1]
-                hs, ht = Wt[:, cin + 1:cin + 1 + Hd], Wt[:, cin + 1 + Hd:]
-                d = {"m": m.reshape(4 * Hd, 9).contiguous(), "hs": hs.contiguous(), "ht": ht.contiguous(),
-                     "bias": cell.Gates.bias.detach(), "up": None, "skip": None, "cat": None}
-                if i == 0:
-                    d["skip"] = x.contiguous()
-                else:
-                    cup = self.skip_dims_out[i - 1]
-                    d["up"] = x[:, :cup].contiguous()
-                    if self.skip_mode == "concat":
-                        d["skip"] = x[:, cup:].contiguous()
-                    elif self.skip_mode == "sum":
-                        d["skip"] = d["up"]
-                    d["cat"] = torch.cat([d["up"], d["hs"]], 1).contiguous()
-                out.append(d)
-        self._slices = (key, out)
+        for i, cell in enumerate(self.clstm_list):
+            Wt, bias, Hd, cin = cell.Gates.weight, cell.Gates.bias, cell.hidden_size, cell.input_size
+            if not train:
+                Wt, bias = Wt.detach(), bias.detach()
+            cup = cin if i == 0 or self.skip_mode != "concat" else self.skip_dims_out[i - 1]
+            w_x, w_x2, w_m, w_hs, w_ht = _WeightSlices.apply(Wt, (0, cup, cin, cin + 1, cin + 1 + Hd, cin + 1 + 2 * Hd))
+            d = {"m": w_m.reshape(4 * Hd, 9), "hs": w_hs, "ht": w_ht, "bias": bias, "up": None, "skip": w_x, "cat": None}
+            if i > 0:
+                d["up"] = w_x
+                d["skip"] = w_x2 if self.skip_mode == "concat" else w_x if self.skip_mode == "sum" else None
+                if not train:
+                    _chain_weight(d)
+            out.append(d)
         return out
+
+    def weight_slices(self):
+        """The no-grad cut of ``_cut_slices`` (the fused form's), ``cat`` present.  Made once and kept against the
+        parameters' versions and storages."""
+        key = tuple((p.data_ptr(), p._version, p.device) for p in self.parameters())
+        if self._slices is None or self._slices[0] != key:
+            self._slices = (key, self._cut_slices(train=False))
+        return self._slices[1]
+
+    def train_slices(self):
+        """The differentiable cut of ``_cut_slices`` (the fused training form's).  One ``_WeightSlices`` node per level: a
+        caller that evaluates several objects of a frame on the same slices (``RefineTrainStep``) pays the assembly of the
+        weight's gradient once per frame."""
+        return self._cut_slices(train=True)
 
     def _conv(self, x, w, b=None):
         self.conv_calls += 1
         return F.conv2d(x, w, b, padding=1)
 
-    def skip_terms(self, skip_feats):
+    def skip_terms(self, skip_feats, slices=None):
         """The object-independent share of every level's pre-activation: conv(skip map, W_skip) + bias (None where the
-        level has no such term: 'mul' / 'none' above level 0).  Once per frame."""
-        sl = self.weight_slices()
+        level has no such term: 'mul' / 'none' above level 0).  Once per frame.  ``slices``: default ``weight_slices()``."""
+        sl = self.weight_slices() if slices is None else slices
         return [None if d["skip"] is None else self._conv(f, d["skip"], d["bias"]) for d, f in zip(sl, skip_feats)]
 
-    def temporal_terms(self, hidden_temporal):
+    def temporal_terms(self, hidden_temporal, slices=None):
         """conv(h_t, W_ht) per level; ``hidden_temporal[i]`` may stack every object of the frame along the batch."""
-        sl = self.weight_slices()
+        sl = self.weight_slices() if slices is None else slices
         return [self._conv(h, d["ht"]) for d, h in zip(sl, hidden_temporal)]
 
-    def _level(self, i, d, bufs, skip_term, temporal_term, skip, masks, state_spatial, hidden, cell, up_src):
-        """One level of one object: the chain convolution + the gate launch.  ``up_src``: the hidden of the level above
-        (None at level 0); ``bufs``: this level's scratch ('cat' [B, Cup + Hd, h, w] whose upper channels hold the previous
-        object's hidden of this level, 'up' [B, Cup, h, w])."""
+    def _level(self, i, d, skip_term, temporal_term, skip, masks, state_spatial, hidden, cell, up_src, chain_in=None,
+               holds_state=False, hidden_copy=None):
+        """One level of one object: the chain convolution + the gate launch into ``hidden`` / ``cell``.  ``up_src``: the
+        hidden of the level above (None at level 0).  ``chain_in`` (levels >= 1): the chain convolution's input, written
+        here -- [B, Cup, h, w] without a spatial state, [B, Cup + Hd, h, w] = [up | h_s] with one; ``holds_state``: its upper
+        channels hold the state's hidden already (otherwise it is copied there).  ``hidden_copy``: where the gate launch
+        leaves this level's hidden a second time."""
         chain = None
         bias_in_chain = None if skip_term is not None else d["bias"]
         if i == 0:
@@ -682,21 +709,17 @@ class RSISMask(nn.Module):
                 chain = self._conv(state_spatial[0], d["hs"])
         else:
             cup = self.skip_dims_out[i - 1]
-            if state_spatial is None:
-                dst, wgt = bufs["up"], d["up"]
-            else:
-                dst, wgt = bufs["cat"], d["cat"]
-                if state_spatial[0].data_ptr() != dst[:, cup:].data_ptr() and not bufs.get("cat_holds_state"):
-                    dst[:, cup:].copy_(state_spatial[0])
+            if state_spatial is not None and not holds_state:
+                chain_in[:, cup:].copy_(state_spatial[0])
             if self.skip_mode == "mul":
-                dst[:, :cup].copy_(skip)
-                upsample_bilinear_into(up_src, dst, 0, "mul")
+                chain_in[:, :cup].copy_(skip)
+                upsample_bilinear_into(up_src, chain_in, 0, "mul")
             else:
-                upsample_bilinear_into(up_src, dst, 0, "write")
-            chain = self._conv(dst, wgt, bias_in_chain)
+                upsample_bilinear_into(up_src, chain_in, 0, "write")
+            chain = self._conv(chain_in, d["up"] if state_spatial is None else d["cat"], bias_in_chain)
         pre = [skip_term, temporal_term, chain]
         cell_prev = None if state_spatial is None else state_spatial[1]
-        clstm_gates(pre, masks, d["m"], cell_prev, hidden, cell, bufs.get("next_copy"))
+        clstm_gates(pre, masks, d["m"], cell_prev, hidden, cell, hidden_copy)
         return hidden, cell
 
     def _forward_fused(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal):
@@ -708,16 +731,12 @@ class RSISMask(nn.Module):
             f = skip_feats[i]
             B, (h, w) = f.shape[0], f.shape[-2:]
             Hd = self.skip_dims_out[i]
-            bufs = {}
-            if i > 0:
-                cup = self.skip_dims_out[i - 1]
-                if prev_state_spatial is None:
-                    bufs["up"] = f.new_empty((B, cup, h, w))
-                else:
-                    bufs["cat"] = f.new_empty((B, cup + Hd, h, w))
-            hidden, cell = f.new_empty((B, Hd, h, w)), f.new_empty((B, Hd, h, w))
             st = None if prev_state_spatial is None else prev_state_spatial[i]
-            self._level(i, d, bufs, skip_terms[i], temporal[i], f, prev_mask_list[i], st, hidden, cell, up_src)
+            chain_in = None
+            if i > 0:
+                chain_in = f.new_empty((B, self.skip_dims_out[i - 1] + (0 if st is None else Hd), h, w))
+            hidden, cell = f.new_empty((B, Hd, h, w)), f.new_empty((B, Hd, h, w))
+            self._level(i, d, skip_terms[i], temporal[i], f, prev_mask_list[i], st, hidden, cell, up_src, chain_in)
             hidden_list.append([hidden, cell])
             up_src = hidden
         h, w = up_src.shape[-2:]
@@ -726,23 +745,6 @@ class RSISMask(nn.Module):
         return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
 
     # ---- fused training form ---------------------------------------------------------------------------------------------
-    def train_slices(self):
-        """Per level the differentiable slices of ``Gates.weight`` the fused training form convolves with: ``up``, ``skip``
-        (as in ``weight_slices``), ``m`` [4*Hd, 9], ``hs``, ``ht`` and ``bias``.  One ``_WeightSlices`` node per level: a
-        caller that evaluates several objects of a frame on the same slices (``RefineTrainStep``) pays the assembly of the
-        weight's gradient once per frame."""
-        out = []
-        for i, cell in enumerate(self.clstm_list):
-            Wt, Hd, cin = cell.Gates.weight, cell.hidden_size, cell.input_size
-            # input channels in the order x (= [up | skip] under 'concat' above level 0), mask, h_s, h_t
-            cup = cin if i == 0 or self.skip_mode != "concat" else self.skip_dims_out[i - 1]
-            w_x, w_x2, w_m, w_hs, w_ht = _WeightSlices.apply(Wt, (0, cup, cin, cin + 1, cin + 1 + Hd, cin + 1 + 2 * Hd))
-            d = {"m": w_m.reshape(4 * Hd, 9), "hs": w_hs, "ht": w_ht, "bias": cell.Gates.bias, "up": None, "skip": w_x}
-            if i > 0:
-                d["up"] = w_x
-                d["skip"] = w_x2 if self.skip_mode == "concat" else w_x if self.skip_mode == "sum" else None
-            out.append(d)
-        return out
 
     def _forward_fused_train(self, skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal, slices=None,
                              skip_terms=None, temporal_terms=None, bilinear=None, head=True):
@@ -760,35 +762,29 @@ class RSISMask(nn.Module):
             bilinear = lambda x, size: F.interpolate(x, size=size, mode="bilinear", align_corners=True)
         if slices is None:
             slices = self.train_slices()
+        if skip_terms is None:
+            skip_terms = self.skip_terms(skip_feats, slices)
+        if temporal_terms is None:
+            temporal_terms = [None] * 4 if prev_hidden_temporal is None else self.temporal_terms(prev_hidden_temporal, slices)
         hidden_list, up = [], None
         for i, d in enumerate(slices):
-            bias, w_up, w_skip, w_hs = d["bias"], d["up"], d["skip"], d["hs"]
             f = skip_feats[i]
             st = None if prev_state_spatial is None else prev_state_spatial[i]
-            if skip_terms is not None:
-                skip_term = skip_terms[i]
-            else:
-                skip_term = None if w_skip is None else self._conv(f, w_skip, bias)
-            if temporal_terms is not None:
-                temporal_term = temporal_terms[i]
-            else:
-                temporal_term = None if prev_hidden_temporal is None else self._conv(prev_hidden_temporal[i], d["ht"])
-            chain_bias = None if skip_term is not None else bias
+            chain_bias = None if skip_terms[i] is not None else d["bias"]
             chain = None
             if i == 0:
                 if st is not None:
-                    chain = self._conv(st[0], w_hs)
+                    chain = self._conv(st[0], d["hs"])
             else:
                 x = bilinear(up, tuple(f.shape[-2:]))
                 if self.skip_mode == "mul":
                     x = f * x
                 if st is None:
-                    chain = self._conv(x, w_up, chain_bias)
+                    chain = self._conv(x, d["up"], chain_bias)
                 else:
-                    if "cat" not in d:
-                        d["cat"] = torch.cat([w_up, w_hs], 1)
-                    chain = self._conv(torch.cat([x, st[0]], 1), d["cat"], chain_bias)
-            hidden, c = clstm_gates_fn([skip_term, temporal_term, chain], prev_mask_list[i], d["m"], None if st is None else st[1])
+                    chain = self._conv(torch.cat([x, st[0]], 1), _chain_weight(d), chain_bias)
+            hidden, c = clstm_gates_fn([skip_terms[i], temporal_terms[i], chain], prev_mask_list[i], d["m"],
+                                       None if st is None else st[1])
             hidden_list.append([hidden, c])
             up = hidden
         if not head:
@@ -814,6 +810,26 @@ class RefineState:
 
     def __getitem__(self, t):
         return self.thid[t]
+
+
+def _stock_objects(decode, feats, pyr, prev_thid, n_obj: int, only_temporal: bool):
+    """The object loop of the evaluator (evaluator.py:183-200) and of the trainer (trainer.py:245-273), op for op: object t is
+    decoded on the spatial state of object t - 1 (on none under ``only_temporal``, once there are temporal hiddens) and on its
+    own temporal hiddens of the last frame.  ``decode``: the decoder entry to call; ``pyr``: the four mask levels of all objects
+    ([n_obj, B, 3, h_l, w_l], coarsest first).  -> (``out_mask`` per object, ``thid``)."""
+    assert prev_thid is None or len(prev_thid) == n_obj, (len(prev_thid), n_obj)
+    hidden_spatial, thid, out_masks = None, [], []
+    for t in range(n_obj):
+        hidden_temporal = None
+        if prev_thid is not None:
+            hidden_temporal = prev_thid[t]
+            if only_temporal:
+                hidden_spatial = None
+        out_mask, hidden = decode(feats, [p[t] for p in pyr], hidden_spatial, hidden_temporal)
+        hidden_spatial = hidden
+        thid.append([hc[0] for hc in hidden])
+        out_masks.append(out_mask)
+    return out_masks, thid
 
 
 class RefineStep:
@@ -850,32 +866,15 @@ class RefineStep:
 
     # ---- evaluator.py:179-212 in torch -----------------------------------------------------------------------------------
     def _stock(self, feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W):
-        dec = self.decoder
         prev_thid = state.thid
-        hidden_spatial, thid, logits = None, [], []
-        pool = lambda x: F.max_pool2d(x, (2, 2), ceil_mode=True)
-        for t in range(n_obj):
-            hidden_temporal = None
-            if prev_thid is not None:
-                hidden_temporal = prev_thid[t]
-                if self.only_temporal:
-                    hidden_spatial = None
-            m = torch.stack([prev_mask[:, t].reshape(B, H, W), y_mask[:, t].reshape(B, H, W),
-                             init_pred[:, t].reshape(B, H, W)], 1).to(feats[0].dtype)
-            m = pool(m)
-            pyr = []
-            for _ in range(len(feats)):
-                m = pool(m)
-                pyr.append(m)
-            out_mask, hidden = dec.forward_stock(feats, pyr[::-1], hidden_spatial, hidden_temporal)
-            hidden_spatial = hidden
-            thid.append([hc[0] for hc in hidden])
-            up = F.interpolate(out_mask, size=(H, W), mode="bilinear", align_corners=True)
+        pyr = mask_pyramid_torch(*[m.to(feats[0].dtype) for m in (prev_mask, y_mask, init_pred)], n_obj, H, W)
+        out_masks, thid = _stock_objects(self.decoder.forward_stock, feats, pyr, prev_thid, n_obj, self.only_temporal)
+        logits =[F.interpolate(o, size=(H, W), mode="bilinear", align_corners=True) for o in out_masks]
+        for t, up in enumerate(logits):
             for b in range(B):
                 # (:202-205 video by video, as the reference evaluates it; the gate stays on the device)
                 mask_hist_new[b, t:t + 1] = torch.where(valid[b, t] != 0, torch.sigmoid(up[b]).to(mask_hist_new.dtype),
                                                         mask_hist_new[b, t:t + 1])
-            logits.append(up)
         probs = torch.sigmoid(torch.cat(logits, 1))                             # [B, n_obj, H, W]
         outs = probs.new_zeros((B, O, H * W))
         outs[:, :n_obj] = probs.view(B, n_obj, H * W)
@@ -889,9 +888,8 @@ class RefineStep:
         b = self._bufs.get(key)
         if b is not None:
             return b
+        _check_on_pyramid(feats, H, W)
         sizes = pyramid_sizes(H, W)
-        for f, s in zip(feats, sizes):
-            assert tuple(f.shape[-2:]) == s, ("refine_input_feat does not sit on the mask pyramid", f.shape, s)
         new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
         dims = dec.skip_dims_out
         h3, w3 = sizes[-1]
@@ -930,15 +928,16 @@ class RefineStep:
             up_src, cur = None, []
             for i, d in enumerate(sl):
                 hidden, cell = bufs["hid"][i][t], bufs["cell"][i][t]
-                lb = {"cat_holds_state": True}
+                chain_in = next_copy = None
                 if i > 0:
-                    lb["cat"], lb["up"] = bufs["cat"][i], bufs["up"][i]
-                    # this object's hidden goes, besides its own slot, into the next object's convolution input
+                    chain_in = bufs["up"][i] if spatial is None else bufs["cat"][i]
+                    # this object's hidden goes, besides its own slot, into the next object's convolution input, which
+                    # therefore holds its spatial state already
                     if t + 1 < n_obj and not (have_t and self.only_temporal):
-                        lb["next_copy"] = bufs["cat"][i][:, dims[i - 1]:]
+                        next_copy = bufs["cat"][i][:, dims[i - 1]:]
                 tt = None if temporal is None else temporal[i][t * B:(t + 1) * B]
-                dec._level(i, d, lb, skip_terms[i], tt, feats[i], bufs["pyr"][i][t], None if spatial is None else spatial[i],
-                           hidden, cell, up_src)
+                dec._level(i, d, skip_terms[i], tt, feats[i], bufs["pyr"][i][t], None if spatial is None else spatial[i],
+                           hidden, cell, up_src, chain_in, holds_state=True, hidden_copy=next_copy)
                 cur.append((hidden, cell))
                 up_src = hidden
             spatial = cur
@@ -971,7 +970,8 @@ class RefineTrainStep:
 
     Two routes, decided once per call with the decoder's ``_route``:
 
-    * ``_stock``: the trainer's loop op for op on ``decoder.forward`` -- CPU tensors, active dropout, any dtype, and every
+    * ``_stock``: the trainer's loop op for op on ``decoder.forward`` (``_stock_objects``; the nested pools of the masks are
+      taken for all objects at once, which selects the same values) -- CPU tensors, active dropout, any dtype, and every
       decoder that cannot train on its fused form (``fused_train`` off, 1x1 kernels, ...).
     * ``_fused`` (``decoder.fused_train = True``, HIP fp32 tensors): one ``mask_pyramid_fn`` for all objects, the skip terms
       once per frame, one batched temporal convolution per level for all objects, per object the chain convolutions,
@@ -1008,28 +1008,9 @@ class RefineTrainStep:
 
     # ---- trainer.py:245-287, 302-304 in torch ---------------------------------------------------------------------------
     def _stock(self, feats, prev_mask, ref_mask, init_pred, prev_thid, n_obj, B, O, H, W):
-        dec = self.decoder
-        dtype = feats[0].dtype
-        hidden_spatial, thid, out_masks = None, [], []
-        pool = lambda x: F.max_pool2d(x, (2, 2), ceil_mode=True)
-        for t in range(n_obj):
-            hidden_temporal = None
-            if prev_thid is not None:
-                assert len(prev_thid) == n_obj, (len(prev_thid), n_obj)
-                hidden_temporal = prev_thid[t]
-                if self.only_temporal:
-                    hidden_spatial = None
-            m = torch.cat([prev_mask[:, t].reshape(B, 1, H * W).to(dtype), ref_mask[:, t].reshape(B, 1, H * W).to(dtype),
-                           init_pred[:, t].reshape(B, 1, H * W).to(dtype)], 2).view(B, 3, H, W)
-            m = pool(m)
-            mask_lstm = []
-            for _ in range(len(feats)):
-                m = pool(m)
-                mask_lstm.append(m)
-            out_mask, hidden = dec(feats, mask_lstm[::-1], hidden_spatial, hidden_temporal)
-            thid.append([hc[0] for hc in hidden])
-            hidden_spatial = hidden
-            out_masks.append(F.interpolate(out_mask, (H, W)).view(B, -1))
+        pyr = mask_pyramid_torch(*[m.to(feats[0].dtype) for m in (prev_mask, ref_mask, init_pred)], n_obj, H, W)
+        out_masks, thid = _stock_objects(self.decoder, feats, pyr, prev_thid, n_obj, self.only_temporal)
+        out_masks = [F.interpolate(o, (H, W)).view(B, -1) for o in out_masks]
         probs = torch.sigmoid(torch.cat(out_masks, 1).view(B, n_obj, -1))
         outs_pad = probs.new_zeros((B, O, H * W))
         outs_pad[:, :n_obj] = probs
@@ -1038,19 +1019,18 @@ class RefineTrainStep:
     # ---- the fused step --------------------------------------------------------------------------------------------------
     def _fused(self, feats, prev_mask, ref_mask, init_pred, prev_thid, n_obj, B, O, H, W):
         dec, k = self.decoder, self.kernels
-        for f, s in zip(feats, pyramid_sizes(H, W)):
-            assert tuple(f.shape[-2:]) == s, ("refine_input_feat does not sit on the mask pyramid", f.shape, s)
-        pyramid = mask_pyramid_fn if k["pyramid"] else mask_pyramid_torch
+        _check_on_pyramid(feats, H, W)
+        pyramid =mask_pyramid_fn if k["pyramid"] else mask_pyramid_torch
         bilinear = upsample_bilinear_fn if k["upsample"] else upsample_bilinear_torch
         finish = refine_train_finish_fn if k["finish"] else refine_train_finish_torch
         pyr = pyramid(prev_mask, ref_mask, init_pred, n_obj, H, W)
         sl = dec.train_slices()
-        skip_terms = [None if d["skip"] is None else dec._conv(f, d["skip"], d["bias"]) for d, f in zip(sl, feats)]
+        skip_terms = dec.skip_terms(feats, sl)
         temporal = None
         if prev_thid is not None:
             assert len(prev_thid) == n_obj, (len(prev_thid), n_obj)
             # one convolution per level over the hiddens of every object, stacked along the batch
-            temporal = [dec._conv(torch.cat([prev_thid[t][i] for t in range(n_obj)], 0), d["ht"]) for i, d in enumerate(sl)]
+            temporal = dec.temporal_terms([torch.cat([prev_thid[t][i] for t in range(n_obj)], 0) for i in range(4)], sl)
         hidden_spatial, thid, tops = None, [], []
         for t in range(n_obj):
             tt = None
