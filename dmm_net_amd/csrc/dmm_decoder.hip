@@ -2,7 +2,8 @@
 // Reference: dmm/modules/base.py:115-188 (RSISMask.forward), dmm/modules/clstm.py:80-131 (ConvLSTMCellMask.forward),
 // dmm/modules/evaluator.py:179-212 (the per-object loop of inference_timestep).
 //
-// Four streaming / pointwise kernels, fp32, plain C++: the mask pyramid (nested ceil-mode 2x2 max pools as clipped
+// Four streaming / pointwise kernels, plain C++ (fp32 arithmetic; the cell, the upsample and the finish are templates over
+// the storage type of the activations, fp32 or bf16: include/dmm_match.h (12i)-(12k)): the mask pyramid (nested ceil-mode 2x2 max pools as clipped
 // 2^k windows, all levels and objects in one pass over the image-size planes), the fused LSTM cell (the three
 // evaluations of a level share one pre-activation; each mask plane's share is a 36-weight stencil per hidden channel),
 // the align-corners bilinear upsample written into a channel range of the next level's convolution input, and the
@@ -82,18 +83,32 @@ __global__ __launch_bounds__(256) void mask_pyramid_kernel(
     }
 }
 
-// ---- (12b) fused LSTM cell -----------------------------------------------------------------------------------------
+// ---- storage of the activations (the convolutions' inputs and outputs): fp32, or bf16 for (12i)-(12k) -----------------------
+// A value is widened on load (exact) and rounded ONCE, to nearest even, at the store (torch's rule: a NaN becomes 0x7FC0), so
+// a bf16 instantiation gives its fp32 twin's result on the widened inputs, rounded.  A lane owns one position: 2-byte loads
+// and stores, coalesced over the wave like the dwords of the fp32 form, and right for every alignment a bf16 tensor can have.
+__device__ __forceinline__ float act_load(const float *p) { return *p; }
+__device__ __forceinline__ float act_load(const bf16_t *p) { return MaskIO<bf16_t>::load1(p); }
+__device__ __forceinline__ void act_store(float *p, float v) { *p = v; }
+__device__ __forceinline__ void act_store(bf16_t *p, float v) {
+    const uint32_t u = __float_as_uint(v);
+    p->v = v != v ? (uint16_t)0x7FC0u : (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+
+// ---- (12b) / (12i) fused LSTM cell ---------------------------------------------------------------------------------
 // A lane owns one position (b, y, x) and CH consecutive hidden channels: the 27 stencil inputs (3 planes x 3 x 3,
 // zero padded) are loaded once, the 36 weights of a channel are wave-uniform, every gate / state access is coalesced
-// over the positions.
+// over the positions.  T: the storage of the pre-activation's addends and of the hidden (both copies); the mask planes, the
+// stencil and the cell state are fp32 in either form.
 constexpr int kGateCh = 4;
 
 __device__ __forceinline__ float sigmoid_f32(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+template <typename T>
 __global__ __launch_bounds__(256) void clstm_gates_kernel(
-    const float *__restrict__ pre0, const float *__restrict__ pre1, const float *__restrict__ pre2, int64_t sb0, int64_t sb1,
+    const T *__restrict__ pre0, const T *__restrict__ pre1, const T *__restrict__ pre2, int64_t sb0, int64_t sb1,
     int64_t sb2, const float *__restrict__ masks, int64_t sb_m, const float *__restrict__ wm, const float *__restrict__ c_prev,
-    int B, int Hd, int h, int w, float *__restrict__ hidden, float *__restrict__ cell, float *__restrict__ hidden2,
+    int B, int Hd, int h, int w, T *__restrict__ hidden, float *__restrict__ cell, T *__restrict__ hidden2,
     int64_t sb_h2) {
     const int hw = h * w;
     const int pos = blockIdx.x * 256 + threadIdx.x;
@@ -117,9 +132,9 @@ __global__ __launch_bounds__(256) void clstm_gates_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int64_t off = (int64_t)(q * Hd + ch) * hw + p;
-            float v = pre0[(int64_t)b * sb0 + off];
-            if (pre1) v = v + pre1[(int64_t)b * sb1 + off];
-            if (pre2) v = v + pre2[(int64_t)b * sb2 + off];
+            float v = act_load(pre0 + (int64_t)b * sb0 + off);
+            if (pre1) v = v + act_load(pre1 + (int64_t)b * sb1 + off);
+            if (pre2) v = v + act_load(pre2 + (int64_t)b * sb2 + off);
             g[q] = v;
         }
         const int64_t so = ((int64_t)b * Hd + ch) * hw + p;
@@ -143,9 +158,9 @@ __global__ __launch_bounds__(256) void clstm_gates_kernel(
         // the reference's order: prev_mask (plane 0), init_pred (plane 2), y_mask (plane 1); (a + b + c) / 3
         const float hv = ((hk[0] + hk[2]) + hk[1]) / 3.0f;
         const float cv = ((ck[0] + ck[2]) + ck[1]) / 3.0f;
-        hidden[so] = hv;
+        act_store(hidden + so, hv);
         cell[so] = cv;
-        if (hidden2) hidden2[(int64_t)b * sb_h2 + (int64_t)ch * hw + p] = hv;
+        if (hidden2) act_store(hidden2 + (int64_t)b * sb_h2 + (int64_t)ch * hw + p, hv);
     }
 }
 
@@ -343,7 +358,7 @@ __global__ __launch_bounds__(256) void clstm_gates_bwd_fold_kernel(const float *
     }
 }
 
-// ---- (12c) / (12d) align-corners bilinear -----------------------------------------------------------------------------
+// ---- (12c) / (12d), (12j) / (12k) align-corners bilinear ---------------------------------------------------------------
 // ATen's upsample_bilinear2d with align_corners = True: scale = (in - 1) / (out - 1) (0 for out == 1), src = scale * dst,
 // lower index by truncation, lambda1 = src - lower, lambda0 = 1 - lambda1.
 struct Lerp { int i0, step; float l0, l1; };
@@ -357,15 +372,17 @@ __device__ __forceinline__ Lerp lerp_of(int dst, float scale, int in) {
     r.l0 = 1.0f - r.l1;
     return r;
 }
-__device__ __forceinline__ float bilerp(const float *__restrict__ p, int w, const Lerp &ly, const Lerp &lx) {
-    const float *r0 = p + (int64_t)ly.i0 * w + lx.i0, *r1 = r0 + (int64_t)ly.step * w;
-    return ly.l0 * (lx.l0 * r0[0] + lx.l1 * r0[lx.step]) + ly.l1 * (lx.l0 * r1[0] + lx.l1 * r1[lx.step]);
+template <typename T>
+__device__ __forceinline__ float bilerp(const T *__restrict__ p, int w, const Lerp &ly, const Lerp &lx) {
+    const T *r0 = p + (int64_t)ly.i0 * w + lx.i0, *r1 = r0 + (int64_t)ly.step * w;
+    return ly.l0 * (lx.l0 * act_load(r0) + lx.l1 * act_load(r0 + lx.step)) +
+           ly.l1 * (lx.l0 * act_load(r1) + lx.l1 * act_load(r1 + lx.step));
 }
 __host__ __device__ __forceinline__ float ac_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.0f; }
 
-template <int MODE>   // 0 write, 1 add, 2 mul
-__global__ __launch_bounds__(256) void upsample_into_kernel(const float *__restrict__ src, int64_t sb_src, int C, int h, int w,
-                                                            float *__restrict__ dst, int64_t sb_dst, int c0, int H, int W,
+template <int MODE, typename T>   // 0 write, 1 add, 2 mul; T: the storage of src and dst
+__global__ __launch_bounds__(256) void upsample_into_kernel(const T *__restrict__ src, int64_t sb_src, int C, int h, int w,
+                                                            T *__restrict__ dst, int64_t sb_dst, int c0, int H, int W,
                                                             float sy, float sx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -375,14 +392,16 @@ __global__ __launch_bounds__(256) void upsample_into_kernel(const float *__restr
     r /= H;
     const int c = (int)(r % C), b = (int)(r / C);
     const float v = bilerp(src + (int64_t)b * sb_src + (int64_t)c * h * w, w, lerp_of(Y, sy, h), lerp_of(X, sx, w));
-    float *d = dst + (int64_t)b * sb_dst + ((int64_t)(c0 + c) * H + Y) * W + X;
-    if (MODE == 0) *d = v;
-    else if (MODE == 1) *d = *d + v;
-    else *d = *d * v;
+    T *d = dst + (int64_t)b * sb_dst + ((int64_t)(c0 + c) * H + Y) * W + X;
+    if (MODE == 0) act_store(d, v);
+    else if (MODE == 1) act_store(d, act_load(d) + v);
+    else act_store(d, act_load(d) * v);
 }
 
-// One lane = 4 consecutive pixels of a row of outs[b, t] (rows are 4-byte aligned: float4u stores).
-__global__ __launch_bounds__(256) void refine_finish_kernel(const float *__restrict__ logits, int64_t sb_l, int64_t so_l, int h,
+// One lane = 4 consecutive pixels of a row of outs[b, t] (rows are 4-byte aligned: float4u stores).  T: the storage of the
+// logits, which are gathered element by element; outs and hist are fp32 in either form.
+template <typename T>
+__global__ __launch_bounds__(256) void refine_finish_kernel(const T *__restrict__ logits, int64_t sb_l, int64_t so_l, int h,
                                                             int w, const int *__restrict__ valid, int B, int O, int n_obj, int H,
                                                             int W, int Wq, float sy, float sx, float *__restrict__ outs,
                                                             float *__restrict__ hist, int64_t n) {
@@ -397,7 +416,7 @@ __global__ __launch_bounds__(256) void refine_finish_kernel(const float *__restr
     float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     const bool live = t < n_obj;
     if (live) {
-        const float *p = logits + (int64_t)b * sb_l + (int64_t)t * so_l;
+        const T *p = logits + (int64_t)b * sb_l + (int64_t)t * so_l;
         const Lerp ly = lerp_of(Y, sy, h);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -618,6 +637,61 @@ __global__ __launch_bounds__(256) void refine_train_finish_bwd_kernel(const floa
     d_logits[(int64_t)b * sb_d + (int64_t)t * so_d + (int64_t)y * w + x] = (p * (1.0f - p)) * acc;
 }
 
+// ---- the entries of the three templated kernels: one check and one launch for both storage types --------------------------
+template <typename T>
+static int clstm_gates_entry(const T *pre0, const T *pre1, const T *pre2, int64_t sb0, int64_t sb1, int64_t sb2, const float *masks,
+                             int64_t sb_masks, const float *w_mask, const float *cell_prev, int B, int hidden_size, int h, int w,
+                             T *hidden, float *cell, T *hidden_copy, int64_t sb_copy, dmm_stream_t stream) {
+    if (B < 0 || hidden_size <= 0 || h <= 0 || w <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0) return DMM_OK;
+    if (!pre0 || !masks || !w_mask || !hidden || !cell) return DMM_ERR_BAD_ARG;
+    const int64_t hw = (int64_t)h * w;
+    if (sb0 < 0 || sb1 < 0 || sb2 < 0 || sb_masks < 3 * hw || (hidden_copy && sb_copy < (int64_t)hidden_size * hw))
+        return DMM_ERR_BAD_ARG;
+    const int64_t blocks = ((int64_t)B * hw + 255) / 256, groups = (hidden_size + kGateCh - 1) / kGateCh;
+    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(clstm_gates_kernel<T>, dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0, (hipStream_t)stream, pre0,
+                       pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, B, hidden_size, h, w, hidden, cell,
+                       hidden_copy, sb_copy);
+    return check_launch();
+}
+
+template <typename T>
+static int upsample_into_entry(const T *src, int64_t sb_src, int B, int C, int h, int w, T *dst, int64_t sb_dst, int C_dst, int c0,
+                               int H, int W, int mode, dmm_stream_t stream) {
+    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C_dst <= 0) return DMM_ERR_BAD_ARG;
+    if (c0 < 0 || c0 + C > C_dst || mode < 0 || mode > 2) return DMM_ERR_BAD_ARG;   // the channel range lies inside dst
+    if (B == 0) return DMM_OK;
+    if (!src || !dst) return DMM_ERR_BAD_ARG;
+    if (sb_src < (int64_t)C * h * w || sb_dst < (int64_t)C_dst * H * W) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * C * H * W, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    const float sy = ac_scale(h, H), sx = ac_scale(w, W);
+#define DMM_UP(MODE_)                                                                                                     \
+    hipLaunchKernelGGL((upsample_into_kernel<MODE_, T>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src,    \
+                       sb_src, C, h, w, dst, sb_dst, c0, H, W, sy, sx, n)
+    if (mode == 0) DMM_UP(0);
+    else if (mode == 1) DMM_UP(1);
+    else DMM_UP(2);
+#undef DMM_UP
+    return check_launch();
+}
+
+template <typename T>
+static int refine_finish_entry(const T *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid, int B, int O,
+                               int n_obj, int H, int W, float *outs, float *mask_hist, dmm_stream_t stream) {
+    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || O == 0) return DMM_OK;
+    if (!outs || (n_obj > 0 && !logits) || (mask_hist && !valid)) return DMM_ERR_BAD_ARG;
+    if (sb_logits < 0 || so_logits < 0) return DMM_ERR_BAD_ARG;
+    const int Wq = (W + 3) / 4;
+    const int64_t n = (int64_t)B * O * H * Wq, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(refine_finish_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, sb_logits,
+                       so_logits, h, w, valid, B, O, n_obj, H, W, Wq, ac_scale(h, H), ac_scale(w, W), outs, mask_hist, n);
+    return check_launch();
+}
+
 }  // namespace dmm
 
 extern "C" int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
@@ -641,18 +715,17 @@ extern "C" int dmm_clstm_gates_f32(const float *pre0, const float *pre1, const f
                                    const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
                                    int hidden_size, int h, int w, float *hidden, float *cell, float *hidden_copy,
                                    int64_t sb_copy, dmm_stream_t stream) {
-    if (B < 0 || hidden_size <= 0 || h <= 0 || w <= 0) return DMM_ERR_BAD_ARG;
-    if (B == 0) return DMM_OK;
-    if (!pre0 || !masks || !w_mask || !hidden || !cell) return DMM_ERR_BAD_ARG;
-    const int64_t hw = (int64_t)h * w;
-    if (sb0 < 0 || sb1 < 0 || sb2 < 0 || sb_masks < 3 * hw || (hidden_copy && sb_copy < (int64_t)hidden_size * hw))
-        return DMM_ERR_BAD_ARG;
-    const int64_t blocks = ((int64_t)B * hw + 255) / 256, groups = (hidden_size + dmm::kGateCh - 1) / dmm::kGateCh;
-    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return DMM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dmm::clstm_gates_kernel, dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0, (hipStream_t)stream, pre0,
-                       pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, B, hidden_size, h, w, hidden, cell,
-                       hidden_copy, sb_copy);
-    return dmm::check_launch();
+    return dmm::clstm_gates_entry<float>(pre0, pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, B, hidden_size, h, w,
+                                         hidden, cell, hidden_copy, sb_copy, stream);
+}
+
+extern "C" int dmm_clstm_gates_bf16(const void *pre0, const void *pre1, const void *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                    const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                    int hidden_size, int h, int w, void *hidden, float *cell, void *hidden_copy, int64_t sb_copy,
+                                    dmm_stream_t stream) {
+    typedef dmm::bf16_t T;
+    return dmm::clstm_gates_entry<T>((const T *)pre0, (const T *)pre1, (const T *)pre2, sb0, sb1, sb2, masks, sb_masks, w_mask,
+                                     cell_prev, B, hidden_size, h, w, (T *)hidden, cell, (T *)hidden_copy, sb_copy, stream);
 }
 
 // ws_m [groups][B][27][h * w] then ws_w [position blocks][36 * hidden_size]; 0 for sizes the entry refuses or has no work for
@@ -700,37 +773,26 @@ extern "C" int dmm_clstm_gates_bwd_f32(const float *pre0, const float *pre1, con
 
 extern "C" int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int B, int C, int h, int w, float *dst,
                                               int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream) {
-    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C_dst <= 0) return DMM_ERR_BAD_ARG;
-    if (c0 < 0 || c0 + C > C_dst || mode < 0 || mode > 2) return DMM_ERR_BAD_ARG;   // the channel range lies inside dst
-    if (B == 0) return DMM_OK;
-    if (!src || !dst) return DMM_ERR_BAD_ARG;
-    if (sb_src < (int64_t)C * h * w || sb_dst < (int64_t)C_dst * H * W) return DMM_ERR_BAD_ARG;
-    const int64_t n = (int64_t)B * C * H * W, blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
-    const float sy = dmm::ac_scale(h, H), sx = dmm::ac_scale(w, W);
-#define DMM_UP(MODE_)                                                                                                     \
-    hipLaunchKernelGGL((dmm::upsample_into_kernel<MODE_>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, src,  \
-                       sb_src, C, h, w, dst, sb_dst, c0, H, W, sy, sx, n)
-    if (mode == 0) DMM_UP(0);
-    else if (mode == 1) DMM_UP(1);
-    else DMM_UP(2);
-#undef DMM_UP
-    return dmm::check_launch();
+    return dmm::upsample_into_entry<float>(src, sb_src, B, C, h, w, dst, sb_dst, C_dst, c0, H, W, mode, stream);
+}
+
+extern "C" int dmm_upsample_bilinear_into_bf16(const void *src, int64_t sb_src, int B, int C, int h, int w, void *dst,
+                                               int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream) {
+    typedef dmm::bf16_t T;
+    return dmm::upsample_into_entry<T>((const T *)src, sb_src, B, C, h, w, (T *)dst, sb_dst, C_dst, c0, H, W, mode, stream);
 }
 
 extern "C" int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
                                      int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist,
                                      dmm_stream_t stream) {
-    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || O == 0) return DMM_OK;
-    if (!outs || (n_obj > 0 && !logits) || (mask_hist && !valid)) return DMM_ERR_BAD_ARG;
-    if (sb_logits < 0 || so_logits < 0) return DMM_ERR_BAD_ARG;
-    const int Wq = (W + 3) / 4;
-    const int64_t n = (int64_t)B * O * H * Wq, blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dmm::refine_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits, sb_logits,
-                       so_logits, h, w, valid, B, O, n_obj, H, W, Wq, dmm::ac_scale(h, H), dmm::ac_scale(w, W), outs, mask_hist, n);
-    return dmm::check_launch();
+    return dmm::refine_finish_entry<float>(logits, sb_logits, so_logits, h, w, valid, B, O, n_obj, H, W, outs, mask_hist, stream);
+}
+
+extern "C" int dmm_refine_finish_bf16(const void *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
+                                      int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist,
+                                      dmm_stream_t stream) {
+    return dmm::refine_finish_entry<dmm::bf16_t>((const dmm::bf16_t *)logits, sb_logits, so_logits, h, w, valid, B, O, n_obj, H, W,
+                                                 outs, mask_hist, stream);
 }
 
 extern "C" int dmm_mask_pyramid_bwd_f32(const float *prev_mask, const float *init_pred, int64_t sb_prev, int64_t so_prev,

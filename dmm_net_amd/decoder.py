@@ -37,6 +37,13 @@ Three execution forms behind the one ``forward``:
   objects); only ``W_hs * h_s`` and the share of the upsampled hidden of the level above are computed per object.  The
   convolutions stay on the library (``F.conv2d`` -> MIOpen); what lies between them is ``csrc/dmm_decoder.hip``.  A
   reordering of fp32 sums, not an approximation.
+
+  ``decoder.compute_dtype = torch.bfloat16`` (opt-in; the default is fp32) runs this form on bf16 ACTIVATIONS, behind an
+  encoder that hands out bf16 maps: the skip maps, the hiddens and every convolution's input and output are bf16, the library
+  convolutions run in bf16 on weights cast once (``weight_slices``), and the kernels between them are the 16-bit entries
+  (include/dmm_match.h (12i)-(12k)): fp32 arithmetic on widened values, one rounding at each 16-bit store.  The mask
+  pyramid, the stencil weights, the cells, ``outs`` and the mask history stay fp32; the parameters stay fp32 masters.
+  Calls that require a gradient ignore the setting: the training forms are fp32.
 """
 from __future__ import annotations
 
@@ -51,6 +58,14 @@ from . import _lib
 
 _SKIP_MODES = ("concat", "sum", "mul", "none")
 _UP_MODE = {"write": 0, "add": 1, "mul": 2}
+_ACT_SUFFIX = {torch.float32: "f32", torch.bfloat16: "bf16"}     # the storage types of the activations (dmm_match.h (12i)-(12k))
+
+
+def _act_entry(stem: str, dtype, what: str):
+    """The entry ``stem`` + the suffix of the activations' dtype; anything but fp32 / bf16 raises."""
+    if dtype not in _ACT_SUFFIX:
+        raise _lib.DmmError(f"{stem}*: {what} must be float32 or bfloat16, not {dtype}")
+    return stem + _ACT_SUFFIX[dtype]
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -122,15 +137,18 @@ def _dense_batch(t: torch.Tensor):
     return t, _batch_stride(t)
 
 
-def _addends(pre: Sequence[Optional[torch.Tensor]], shape=None):
-    """The up to three addends of the cell's pre-activation (None entries skipped), each fp32 of ``shape`` = [B, 4*Hd, h, w]
-    (default: the first one's) -> (pointers, batch strides, the tensors behind the pointers), the first two padded to three."""
+def _addends(pre: Sequence[Optional[torch.Tensor]], shape=None, dtype=torch.float32):
+    """The up to three addends of the cell's pre-activation (None entries skipped), each of ``dtype`` and of ``shape`` =
+    [B, 4*Hd, h, w] (default: the first one's) -> (pointers, batch strides, the tensors behind the pointers), the first two
+    padded to three."""
     pre = [p for p in pre if p is not None]
     assert 1 <= len(pre) <= 3
     shape = tuple(pre[0].shape if shape is None else shape)
     ptrs, strides, keep = [], [], []
     for p in pre:
-        assert tuple(p.shape) == shape and p.dtype == torch.float32, (p.shape, shape)
+        if p.dtype != dtype:
+            raise _lib.DmmError(f"clstm_gates: an addend of the pre-activation is {p.dtype}, the hidden it feeds {dtype}")
+        assert tuple(p.shape) == shape, (p.shape, shape)
         p, sb = _dense_batch(p)
         keep.append(p)
         ptrs.append(p.data_ptr())
@@ -141,12 +159,19 @@ def _addends(pre: Sequence[Optional[torch.Tensor]], shape=None):
 
 
 def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev, hidden, cell, hidden_copy=None):
-    """``dmm_clstm_gates_f32``: pre = up to three addends [B, 4*Hd, h, w]; masks [B, 3, h, w]; w_mask [4*Hd, 9]; cell_prev
-    [B, Hd, h, w] or None; writes ``hidden`` / ``cell`` (dense) and, when given, ``hidden_copy`` (a channel slice of the
-    next evaluation's convolution input)."""
+    """``dmm_clstm_gates_f32`` / ``_bf16`` by ``hidden``'s dtype: pre = up to three addends [B, 4*Hd, h, w]; masks [B, 3, h, w];
+    w_mask [4*Hd, 9]; cell_prev [B, Hd, h, w] or None; writes ``hidden`` / ``cell`` (dense) and, when given, ``hidden_copy`` (a
+    channel slice of the next evaluation's convolution input).  The addends and ``hidden_copy`` have ``hidden``'s dtype;
+    masks, w_mask, cell_prev and cell are fp32 in either form."""
     _need_device(masks)
     B, Hd, h, w = hidden.shape
-    ptrs, strides, keep = _addends(pre, (B, 4 * Hd, h, w))
+    entry = _act_entry("dmm_clstm_gates_", hidden.dtype, "hidden")
+    ptrs, strides, keep = _addends(pre, (B, 4 * Hd, h, w), hidden.dtype)
+    for name, t in (("masks", masks), ("w_mask", w_mask), ("cell_prev", cell_prev), ("cell", cell)):
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.DmmError(f"clstm_gates: {name} is {t.dtype}; the mask planes, the stencil and the cell state are float32")
+    if hidden_copy is not None and hidden_copy.dtype != hidden.dtype:
+        raise _lib.DmmError(f"clstm_gates: hidden_copy is {hidden_copy.dtype}, hidden {hidden.dtype}")
     masks, sbm = _dense_batch(masks)
     assert tuple(masks.shape) == (B, 3, h, w) and w_mask.is_contiguous() and tuple(w_mask.shape) == (4 * Hd, 9)
     assert hidden.is_contiguous() and cell.is_contiguous() and tuple(cell.shape) == (B, Hd, h, w)
@@ -157,7 +182,7 @@ def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev,
     if hidden_copy is not None:
         assert tuple(hidden_copy.shape) == (B, Hd, h, w) and _dense_samples(hidden_copy)
         sbc = _batch_stride(hidden_copy)
-    _lib.call("dmm_clstm_gates_f32", masks.device, *ptrs, *strides, _ptr(masks), sbm, _ptr(w_mask), _ptr(cell_prev),
+    _lib.call(entry, masks.device, *ptrs, *strides, _ptr(masks), sbm, _ptr(w_mask), _ptr(cell_prev),
               B, Hd, h, w, _ptr(hidden), _ptr(cell), _ptr(hidden_copy), sbc, _stream(masks))
     return hidden, cell
 
@@ -305,22 +330,28 @@ class _ConvStacked(torch.autograd.Function):
 
 
 def upsample_bilinear_into(src, dst, c0: int = 0, mode: str = "write"):
-    """``dmm_upsample_bilinear_into_f32``: UpsamplingBilinear2d(src [B,C,h,w]) to dst's size, combined into
-    dst[:, c0:c0+C] ([B, C', H, W] dense) by ``mode`` ('write' | 'add' | 'mul')."""
+    """``dmm_upsample_bilinear_into_f32`` / ``_bf16`` by the dtype of ``src`` and ``dst`` (the same one):
+    UpsamplingBilinear2d(src [B,C,h,w]) to dst's size, combined into dst[:, c0:c0+C] ([B, C', H, W] dense) by ``mode``
+    ('write' | 'add' | 'mul')."""
     _need_device(src)
+    entry = _act_entry("dmm_upsample_bilinear_into_", src.dtype, "src")
+    if dst.dtype != src.dtype:
+        raise _lib.DmmError(f"upsample_bilinear_into: src is {src.dtype}, dst {dst.dtype}")
     src, sbs = _dense_batch(src)
     B, C, h, w = src.shape
     Bd, Cd, H, W = dst.shape
-    assert Bd == B and dst.dtype == src.dtype == torch.float32 and _dense_samples(dst), (src.shape, dst.shape, dst.stride())
-    _lib.call("dmm_upsample_bilinear_into_f32", src.device, _ptr(src), sbs, B, C, h, w, _ptr(dst), _batch_stride(dst), Cd, int(c0),
+    assert Bd == B and _dense_samples(dst), (src.shape, dst.shape, dst.stride())
+    _lib.call(entry, src.device, _ptr(src), sbs, B, C, h, w, _ptr(dst), _batch_stride(dst), Cd, int(c0),
               H, W, _UP_MODE[mode], _stream(src))
     return dst
 
 
 def refine_finish(logits, valid_i32, outs, mask_hist, n_obj: int):
-    """``dmm_refine_finish_f32``: logits [B, n_obj, h, w] (any batch / object strides, dense planes) -> outs [B,O,H,W]
-    (sigmoid of the upsampled logits, zero rows beyond n_obj) and mask_hist[b, t] where valid_i32[b, t]."""
+    """``dmm_refine_finish_f32`` / ``_bf16`` by the logits' dtype: logits [B, n_obj, h, w] (any batch / object strides, dense
+    planes) -> outs [B,O,H,W] fp32 (sigmoid of the upsampled logits, zero rows beyond n_obj) and mask_hist[b, t] (fp32) where
+    valid_i32[b, t]."""
     _need_device(outs)
+    entry = _act_entry("dmm_refine_finish_", logits.dtype, "logits")
     B, O, H, W = outs.shape
     assert outs.is_contiguous() and outs.dtype == torch.float32
     assert mask_hist is None or (mask_hist.is_contiguous() and tuple(mask_hist.shape) == (B, O, H, W) and
@@ -329,7 +360,7 @@ def refine_finish(logits, valid_i32, outs, mask_hist, n_obj: int):
                                  tuple(valid_i32.shape) == (B, O))
     h, w = logits.shape[-2:]
     assert logits.shape[0] == B and logits.shape[1] >= n_obj and logits.stride(3) == 1 and logits.stride(2) == w
-    _lib.call("dmm_refine_finish_f32", outs.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w, _ptr(valid_i32),
+    _lib.call(entry, outs.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w, _ptr(valid_i32),
               B, O, int(n_obj), H, W, _ptr(outs), _ptr(mask_hist), _stream(outs))
     return outs
 
@@ -570,12 +601,27 @@ class RSISMask(nn.Module):
         self.conv_out = nn.Conv2d(self.skip_dims_out[-1], 1, self.kernel_size, padding=padding)
         self.fused = True                    # False: always the stock form (A/B timing, tests)
         self.fused_train = False             # True: calls that require a gradient take the fused training form
-        self._slices = None                  # (key, per-level weight slices) of the fused form
+        self._compute_dtype = torch.float32  # the activations' dtype of the fused (no-grad) form: ``compute_dtype``
+        self._slices = None                  # (key, per-level weight slices, conv_out's pair) of the fused form
         self.conv_calls = 0                  # convolutions issued by the fused form (diagnostic, like dmm_launch_count)
+
+    @property
+    def compute_dtype(self):
+        """The dtype of the fused inference form's activations: ``torch.float32`` (default) or, opt-in, ``torch.bfloat16``
+        (module docstring).  The parameters stay fp32 either way; calls that require a gradient ignore it."""
+        return self._compute_dtype
+
+    @compute_dtype.setter
+    def compute_dtype(self, dtype):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"RSISMask.compute_dtype is torch.float32 or torch.bfloat16, not {dtype!r}")
+        self._compute_dtype = dtype
 
     # ---- dispatch ------------------------------------------------------------------------------------------------
     def _route(self, tensors: Sequence[torch.Tensor]) -> str:
-        """'fused' (no gradient), 'train' (a gradient is required and ``fused_train`` is on) or 'stock'."""
+        """'fused' (no gradient), 'train' (a gradient is required and ``fused_train`` is on) or 'stock'.  Without a gradient
+        and with ``compute_dtype = torch.bfloat16`` the fused form takes bf16 tensors beside fp32 ones (which tensor has to be
+        which: ``_check_bf16_operands``); in every other case all of them are fp32."""
         if not self.fused or self.skip_mode not in _SKIP_MODES or int(self.kernel_size) != 3 or self.prev_mask_d != 1:
             return "stock"
         if self.training and self.dropout > 0:
@@ -584,9 +630,20 @@ class RSISMask(nn.Module):
         grad = torch.is_grad_enabled() and any(t.requires_grad for t in list(tensors) + params)
         if grad and not self.fused_train:
             return "stock"
-        if not all(t.is_cuda and t.dtype == torch.float32 for t in list(tensors) + params):
+        if not all(t.is_cuda and t.dtype == torch.float32 for t in params):
+            return "stock"
+        taken = (torch.float32,) if grad or self._compute_dtype == torch.float32 else (torch.float32, torch.bfloat16)
+        if not all(t.is_cuda and t.dtype in taken for t in tensors):
             return "stock"
         return "train" if grad else "fused"
+
+    @staticmethod
+    def _check_bf16_operands(low, full):
+        """The operand set of the bf16 fused form: ``low`` (skip maps, hiddens) bf16, ``full`` (mask planes, cells) fp32."""
+        if not all(t.dtype == torch.bfloat16 for t in low) or not all(t.dtype == torch.float32 for t in full):
+            raise _lib.DmmError("RSISMask with compute_dtype = torch.bfloat16 takes bfloat16 skip maps, spatial hiddens and "
+                                "temporal hiddens and float32 mask planes and cells; got "
+                                f"{sorted({str(t.dtype) for t in low})} and {sorted({str(t.dtype) for t in full})}")
 
     def fused_ok(self, tensors: Sequence[torch.Tensor]) -> bool:
         """Does the fused inference form cover this call?  (Anything else is the stock form -- same results, torch ops --
@@ -601,6 +658,13 @@ class RSISMask(nn.Module):
             ts += list(prev_hidden_temporal)
         route = self._route(ts)
         if route == "fused":
+            if self._compute_dtype == torch.bfloat16:
+                low = list(skip_feats) + ([] if prev_hidden_temporal is None else list(prev_hidden_temporal))
+                full = list(prev_mask_list)
+                if prev_state_spatial is not None:
+                    low += [st[0] for st in prev_state_spatial]
+                    full += [st[1] for st in prev_state_spatial]
+                self._check_bf16_operands(low, full)
             return self._forward_fused(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
         if route == "train":
             return self._forward_fused_train(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
@@ -668,11 +732,26 @@ class RSISMask(nn.Module):
 
     def weight_slices(self):
         """The no-grad cut of ``_cut_slices`` (the fused form's), ``cat`` present.  Made once and kept against the
-        parameters' versions and storages."""
-        key = tuple((p.data_ptr(), p._version, p.device) for p in self.parameters())
+        parameters' versions and storages and ``compute_dtype``: with bf16 set, the same layout with the convolution weights
+        and the bias cast to bf16 (once, here); ``m``, the mask stencil the gate kernel reads, stays fp32."""
+        return self._cached_slices()[1]
+
+    def head_weights(self):
+        """``conv_out``'s (weight, bias) as the fused form applies them: the parameters, or their bf16 casts kept with
+        ``weight_slices()``."""
+        return self._cached_slices()[2]
+
+    def _cached_slices(self):
+        key = (self._compute_dtype,) + tuple((p.data_ptr(), p._version, p.device) for p in self.parameters())
         if self._slices is None or self._slices[0] != key:
-            self._slices = (key, self._cut_slices(train=False))
-        return self._slices[1]
+            sl = self._cut_slices(train=False)
+            head = (self.conv_out.weight.detach(), self.conv_out.bias.detach())
+            if self._compute_dtype != torch.float32:
+                cast = lambda t: None if t is None else t.to(self._compute_dtype)
+                sl = [{k: (v if k == "m" else cast(v)) for k, v in d.items()} for d in sl]
+                head = tuple(cast(t) for t in head)
+            self._slices = (key, sl, head)
+        return self._slices
 
     def train_slices(self):
         """The differentiable cut of ``_cut_slices`` (the fused training form's).  One ``_WeightSlices`` node per level: a
@@ -735,14 +814,14 @@ class RSISMask(nn.Module):
             chain_in = None
             if i > 0:
                 chain_in = f.new_empty((B, self.skip_dims_out[i - 1] + (0 if st is None else Hd), h, w))
-            hidden, cell = f.new_empty((B, Hd, h, w)), f.new_empty((B, Hd, h, w))
+            hidden, cell = f.new_empty((B, Hd, h, w)), f.new_empty((B, Hd, h, w), dtype=torch.float32)
             self._level(i, d, skip_terms[i], temporal[i], f, prev_mask_list[i], st, hidden, cell, up_src, chain_in)
             hidden_list.append([hidden, cell])
             up_src = hidden
         h, w = up_src.shape[-2:]
         top = up_src.new_empty((up_src.shape[0], self.skip_dims_out[-1], 2 * h, 2 * w))
         upsample_bilinear_into(up_src, top, 0, "write")
-        return self._conv(top, self.conv_out.weight, self.conv_out.bias), hidden_list
+        return self._conv(top, *self.head_weights()), hidden_list
 
     # ---- fused training form ---------------------------------------------------------------------------------------------
 
@@ -843,15 +922,20 @@ class RefineStep:
     upsample + ``conv_out`` for all objects, one finish launch.  ``valid_num_obj_max`` is read when ``state is None``
     (frame 0 of a clip) and kept in the state: afterwards no host sync, and every buffer is kept by shape, so the step can
     be captured into a graph and replayed.  ``mask_hist_new`` is then updated in place (FrameLoop hands over a tensor of
-    its own for that)."""
+    its own for that).
+
+    With ``decoder.compute_dtype = torch.bfloat16`` (and HIP tensors, no gradient) the same step runs on bf16 activations:
+    the feature maps are taken as bf16 (a bf16 encoder's pass through untouched, others are cast), the hidden buffers -- so
+    the temporal state in ``RefineState`` -- and every convolution are bf16; the pyramid, the cells, ``outs`` and
+    ``mask_hist_new`` stay fp32.  The same convolution and launch counts, buffers kept by shape and dtype."""
 
     def __init__(self, decoder: RSISMask, only_spatial: bool = False, only_temporal: bool = False):
         self.decoder, self.only_spatial, self.only_temporal = decoder, bool(only_spatial), bool(only_temporal)
         self._bufs = {}
 
     def __call__(self, features, prev_mask, y_mask, init_pred, mask_hist_new, valid, state):
-        low = (torch.float16, torch.bfloat16)                    # a bf16 encoder's maps: the decoder's arithmetic is fp32
-        feats = [f.float() if f.dtype in low else f for f in features["refine_input_feat"]]
+        low = (torch.float16, torch.bfloat16)
+        maps = list(features["refine_input_feat"])
         B, O = init_pred.shape[:2]
         H, W = init_pred.shape[-2:]
         if state is None:
@@ -859,7 +943,15 @@ class RefineStep:
             state = RefineState(max(1, int((valid.sum(0) > 0).sum())))
         n_obj = min(state.n_obj, O)
         init_pred = init_pred.float() if init_pred.dtype in low else init_pred
-        ts = feats + [prev_mask, y_mask, init_pred, mask_hist_new]
+        planes = [prev_mask, y_mask, init_pred, mask_hist_new]
+        dt = getattr(self.decoder, "compute_dtype", torch.float32)
+        if dt != torch.float32 and maps[0].is_cuda:
+            # the opt-in 16-bit form: a bf16 encoder's maps pass through untouched, others are cast; the planes stay fp32
+            feats = [f if f.dtype == dt else f.to(dt) for f in maps]
+            if self.decoder.fused_ok(feats + planes):
+                return self._fused(feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W)
+        feats = [f.float() if f.dtype in low else f for f in maps]   # a bf16 encoder's maps: the default arithmetic is fp32
+        ts = feats + planes
         if self.decoder.fused_ok(ts):
             return self._fused(feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W)
         return self._stock(feats, prev_mask, y_mask, init_pred, mask_hist_new, valid, state, n_obj, B, O, H, W)
@@ -884,22 +976,24 @@ class RefineStep:
     def _buffers(self, feats, n_obj, B, O, H, W):
         dec = self.decoder
         dev = feats[0].device
-        key = (dev, n_obj, B, O, H, W, dec.skip_mode, tuple(tuple(f.shape) for f in feats))
+        act = feats[0].dtype                                      # the activations: fp32, or the decoder's compute_dtype
+        key = (dev, act, n_obj, B, O, H, W, dec.skip_mode, tuple(tuple(f.shape) for f in feats))
         b = self._bufs.get(key)
         if b is not None:
             return b
         _check_on_pyramid(feats, H, W)
         sizes = pyramid_sizes(H, W)
         new = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)
+        new_act = lambda *shape: torch.zeros(shape, dtype=act, device=dev)
         dims = dec.skip_dims_out
         h3, w3 = sizes[-1]
         b = {"pyr": [new(n_obj, B, 3, h, w) for h, w in sizes],
              # hidden / cell of every object and level: the spatial chain of this frame, the temporal state of the next
-             "hid": [new(n_obj, B, dims[i], *sizes[i]) for i in range(4)],
+             "hid": [new_act(n_obj, B, dims[i], *sizes[i]) for i in range(4)],
              "cell": [new(n_obj, B, dims[i], *sizes[i]) for i in range(4)],
-             "cat": [None] + [new(B, dims[i - 1] + dims[i], *sizes[i]) for i in range(1, 4)],
-             "up": [None] + [new(B, dims[i - 1], *sizes[i]) for i in range(1, 4)],
-             "top": new(n_obj * B, dims[-1], 2 * h3, 2 * w3),
+             "cat": [None] + [new_act(B, dims[i - 1] + dims[i], *sizes[i]) for i in range(1, 4)],
+             "up": [None] + [new_act(B, dims[i - 1], *sizes[i]) for i in range(1, 4)],
+             "top": new_act(n_obj * B, dims[-1], 2 * h3, 2 * w3),
              "outs": new(B, O, H, W), "valid": torch.zeros((B, O), dtype=torch.int32, device=dev)}
         self._bufs[key] = b
         return b
@@ -942,7 +1036,7 @@ class RefineStep:
                 up_src = hidden
             spatial = cur
         upsample_bilinear_into(bufs["hid"][3].view(n_obj * B, dims[3], *bufs["hid"][3].shape[-2:]), bufs["top"], 0, "write")
-        logits = dec._conv(bufs["top"], dec.conv_out.weight, dec.conv_out.bias)    # [n_obj * B, 1, 2h, 2w]
+        logits = dec._conv(bufs["top"], *dec.head_weights())                        # [n_obj * B, 1, 2h, 2w]
         logits = logits.view(n_obj, B, *logits.shape[-2:]).transpose(0, 1)          # [B, n_obj, 2h, 2w] (strided view)
         refine_finish(logits, bufs["valid"], bufs["outs"], mask_hist_new, n_obj)
         if self.only_spatial:

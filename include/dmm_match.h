@@ -854,12 +854,14 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
 
 /* ---------------------------------------------------------------------------------------------
  * (12) The ConvLSTM refine decoder (dmm/modules/base.py:71-188 RSISMask, dmm/modules/clstm.py:68-131 ConvLSTMCellMask, driven
- * per object by dmm/modules/evaluator.py:179-212): everything BETWEEN its convolutions.  fp32, dense planes (row stride =
- * width, channel stride = plane), batch / object strides in elements; nothing allocates, no memset nodes.  Used by
+ * per object by dmm/modules/evaluator.py:179-212): everything BETWEEN its convolutions.  fp32 ((12i)-(12k): the evaluator's
+ * forward on bf16 activations), dense planes (row stride = width, channel stride = plane), batch / object strides in elements;
+ * nothing allocates, no memset nodes.  Used by
  * dmm_net_amd/decoder.py, which keeps the convolutions on the library.  (12a)-(12d) are the forward; (12e) is the backward of
  * the cell (12b); (12f)-(12h) are what the refine step of TRAINING (dmm/modules/trainer.py:236-306) runs around the decoder:
  * the backward of the pyramid (12a), the backward of the upsample (12c) in 'write' mode, and the trainer's own finish
- * (nearest interpolation, sigmoid, pad) with its backward.  None of (12f)-(12h) uses an atomic or a workspace.
+ * (nearest interpolation, sigmoid, pad) with its backward.  None of (12f)-(12h) uses an atomic or a workspace.  (12i)-(12k) are
+ * (12b)-(12d) on bf16 activations, for the evaluator behind a bf16 encoder (RSISMask.compute_dtype = torch.bfloat16).
  *
  * (12a) dmm_mask_pyramid_f32 -- evaluator.py:188-195: MaxPool2d((2,2), ceil_mode=True) applied 5, 4, 3 and 2 times to the planes
  *   prev_mask[b, t], y_mask[b, t], init_pred[b, t] (each H x W at base + b * sb + t * so), b < B, t < n_obj, in ONE launch and
@@ -935,6 +937,22 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  *   block, summed Y then X ascending; a logit nobody reads (out < in) gets 0; p is recomputed from the logit.  d_outs
  *   [B, O, H, W] dense (rows t >= n_obj are not read); d_logits: plane (b, t), t < n_obj, at base + b * sb_d + t * so_d.
  *
+ * (12i)-(12k) The forward entries (12b)-(12d) with the ACTIVATIONS -- what the library convolutions write and read -- stored as
+ *   bf16 (the upper 16 bits of the fp32 pattern; pointers declared void *, 2-byte aligned, strides in ELEMENTS as before).  One
+ *   rule for all three: every 16-bit value is widened to fp32 on load (exact), the expressions are those of the fp32 entry in
+ *   the same order (the library is built with -ffp-contract=off; the kernels are one template over the storage type), and every
+ *   16-bit output is rounded ONCE, to nearest even, at its store (a NaN becomes 0x7FC0, torch's rule).  So entry_bf16(x) equals
+ *   bf16(entry_f32(widened x)) bit for bit, and its fp32 outputs equal entry_f32's bit for bit.  A lane owns one position and
+ *   issues 2-byte loads and stores: any width, any 2-byte-aligned plane or row, nothing stored outside the tensor.  No backward
+ *   forms, no atomics, no workspace.  Each entry validates as its fp32 sibling does: the same answers in the same order, before
+ *   any HIP call.
+ * (12i) dmm_clstm_gates_bf16 -- (12b) with pre0..2, hidden and hidden_copy bf16 (same null meanings and batch strides).  masks,
+ *   w_mask, cell_prev and cell stay fp32: the cell state is the recurrence along the object chain and keeps full precision; the
+ *   mask planes and the 36-weight stencil are what (12a) and the fp32 parameters hand over.
+ * (12j) dmm_upsample_bilinear_into_bf16 -- (12c) with src and dst bf16, modes 0 / 1 / 2; in modes 1 and 2 dst is read as bf16,
+ *   combined in fp32 and rounded once.
+ * (12k) dmm_refine_finish_bf16 -- (12d) with bf16 logits (the output of a bf16 conv_out); outs and mask_hist fp32, valid int32.
+ *
  * Answers of (12f)-(12h) before any launch, in this order: DMM_ERR_BAD_ARG for a negative B / O / n_obj, n_obj > O, a size
  * <= 0, a channel range outside d_dst; (12g) DMM_ERR_UNSUPPORTED for H < h or W < w; DMM_OK when there is nothing to do
  * (B == 0, no object, no wanted plane); DMM_ERR_BAD_ARG for a needed null pointer, a negative stride, an output plane stride
@@ -957,6 +975,14 @@ DMM_API int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int
                                            int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream);
 DMM_API int dmm_refine_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
                                   int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist, dmm_stream_t stream);
+DMM_API int dmm_clstm_gates_bf16(const void *pre0, const void *pre1, const void *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                 const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                 int hidden_size, int h, int w, void *hidden, float *cell, void *hidden_copy, int64_t sb_copy,
+                                 dmm_stream_t stream);
+DMM_API int dmm_upsample_bilinear_into_bf16(const void *src, int64_t sb_src, int B, int C, int h, int w, void *dst,
+                                            int64_t sb_dst, int C_dst, int c0, int H, int W, int mode, dmm_stream_t stream);
+DMM_API int dmm_refine_finish_bf16(const void *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const int *valid,
+                                   int B, int O, int n_obj, int H, int W, float *outs, float *mask_hist, dmm_stream_t stream);
 DMM_API int dmm_mask_pyramid_bwd_f32(const float *prev_mask, const float *init_pred, int64_t sb_prev, int64_t so_prev,
                                      int64_t sb_init, int64_t so_init, int B, int n_obj, int H, int W, const float *d_out5,
                                      const float *d_out4, const float *d_out3, const float *d_out2, float *d_prev,
