@@ -205,6 +205,15 @@ class ClipProposals:
         return cls(prob.to(dev, non_blocking=True), boxes.to(dev, non_blocking=True), scores.to(dev, non_blocking=True),
                    counts.to(dev, non_blocking=True))
 
+    def load(self, proposals, T: int, im_h: int, im_w: int) -> None:
+        """The first T frames of this (larger) buffer = a clip: another ``ClipProposals`` of the same B, R and M, or
+        proposals[b][t] BoxLists (``from_boxlists``)."""
+        if isinstance(proposals, ClipProposals):
+            for name in ("prob", "boxes", "scores", "counts"):
+                getattr(self, name)[:T].copy_(getattr(proposals, name)[:T], non_blocking=True)
+        else:
+            ClipProposals.from_boxlists(proposals, T, im_h, im_w, self.prob.device, out=self)
+
     @classmethod
     def empty(cls, T, B, R, M, device):
         f32 = dict(dtype=torch.float32, device=device)

@@ -22,14 +22,17 @@ Nothing here has a CPU implementation of the device work: CPU tensors raise ``Dm
 """
 from __future__ import annotations
 
+import contextlib
 import io
 import os
 import pickle
+from collections import namedtuple
 from typing import Callable, List, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, ops
+from .roi_features import roialign4_mean_into
 from .proposals import ClipProposals, ProposalSlots, SimpleBoxList, filter_results, forward_mask_prop, prepare_slots
 
 
@@ -174,7 +177,6 @@ def load_offline_proposals(path: str, map_location="cpu"):
 # ------------------------------------------------------------------------------------------------------------------
 # frame loop
 # ------------------------------------------------------------------------------------------------------------------
-import contextlib
 _NULL = contextlib.nullcontext()
 
 
@@ -193,6 +195,57 @@ def _slice_batch(out, lo: int, hi: int):
     """Rows lo..hi of every tensor in an encoder's output."""
     return _map_tensors(out, lambda v: v[lo:hi])
 
+
+def _frame_features(chunk, g: int, j: int, B: int):
+    """The encoder output of frame j of a time-major chunk of g frames (a one-frame chunk is handed over whole)."""
+    return chunk if g == 1 else _slice_batch(chunk, j * B, (j + 1) * B)
+
+
+def _frame_inputs(t: int, y0, targets, n_frames):
+    """(extra, y_mask) of frame t: which videos are past their real length (evaluator.py:86), and the annotation the
+    decoder is shown -- frame 0's own, the per-frame targets, or ``None`` = zeros (only the decoder reads it)."""
+    y_mask = y0 if t == 0 else (targets[:, t].float().view(y0.shape) if targets is not None else None)
+    return [n <= t for n in n_frames], y_mask
+
+
+def _reported(t: int, outs, y0):
+    return y0 if t == 0 else outs           # frame 0 only warms the decoder state (evaluator.py:119-128)
+
+
+def _emit_labels(on_labels, t: int, labels, extra):
+    for b, skip in enumerate(extra):
+        if not skip:                            # only videos that really have a frame t
+            on_labels(b, t, labels[b])
+
+
+ClipSchedule = namedtuple("ClipSchedule", "chunks chunk_of G")         # see FrameLoop._schedule
+
+
+def img_base_rows(sched: ClipSchedule, B: int) -> List[int]:
+    """Per frame t, the first image row of its features in the plan's feature batch [2 * G * B, ..]: chunk k lives in
+    half k % 2 (the steps of chunk k read one half while chunk k + 1 lands in the other), frame j of it at j * B."""
+    return [(k % 2) * sched.G * B + (t - sched.chunks[k][0]) * B for t, k in enumerate(sched.chunk_of)]
+
+
+def step_tables(n_frames: Sequence[int], n_tplt: Sequence[int], T: int) -> list:
+    """[T, 2, B] rows of ``StepPlan.tables``: ``[t, 0]`` = m_valid, the live templates of video b in frame t (0 = skipped:
+    past its length, or no templates); ``[t, 1]`` = commit, 1 where frame t's masks become the history (never in frame 0)."""
+    live = [[0 if (n <= t or n_tplt[b] == 0) else n_tplt[b] for b, n in enumerate(n_frames)] for t in range(T)]
+    return [[row, [int(t > 0 and m > 0) for m in row]] for t, row in enumerate(live)]
+
+
+class StepKey(namedtuple("StepKey", "B O H W R Mm K G tail fused cfg nms_thresh mask_thresh padding")):
+    """What makes two clips share a captured frame step: the shapes of the plan's buffers AND every value the captured
+    launches carry as an immediate -- the solver configuration ``cfg`` = (score_weight, max_iter, proj_iter, lr, is_test,
+    algo), the NMS / paste thresholds, the padding, which epilogue runs (``fused``) and whether the step ends in commit
+    + label map (``tail``: no decoder).  A change of any of them (``loop.nms_thresh = ...``, another match layer) must
+    rebuild and recapture -- the BoxList path reads them live.  Built in ``FrameLoop._step_key`` only."""
+    __slots__ = ()
+
+    def runs_on_slots(self) -> bool:
+        """Shapes inside the kernels' envelopes; the Hungarian step exists in the fused epilogue form only."""
+        return (0 < self.R <= 1024 and self.Mm + 2 * self.padding <= 64 and self.B * self.K <= 65535 and self.O <= 32
+                and self.K <= 256 and (self.cfg[5] != "hun" or self.fused))
 
 
 class StepPlan:
@@ -218,28 +271,26 @@ class StepPlan:
     (``img_base[t]``).  ``hist`` is mask_last_occurence / mask_hist, ``tplt_feat`` the template features (fixed from
     frame 0, dmm_model.py:44)."""
 
-    def __init__(self, B, O, H, W, R, Mm, K, G, T_cap, feat_like, device, cfg, nms_thresh, mask_thresh, padding,
-                 tail: bool, fuse_epilogue: bool = True):
-        from . import ops
-        self.B, self.O, self.H, self.W, self.R, self.K, self.G, self.T_cap = B, O, H, W, R, K, G, T_cap
-        self.cfg, self.tail = cfg, bool(tail)
-        self.nms_thresh, self.mask_thresh, self.padding = float(nms_thresh), float(mask_thresh), int(padding)
+    def __init__(self, key: StepKey, T_cap: int, feat_like, device):
+        self.key, self.T_cap = key, T_cap
+        (B, O, H, W, R, Mm, K, G, self.tail, self.fused, self.cfg, self.nms_thresh, self.mask_thresh,
+         self.padding) = key
+        self.B, self.O, self.H, self.W, self.R, self.K, self.G = B, O, H, W, R, K, G
         dev = torch.device(device)
         f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         self.clip = ClipProposals.empty(T_cap, B, R, Mm, dev)
         # fused epilogue (dmm_step_finish_f32): the selected proposals are pasted on the fly in the mix, the soft planes
         # are never written, commit / label merge / the history's 1-bit planes come out of the same pass
-        self.fused = bool(fuse_epilogue) and O <= 8 and Mm + 2 * padding <= 32
         self.slots = ProposalSlots(B, K, H, W, R, dev, soft_planes=not self.fused)
         self.Pp = ops.padded_width(K, O)
         self.Rb = torch.zeros((B, O, self.Pp), **f32)
         self.packed_hist = torch.zeros((B, O, ops.pack_words(H * W)), dtype=torch.int64, device=dev)
-        cl = [f.dim() == 4 and f.is_contiguous(memory_format=torch.channels_last) and not f.is_contiguous() for f in feat_like]
+        cl = [f.dim() == 4 and f.is_contiguous(memory_format=torch.channels_last) and not f.is_contiguous()
+              for f in feat_like]
         self.feats = [torch.empty((2 * G * B,) + tuple(f.shape[1:]), dtype=f.dtype, device=dev,
                                   memory_format=torch.channels_last if c else torch.contiguous_format).zero_()
                       for f, c in zip(feat_like, cl)]
-        C = int(feat_like[0].shape[1])
-        self.D = 4 * C
+        self.D = 4 * int(feat_like[0].shape[1])
         self.feat_p = torch.zeros((B * K, self.D), **f32)
         self.tplt_feat = torch.zeros((B, O, self.D), **f32)
         self.hist = torch.zeros((B, O, H, W), **f32)
@@ -248,7 +299,7 @@ class StepPlan:
         self.workspace = torch.empty((int(_lib.load().dmm_workspace_bytes_packed(B, K, O, self.D, H * W)),),
                                      dtype=torch.uint8, device=dev)
         self.step = torch.zeros((1,), **i32)
-        self.tables = torch.zeros((T_cap, 2, B), **i32)          # [t, 0] = m_valid, [t, 1] = commit
+        self.tables = torch.zeros((T_cap, 2, B), **i32)          # [t, 0] = m_valid, [t, 1] = commit (step_tables)
         self.cur = torch.zeros((2, B), **i32)
         self.img_base = torch.zeros((T_cap,), **i32)
         self.n_tplt = torch.zeros((B,), **i32)
@@ -261,72 +312,81 @@ class StepPlan:
         self.graphs = {}                                         # row_scale? -> captured graph
         self.device = dev
 
-    def key_fits(self, B, O, H, W, R, Mm, K, G, T, feat_like, tail, fuse_epilogue=True, cfg=None, nms_thresh=None,
-                 mask_thresh=None, padding=None):
-        """Can this plan (buffers + captured graphs) serve the clip?  Shapes AND every value the captured launches carry
-        as an immediate: the solver configuration, the NMS / paste thresholds and the padding are baked into the graph,
-        so a change of any of them (``loop.nms_thresh = ...``, another match layer) must rebuild and recapture --
-        the BoxList path reads them live on every frame."""
-        if cfg is not None and tuple(cfg) != tuple(self.cfg):
-            return False
-        if (nms_thresh is not None and float(nms_thresh) != self.nms_thresh) or \
-                (mask_thresh is not None and float(mask_thresh) != self.mask_thresh) or \
-                (padding is not None and int(padding) != self.padding):
-            return False
-        return ((self.B, self.O, self.H, self.W, self.R, self.clip.M, self.K, self.G, self.tail) ==
-                (B, O, H, W, R, Mm, K, G, bool(tail)) and T <= self.T_cap and
-                self.fused == (bool(fuse_epilogue) and O <= 8 and Mm + 2 * self.padding <= 32) and
-                all(tuple(a.shape[1:]) == tuple(b.shape[1:]) and a.dtype == b.dtype and
+    def fits(self, key: StepKey, T: int, feat_like) -> bool:
+        """Can this plan (buffers + captured graphs) serve the clip?  Same key, T within the buffers, same feature layout."""
+        return (key == self.key and T <= self.T_cap and
+                all(tuple(a.shape[1:]) == tuple(b.shape[1:]) and a.dtype == b.dtype and b.device == self.device and
                     a.is_contiguous() == b.is_contiguous() for a, b in zip(self.feats, feat_like)))
+
+    def land(self, k: int, backbone, enc_side, fence):
+        """Backbone features of chunk k -> half k % 2 of the feature batch, on the encoder's stream when there is one
+        (behind ``fence``, an event of the main stream) -> the event the chunk's first step waits for."""
+        with torch.cuda.stream(enc_side) if enc_side is not None else _NULL:
+            if fence is not None:
+                enc_side.wait_event(fence)
+            lo = (k % 2) * self.G * self.B
+            for dst, src in zip(self.feats, backbone):
+                dst[lo:lo + src.shape[0]].copy_(src)
+            return enc_side.record_event() if enc_side is not None else None
+
+    def set_history(self, h):
+        """``hist`` = h, with its 1-bit planes when the fused step counts on them."""
+        self.hist.copy_(h.view(self.B, self.O, self.H, self.W))
+        if self.fused:
+            self.packed_hist.copy_(ops.pack_masks(self.hist))
+
+    def raise_on_status(self, T: int):
+        """algo 'hun': the clip's assignment statuses, one read: scipy's ValueError for a NaN / infeasible cost table."""
+        if self.cfg[5] != "hun" or torch.cuda.is_current_stream_capturing():
+            return
+        st = self.status_all[:T].cpu()
+        bad = torch.nonzero(st)
+        if bad.numel():
+            t, b = (int(v) for v in bad[0])
+            raise ValueError(f"{ops._LSAP_MESSAGES.get(int(st[t, b]), 'linear_sum_assignment failed')} "
+                             f"(video {b}, frame {t})")
 
     def body(self):
         """The frame step as launches on the current stream (captured, or run directly)."""
-        from . import ops
-        from .roi_features import roialign4_mean_into
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        _lib.call("dmm_step_select_i32", None, self.tables.data_ptr(), self.step.data_ptr(), 2 * self.B, self.cur.data_ptr(),
-                  s)
+        s, B, O, HW = torch.cuda.current_stream(self.device).cuda_stream, self.B, self.O, self.H * self.W
+        _lib.call("dmm_step_select_i32", None, self.tables.data_ptr(), self.step.data_ptr(), 2 * B, self.cur.data_ptr(), s)
         prepare_slots(self.clip, self.slots, self.nms_thresh, self.mask_thresh, self.padding, step=self.step,
                       img_base=self.img_base)
         roialign4_mean_into(self.slots.rois, self.feats, self.feat_p)
         score_weight, max_iter, proj_iter, lr, is_test, algo = self.cfg
+        feat_p = self.feat_p.view(B, self.K, self.D)
         if self.fused:
+            inputs = (self.slots.packed, self.packed_hist, feat_p, self.tplt_feat, self.slots.scores, self.slots.count,
+                      self.cur[0], HW)
             if algo == "hun":                                    # the exact assignment (scipy's), status per step
-                ops.match_solve_packed_hun(self.slots.packed, self.packed_hist, self.feat_p.view(self.B, self.K, self.D),
-                                           self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0],
-                                           self.H * self.W, score_weight=score_weight, is_test=is_test,
-                                           out=(self.Rb, self.out[1], self.out[2]), status=self.status,
-                                           workspace=self.workspace)
-                self.status_all.index_copy_(0, self.step.long(), self.status.view(1, self.B))
+                ops.match_solve_packed_hun(*inputs, score_weight=score_weight, is_test=is_test, status=self.status,
+                                           out=(self.Rb, self.out[1], self.out[2]), workspace=self.workspace)
+                self.status_all.index_copy_(0, self.step.long(), self.status.view(1, B))
             else:
-                ops.match_solve_packed(self.slots.packed, self.packed_hist, self.feat_p.view(self.B, self.K, self.D),
-                                       self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0], self.H * self.W,
-                                       score_weight=score_weight, max_iter=max_iter, proj_iter=proj_iter, lr=lr,
-                                       is_test=is_test, out=(self.Rb, self.out[1], self.out[2], self.out[3]),
-                                       workspace=self.workspace)
+                ops.match_solve_packed(*inputs, score_weight=score_weight, max_iter=max_iter, proj_iter=proj_iter, lr=lr,
+                                       is_test=is_test, out=(self.Rb,) + self.out[1:], workspace=self.workspace)
             if self.row_scale is not None:
                 self.Rb.mul_(self.row_scale[:, :, None])         # rows of slots i < O with valid[i] == 0: zero weights
             c = self.clip
             _lib.call("dmm_step_finish_f32", None,
                       self.Rb.data_ptr(), self.Pp, c.prob.data_ptr(), c.boxes.data_ptr(), self.slots.keep.data_ptr(),
-                      self.slots.count.data_ptr(), self.B, c.R, c.M, self.K, self.O, self.H, self.W, self.padding,
+                      self.slots.count.data_ptr(), B, c.R, c.M, self.K, O, self.H, self.W, self.padding,
                       self.step.data_ptr(), self.cur[0].data_ptr(), self.cur[1].data_ptr() if self.tail else None,
                       self.n_tplt.data_ptr(), self.full.data_ptr(), self.hist.data_ptr(), self.packed_hist.data_ptr(),
                       self.labels.data_ptr() if self.tail else None, s)
             _lib.call("dmm_step_advance", None, self.step.data_ptr(), s)
             return
         assert algo == "relax", "algo 'hun' runs in the fused epilogue form of the frame step only (FrameLoop._slots_ok)"
-        ops.match_forward_packed(self.slots.planes, self.slots.packed, self.hist, self.feat_p.view(self.B, self.K, self.D),
-                                 self.tplt_feat, self.slots.scores, self.slots.count, self.cur[0],
-                                 score_weight=score_weight, max_iter=max_iter, proj_iter=proj_iter, lr=lr, is_test=is_test,
-                                 out=self.out, workspace=self.workspace)
+        ops.match_forward_packed(self.slots.planes, self.slots.packed, self.hist, feat_p, self.tplt_feat, self.slots.scores,
+                                 self.slots.count, self.cur[0], score_weight=score_weight, max_iter=max_iter,
+                                 proj_iter=proj_iter, lr=lr, is_test=is_test, out=self.out, workspace=self.workspace)
         if self.row_scale is not None:
             self.full.mul_(self.row_scale[:, :, None, None])
         if self.tail:
-            _lib.call("dmm_commit_masks_f32", None, self.full.data_ptr(), self.hist.data_ptr(), self.cur[1].data_ptr(),
-                      self.B, self.O * self.H * self.W, s)
-            _lib.call("dmm_merge_labels_f32", None, self.full.data_ptr(), self.B, self.O, self.H * self.W,
-                      self.O * self.H * self.W, self.H * self.W, self.n_tplt.data_ptr(), self.labels.data_ptr(), s)
+            _lib.call("dmm_commit_masks_f32", None, self.full.data_ptr(), self.hist.data_ptr(), self.cur[1].data_ptr(), B,
+                      O * HW, s)
+            _lib.call("dmm_merge_labels_f32", None, self.full.data_ptr(), B, O, HW, O * HW, HW, self.n_tplt.data_ptr(),
+                      self.labels.data_ptr(), s)
         _lib.call("dmm_step_advance", None, self.step.data_ptr(), s)
 
     def run_step(self, graph: bool):
@@ -336,18 +396,18 @@ class StepPlan:
         g = self.graphs.get(key)
         if g is None:
             # warm-up on the real buffers would advance the clip: save / restore the two pieces of state it touches
-            from .ops import _CAPTURE_LOCK
             keep_step, keep_hist, keep_packed = self.step.clone(), self.hist.clone(), self.packed_hist.clone()
             self.body()
             self.step.copy_(keep_step)
             self.hist.copy_(keep_hist)
             self.packed_hist.copy_(keep_packed)
-            with _CAPTURE_LOCK, torch.cuda.device(self.device):
+            with ops._CAPTURE_LOCK, torch.cuda.device(self.device):
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     self.body()
             self.graphs[key] = g
         g.replay()
+
 
 class FrameLoop:
     """Frame loop of the evaluator for a batch of B videos (evaluator.py:63-213).
@@ -368,25 +428,26 @@ class FrameLoop:
     Two reorderings against the reference's strictly sequential loop, neither changes a result for a feed-forward
     encoder (``lookahead = False``, ``encode_ahead = 1``, ``encode_overlap = False`` restore the reference's order):
     ``lookahead``: the proposals of frame t + 1 (paste, NMS, top-k -- they depend on nothing the loop computes) are
-    prepared on a side stream after frame t's work has been enqueued, so the step's one host sync does not drain the main
-    stream; ``encode_ahead``: that many frames of the clip go through the encoder as one time-major batch (the encoder
-    has no temporal state; the templates, the mask history and the decoder carry it), and with ``encode_overlap`` the
-    NEXT batch is encoded on its own stream while this one's steps run (outputs of a static-buffer encoder are cloned).
-    An encoder whose output for an image depends on the rest of the batch (BatchNorm in train mode) needs
-    ``encode_ahead = 1``.
+    prepared on a side stream after frame t's work has been enqueued, so the step's one host sync does not drain the
+    main stream; ``encode_ahead``: that many frames of the clip go through the encoder as one time-major batch (the
+    encoder has no temporal state; the templates, the mask history and the decoder carry it), and with
+    ``encode_overlap`` the NEXT batch is encoded on its own stream while this one's steps run (outputs of a
+    static-buffer encoder are cloned).  An encoder whose output for an image depends on the rest of the batch
+    (BatchNorm in train mode) needs ``encode_ahead = 1``.
 
     Two execution forms, bit-identical results (tests/test_gpu_video.py):
-    ``slots = True`` (default; raw proposal masks, ``algo: 'relax'``, or ``'hun'`` with the fused epilogue): the FIXED-SLOT frame step of ``StepPlan`` -- the
-    clip's raw proposals are uploaded once (``proposals.ClipProposals``; ``run`` also accepts one directly), the proposals
-    that survive NMS + top-k live in ``max_proposals`` slots per video with the live count on the device, the whole step is
-    nine launches and, with ``graph = True``, ONE HIP-graph replay per frame: no host sync, upload or allocation per
-    frame.  ``fuse_epilogue`` (<= 8 template slots, raw masks <= 30 x 30): no soft proposal plane is ever written, the mix
-    pastes its selected proposals on the fly and emits ``out_mask_last``, the label map and the template history's 1-bit
-    planes in the same pass.  ``on_labels(b, t, labels)`` receives a view of a per-clip buffer, valid in stream order.
+    ``slots = True`` (default; raw proposal masks, ``algo: 'relax'``, or ``'hun'`` with the fused epilogue): the
+    FIXED-SLOT frame step of ``StepPlan`` -- the clip's raw proposals are uploaded once (``proposals.ClipProposals``;
+    ``run`` also accepts one directly), the proposals that survive NMS + top-k live in ``max_proposals`` slots per video
+    with the live count on the device, the whole step is nine launches and, with ``graph = True``, ONE HIP-graph replay
+    per frame: no host sync, upload or allocation per frame.  ``fuse_epilogue`` (<= 8 template slots, raw masks
+    <= 30 x 30): no soft proposal plane is ever written, the mix pastes its selected proposals on the fly and emits
+    ``out_mask_last``, the label map and the template history's 1-bit planes in the same pass.
+    ``on_labels(b, t, labels)`` receives a view of a per-clip buffer, valid in stream order.
     ``slots = False``: the BoxList path -- paste every raw proposal, NMS, index the kept ones (one host sync per frame),
     ``DMM_Model.inference`` -- the reference's per-frame steps one to one (also taken for ``pasted = True``).  Under
-    ``algo: 'hun'`` the fixed-slot step keeps each step's assignment status on the device and reads the clip's once at its
-    end: a NaN / infeasible cost table raises scipy's ``ValueError`` naming the video and frame.
+    ``algo: 'hun'`` the fixed-slot step keeps each step's assignment status on the device and reads the clip's once at
+    its end: a NaN / infeasible cost table raises scipy's ``ValueError`` naming the video and frame.
     """
 
     def __init__(self, encoder: Callable, dmm, refine: Optional[Callable] = None, nms_thresh: float = 0.4,
@@ -394,27 +455,29 @@ class FrameLoop:
         self.encoder, self.dmm, self.refine = encoder, dmm, refine
         self.nms_thresh, self.max_proposals = float(nms_thresh), int(max_proposals)
         self.mask_thresh, self.padding, self.pasted = float(mask_thresh), int(padding), bool(pasted)
-        self.lookahead = True                                    # proposals of frame t + 1 on a side stream (see run)
-        self.encode_ahead = 0                                    # frames per encoder batch (see run); 1 = the reference's order;
-                                                                 # 0 = by clip length: ceil(T / 3) within [4, 9]
-        self.steps_priority = 0                                  # HIP stream priority of the steps' stream (-1: 0.412 -> 0.407 ms per step, within noise)
-        self.encode_overlap = True                               # next chunk's encoder on its own stream (see run)
+        self.lookahead = True                # proposals of frame t + 1 on a side stream (see run)
+        self.encode_ahead = 0                # frames per encoder batch (see run); 1 = the reference's order;
+                                             # 0 = by clip length: ceil(T / 3) within [4, 9]
+        self.steps_priority = 0              # HIP priority of the steps' stream (-1: 0.412 -> 0.407 ms per step: noise)
+        self.encode_overlap = True           # next chunk's encoder on its own stream (see run)
         # fixed-slot frame step (StepPlan): raw proposals of the whole clip on the device, two-phase paste, kept counts
         # stay on the device, and -- ``graph`` -- the whole step replayed from one HIP graph.  Off = the BoxList path
         # (paste every raw proposal, NMS, gather the kept ones, one host sync per frame).
         self.slots = True
         self.graph = True
-        self.fuse_epilogue = True                                # dmm_step_finish_f32: mix with on-the-fly paste + commit +
-                                                                 # label map in one pass, no soft proposal planes (StepPlan)
-        self.encode_first = 0                                    # frames in the FIRST encoder batch (0 = encode_ahead): a short
-                                                                 # first chunk shortens the pipeline fill before frame 0's step
-        self.encoder_priority = 0                                # HIP stream priority of the encoder's side stream (-1 = high; measured harmful, see encoder.pick_parallel_stream)
+        self.fuse_epilogue = True            # dmm_step_finish_f32: mix with on-the-fly paste + commit + label map in
+                                             # one pass, no soft proposal planes (StepPlan)
+        self.encode_first = 0                # frames in the FIRST encoder batch (0 = encode_ahead): a short first
+                                             # chunk shortens the pipeline fill before frame 0's step
+        self.encoder_priority = 0            # HIP priority of the encoder's side stream (-1 = high: measured harmful,
+                                             # see encoder.pick_parallel_stream)
         self._side = {}
         self._plan = None
         self._prefetched = None              # (key, encoder output) of the next clip's first chunk (run(next_frames=...))
         self.record_iters = False            # fixed-slot path: keep every step's solver iteration counts in
         self.last_iters = None               # ``last_iters`` [T,B] int32 (one small device copy per step; tests)
 
+    # ---- the clip's encoder chunks ---------------------------------------------------------------------------------
     def _frames_per_chunk(self, T: int, pipelined: bool = False) -> int:
         """``encode_ahead``, or by clip length when it is 0.  The ResNet gets more efficient with the batch (4 videos of
         255x448: 0.64 / 0.60 ms per frame step at 4 frames per chunk for clips of 12 / 24 frames, 0.50 at 8 of 24, 0.46 at
@@ -429,6 +492,39 @@ class FrameLoop:
             return max(4, min(12, int(T)))
         return max(4, min(9, -(-int(T) // 3)))
 
+    def _first_chunk(self, T: int, pipelined: bool = False) -> int:
+        G = max(1, min(self._frames_per_chunk(T, pipelined), T))
+        return max(1, min(int(self.encode_first) or G, G, T))
+
+    def _schedule(self, T: int, pipelined: bool = False, boxlist: bool = False) -> ClipSchedule:
+        """The encoder chunks of a clip: ``chunks[k] = (t0, g)`` = frames [t0, t0 + g) as one time-major batch, at most
+        G = ``_frames_per_chunk`` frames each, tiling [0, T) in order; ``chunk_of[t]`` = the chunk of frame t.  The
+        fixed-slot route starts with ``_first_chunk`` frames (``encode_first``: a shorter pipeline fill).  ``boxlist``:
+        the BoxList route keeps uniform chunks -- it does NOT apply ``encode_first`` (and never runs ``pipelined``)."""
+        G = max(1, min(self._frames_per_chunk(T, pipelined), T))
+        g0 = 0 if boxlist else self._first_chunk(T, pipelined)
+        chunks = ([(0, g0)] if g0 else []) + [(t0, min(G, T - t0)) for t0 in range(g0, T, G)]
+        return ClipSchedule(chunks, [k for k, (t0, g) in enumerate(chunks) for _ in range(g)], G)
+
+    def _encode_chunk(self, src, t0: int, g: int, main, enc_side, clone_static: bool, fence_on_main: bool):
+        """Frames [t0, t0 + g) of ``src`` [B,T,C,H,W] through the encoder as one time-major batch, on ``enc_side`` when
+        there is one, its outputs handed to ``main`` (``record_stream``) -> (encoder output, event or None).
+        ``clone_static``: clone what an encoder with static output buffers returns (its next call overwrites them).
+        ``fence_on_main``: the event is taken on ``main`` BEFORE encoding (for ``StepPlan.land`` to wait behind), not on
+        ``enc_side`` after it (for the consumer to wait on)."""
+        B, _, C, H, W = src.shape
+        event = main.record_event() if fence_on_main and enc_side is not None else None
+        with torch.cuda.stream(enc_side) if enc_side is not None else _NULL:
+            xs = src[:, t0] if g == 1 else src[:, t0:t0 + g].transpose(0, 1).reshape(g * B, C, H, W)
+            out = self.encoder(xs)
+            if clone_static and getattr(self.encoder, "static_outputs", False):
+                out = _map_tensors(out, lambda v: v.clone())
+            if enc_side is not None:
+                _map_tensors(out, lambda v: (v.record_stream(main), v)[1])
+                if not fence_on_main:
+                    event = enc_side.record_event()
+        return out, event
+
     def _side_stream(self, dev, role="proposals", beside=()):
         prio = int(self.encoder_priority) if role == "encoder" else (int(self.steps_priority) if role == "steps" else 0)
         key = (role, dev.index if dev.index is not None else torch.cuda.current_device(), prio)
@@ -440,29 +536,39 @@ class FrameLoop:
                 self._side[key] = torch.cuda.Stream(device=dev, priority=prio)
         return self._side[key]
 
-
     # ---- fixed-slot path ---------------------------------------------------------------------------------------------
-    def _slots_ok(self, frames, proposals, O) -> bool:
-        """The fixed-slot step covers the product's configuration: raw mask probabilities, the relaxed solver (or the
-        Hungarian one in the fused epilogue form: <= 8 template slots, raw masks <= 30 x 30), shapes inside the kernels'
-        envelopes.  Anything else takes the BoxList path."""
-        algo = self.dmm.match_algo
-        if not (self.slots and frames.is_cuda and not self.pasted and algo in ("relax", "hun")):
-            return False
+    def _step_key(self, B: int, O: int, H: int, W: int, proposals, G: int = 0) -> Optional[StepKey]:
+        """The ``StepKey`` of a clip under this loop's settings, or None for nested BoxLists that are empty or carry no
+        raw 'mask'.  The ONLY place that reads (R, Mm) off ``proposals`` (a ``ClipProposals``, or proposals[b][t]
+        BoxLists), derives K and decides ``fused``.  ``G`` is known once the clip is scheduled (``_replace``)."""
         if isinstance(proposals, ClipProposals):
             R, Mm = proposals.R, proposals.M
         else:
             ps = [p for v in proposals for p in v]
             if not ps or any("mask" not in p.fields() for p in ps):
-                return False
+                return None
             R, Mm = max(len(p) for p in ps), int(ps[0].get_field("mask").shape[-1])
         K = self.max_proposals if self.max_proposals > 0 else R
-        ok = 0 < R <= 1024 and Mm + 2 * self.padding <= 64 and frames.shape[0] * K <= 65535 and O <= 32 and K <= 256
-        if algo == "hun":                                         # the Hungarian step exists in the fused epilogue form
-            ok = ok and self.fuse_epilogue and O <= 8 and Mm + 2 * self.padding <= 32
-        return ok
+        ml, padding = self.dmm.match_layer, int(self.padding)
+        cfg = (float(ml.cfgs["score_weight"]), int(ml.max_iter), int(ml.proj_iter), float(ml.relax_lr),
+               int(bool(ml.is_test)), str(self.dmm.match_algo))
+        # fused epilogue (dmm_step_finish_f32): <= 8 template slots, raw masks <= 30 x 30 (+ padding <= 32)
+        fused = bool(self.fuse_epilogue) and O <= 8 and Mm + 2 * padding <= 32
+        return StepKey(int(B), int(O), int(H), int(W), int(R), int(Mm), int(K), int(G), self.refine is None, fused, cfg,
+                       float(self.nms_thresh), float(self.mask_thresh), padding)
 
-    def _run_slots(self, frames, first_masks, proposals, n_frames, targets, on_labels, next_frames=None):
+    def _slots_key(self, frames, proposals, O) -> Optional[StepKey]:
+        """The clip's key (G still open) when the fixed-slot step covers it -- raw mask probabilities, the relaxed solver or
+        the Hungarian one, ``StepKey.runs_on_slots`` -- else None: the clip takes the BoxList path."""
+        if not (self.slots and frames.is_cuda and not self.pasted and self.dmm.match_algo in ("relax", "hun")):
+            return None
+        key = self._step_key(frames.shape[0], O, frames.shape[3], frames.shape[4], proposals)
+        return key if key is not None and key.runs_on_slots() else None
+
+    def _slots_ok(self, frames, proposals, O) -> bool:
+        return self._slots_key(frames, proposals, O) is not None
+
+    def _run_slots(self, key, frames, first_masks, proposals, n_frames, targets, on_labels, next_frames=None):
         """``run`` on the fixed-slot step: zero host syncs per frame, and with ``graph`` one graph replay per frame.
 
         The steps run on the loop's OWN stream and the encoder's stream is PROBED against it: HIP maps streams onto a
@@ -480,20 +586,40 @@ class FrameLoop:
                 fast.avoid_streams.append(work)                  # ... and the encoder's own side stream a third one
         work.wait_stream(caller)
         with torch.cuda.stream(work):
-            history = self._run_slots_on_stream(frames, first_masks, proposals, n_frames, targets, on_labels, next_frames)
+            history = self._run_slots_on_stream(key, frames, first_masks, proposals, n_frames, targets, on_labels,
+                                                next_frames)
         caller.wait_stream(work)
         for h in history[:1]:
             h.record_stream(caller)                              # (the entries are views of one buffer)
         return history
 
-    def _first_chunk(self, T: int, pipelined: bool = False) -> int:
-        G = max(1, min(self._frames_per_chunk(T, pipelined), T))
-        return max(1, min(int(self.encode_first) or G, G, T))
+    def _plan_for(self, key: StepKey, T: int, feat_like, dev) -> StepPlan:
+        """The plan (buffers + captured graphs) for this key: the loop's one plan when it fits, else a new one."""
+        if self._plan is None or not self._plan.fits(key, T, feat_like):
+            self._plan = StepPlan(key, max(T, 32), feat_like, dev)
+        return self._plan
 
-    def _run_slots_on_stream(self, frames, first_masks, proposals, n_frames, targets, on_labels, next_frames=None):
+    def _set_templates(self, plan: StepPlan, y0, n_frames, T: int):
+        """forward_timestep_init (evaluator.py:215-225) on the plan: template boxes and features of frame 0 (chunk 0's
+        features must have landed), the valid layout, the clip's per-frame tables -> tplt_valid [B,O]."""
+        B, O, H, W = plan.B, plan.O, plan.H, plan.W
+        boxes, valid = mask_boxes(y0.view(B * O, H, W), 0.0)
+        tplt_valid = valid.view(B, O).long()
+        n_tplt, row_scale = self.dmm._valid_layout(tplt_valid)  # the clip's ONE host sync
+        ids = torch.arange(B, device=plan.device, dtype=torch.float32).repeat_interleave(O)
+        rois = torch.cat([ids[:, None], boxes], 1)
+        roialign4_mean_into(rois, plan.feats, plan.tplt_feat.view(B * O, -1))
+        if row_scale is not None:
+            plan.tplt_feat.mul_(row_scale[:, :, None])
+            plan.row_scale_buf.copy_(row_scale)
+        plan.row_scale = plan.row_scale_buf if row_scale is not None else None
+        plan.n_tplt.copy_(_lib.small_to_device(n_tplt, torch.int32, plan.device))
+        plan.tables[:T].copy_(_lib.small_to_device(step_tables(n_frames, n_tplt, T), torch.int32, plan.device))
+        return tplt_valid
+
+    def _run_slots_on_stream(self, key, frames, first_masks, proposals, n_frames, targets, on_labels, next_frames):
         B, T, C, H, W = frames.shape
-        O = first_masks.shape[1]
-        dev = frames.device
+        O, dev = first_masks.shape[1], frames.device
         main = torch.cuda.current_stream(dev)
         enc_side = self._side_stream(dev, "encoder") if self.encode_overlap else None
         # a prefetch is identified by the frames TENSOR it was issued for (held in the record, so the allocator cannot hand
@@ -502,179 +628,80 @@ class FrameLoop:
         if pre is not None and not (pre[0][0] is frames and pre[0][1] == frames._version):
             pre = None                                           # a prefetch for other frames: ignored
         pipelined = enc_side is not None and (pre is not None or next_frames is not None)
-        G = max(1, min(self._frames_per_chunk(T, pipelined), T))
-        need_features = self.refine is not None                  # the decoder reads refine_input_feat of every frame
-        static = getattr(self.encoder, "static_outputs", False)
-        plan = None
-
-        # chunks of the clip: (first frame, frames); the first one may be shorter (encode_first)
-        g0 = self._first_chunk(T, pipelined)
-        chunks = [(0, g0)] + [(t0, min(G, T - t0)) for t0 in range(g0, T, G)]
-        chunk_of = [k for k, (t0, g) in enumerate(chunks) for _ in range(g)]
-
-        def encode(k, clip=None):
-            """chunk k = frames [t0, t0 + g): encoder batch, time-major; its backbone features go to half k % 2 of the
-            plan's feature batch ON THE STREAM THAT PRODUCED THEM (a static-output encoder overwrites them on its next
-            call), after the steps that still read that half (chunk k - 2) have been passed on the main stream.
-            ``clip``: the NEXT clip's frames -- its first chunk, prefetched."""
-            t0, g = chunks[k] if clip is None else (0, self._first_chunk(clip.shape[1], True))
-            src = frames if clip is None else clip
-            ctx = torch.cuda.stream(enc_side) if enc_side is not None else _NULL
-            fence = main.record_event() if enc_side is not None else None
-            with ctx:
-                xs = src[:, t0] if g == 1 else src[:, t0:t0 + g].transpose(0, 1).reshape(g * src.shape[0], C, H, W)
-                out = self.encoder(xs)
-                if need_features and static:
-                    out = _map_tensors(out, lambda v: v.clone())
-                if enc_side is not None:
-                    _map_tensors(out, lambda v: (v.record_stream(main), v)[1])
-                return out, fence
-
-        def land(k, out, fence):
-            """backbone features of chunk k -> the plan's feature batch (needs the plan, i.e. the first chunk's shapes)."""
-            ctx = torch.cuda.stream(enc_side) if enc_side is not None else _NULL
-            with ctx:
-                if fence is not None:
-                    enc_side.wait_event(fence)
-                lo = (k % 2) * G * B
-                for dst, src in zip(plan.feats, out["backbone_feature"]):
-                    dst[lo:lo + src.shape[0]].copy_(src)
-                return enc_side.record_event() if enc_side is not None else None
-
+        chunks, chunk_of, G = sched = self._schedule(T, pipelined)
+        # chunk k's backbone features go to half k % 2 of the plan's feature batch ON THE STREAM THAT PRODUCED THEM (a
+        # static-output encoder overwrites them on its next call), behind a fence on main: past the steps that still read
+        # that half (chunk k - 2).  So its outputs need a clone only when a decoder reads refine_input_feat of every frame.
+        enc = dict(main=main, enc_side=enc_side, clone_static=self.refine is not None, fence_on_main=True)
         if enc_side is not None:
             enc_side.wait_stream(main)
-        if pre is not None and pre[0][2:] == (g0, enc_side):
-            out0 = pre[1]                                        # issued under the previous clip's last steps
+        if pre is not None and pre[0][2:] == (chunks[0][1], enc_side):
+            chunk = pre[1]                                       # issued under the previous clip's last steps
         else:
-            out0, _ = encode(0)
-        # ---- the plan (buffers + captured graph) for this shape --------------------------------------------------------
-        if isinstance(proposals, ClipProposals):
-            R, Mm = proposals.R, proposals.M
-        else:
-            R = max(len(p) for v in proposals for p in v)
-            Mm = int(proposals[0][0].get_field("mask").shape[-1])
-        K = self.max_proposals if self.max_proposals > 0 else R
-        cfg = self.dmm.match_layer
-        cfg = (float(cfg.cfgs["score_weight"]), int(cfg.max_iter), int(cfg.proj_iter), float(cfg.relax_lr),
-               int(bool(cfg.is_test)), str(self.dmm.match_algo))
-        tail = self.refine is None
-        plan = self._plan
-        if plan is None or plan.device != dev or not plan.key_fits(
-                B, O, H, W, R, Mm, K, G, T, out0["backbone_feature"], tail, self.fuse_epilogue, cfg=cfg,
-                nms_thresh=self.nms_thresh, mask_thresh=self.mask_thresh, padding=self.padding):
-            plan = self._plan = StepPlan(B, O, H, W, R, Mm, K, G, max(T, 32), out0["backbone_feature"], dev, cfg,
-                                         self.nms_thresh, self.mask_thresh, self.padding, tail, self.fuse_epilogue)
+            chunk, _ = self._encode_chunk(frames, *chunks[0], **enc)
+        plan = self._plan_for(key._replace(G=G), T, chunk["backbone_feature"], dev)
         # (the plan's buffers may have just been created -- zero-filled -- on THIS stream: chunk 0 lands behind that, not
         # behind the fence taken before the plan existed; a high-priority encoder stream overtook the fill otherwise)
-        ready = land(0, out0, main.record_event() if enc_side is not None else None)
-        chunk = out0
-        # ---- the clip's raw proposals and per-frame tables: one upload, before the loop ----------------------------
-        if isinstance(proposals, ClipProposals):
-            for dst, src in ((plan.clip.prob, proposals.prob), (plan.clip.boxes, proposals.boxes),
-                             (plan.clip.scores, proposals.scores), (plan.clip.counts, proposals.counts)):
-                dst[:T].copy_(src[:T], non_blocking=True)
-        else:
-            ClipProposals.from_boxlists(proposals, T, H, W, dev, out=plan.clip)
-        plan.img_base[:T].copy_(_lib.small_to_device([(chunk_of[t] % 2) * G * B + (t - chunks[chunk_of[t]][0]) * B
-                                                      for t in range(T)], torch.int32, dev))
+        ready = plan.land(0, chunk["backbone_feature"], enc_side, main.record_event() if enc_side is not None else None)
+        plan.clip.load(proposals, T, H, W)                       # the clip's raw proposals: one upload, before the loop
+        plan.img_base[:T].copy_(_lib.small_to_device(img_base_rows(sched, B), torch.int32, dev))
         plan.step.zero_()
         plan.status_all.zero_()
         y0 = first_masks.float().view(B, O, H * W)
-        plan.hist.copy_(y0.view(B, O, H, W))
-        if plan.fused:
-            from . import ops
-            plan.packed_hist.copy_(ops.pack_masks(plan.hist))
-        history, state, prev_mask, tplt_valid = [], None, y0, None
+        plan.set_history(y0)
+        history, state, prev_mask, tplt_valid, next_chunk = [], None, y0, None, None
         hist_all = torch.empty((T, B, O, H * W), dtype=torch.float32, device=dev)
         lab_all = torch.empty((T, B, H, W), dtype=torch.uint8, device=dev) if on_labels is not None else None
         it_all = torch.full((T, B), -1, dtype=torch.int32, device=dev) if self.record_iters else None
-        next_chunk = None
         for t in range(T):
-            extra = [n <= t for n in n_frames]
-            if t == 0:
-                y_mask = y0
-            elif targets is not None:
-                y_mask = targets[:, t].float().view(B, O, H * W)
-            else:
-                y_mask = None                                            # zeros (only the decoder reads it)
+            extra, y_mask = _frame_inputs(t, y0, targets, n_frames)
             kc = chunk_of[t]
-            j = t - chunks[kc][0]
-            if j == 0:
+            t0, g = chunks[kc]
+            if t == t0:                                          # a chunk's first frame: take it, issue the one after it
                 if t > 0:
                     chunk, ready = next_chunk
                 if ready is not None:
                     main.wait_event(ready)
                 if kc + 1 < len(chunks):
-                    o, f = encode(kc + 1)
-                    next_chunk = (o, land(kc + 1, o, f))
+                    o, fence = self._encode_chunk(frames, *chunks[kc + 1], **enc)
+                    next_chunk = (o, plan.land(kc + 1, o["backbone_feature"], enc_side, fence))
                 elif (next_frames is not None and enc_side is not None and next_frames.is_cuda
                       and tuple(next_frames.shape[2:]) == (C, H, W)):
                     # the encoder's stream has nothing left to do for this clip: the next clip's first chunk
                     next_frames.record_stream(enc_side)          # read there after this run has returned
-                    self._prefetched = ((next_frames, next_frames._version,
-                                         self._first_chunk(next_frames.shape[1], True), enc_side),
-                                        encode(0, clip=next_frames)[0])
-            if t == 0:                                                   # forward_timestep_init, :215-225
-                boxes, valid = mask_boxes(y0.view(B * O, H, W), 0.0)
-                tplt_valid = valid.view(B, O).long()
-                n_tplt, row_scale = self.dmm._valid_layout(tplt_valid)  # the clip's ONE host sync
-                ids = torch.arange(B, device=dev, dtype=torch.float32).repeat_interleave(O)
-                rois = torch.cat([ids[:, None], boxes], 1)
-                from .roi_features import roialign4_mean_into
-                roialign4_mean_into(rois, plan.feats, plan.tplt_feat.view(B * O, -1))
-                if row_scale is not None:
-                    plan.tplt_feat.mul_(row_scale[:, :, None])
-                if row_scale is not None:
-                    plan.row_scale_buf.copy_(row_scale)
-                plan.row_scale = plan.row_scale_buf if row_scale is not None else None
-                plan.n_tplt.copy_(_lib.small_to_device(n_tplt, torch.int32, dev))
-                rows = [[[0 if (n <= tt or n_tplt[b] == 0) else n_tplt[b] for b, n in enumerate(n_frames)],
-                         [0 if (tt == 0 or n <= tt or n_tplt[b] == 0) else 1 for b, n in enumerate(n_frames)]]
-                        for tt in range(T)]
-                plan.tables[:T].copy_(_lib.small_to_device(rows, torch.int32, dev))
+                    g1 = self._first_chunk(next_frames.shape[1], True)
+                    self._prefetched = ((next_frames, next_frames._version, g1, enc_side),
+                                        self._encode_chunk(next_frames, 0, g1, **enc)[0])
+            if t == 0:
+                tplt_valid = self._set_templates(plan, y0, n_frames, T)
             plan.run_step(self.graph)
             if it_all is not None:
                 it_all[t].copy_(plan.out[3])
             if self.refine is not None:
-                features = chunk if chunks[kc][1] == 1 else _slice_batch(chunk, j * B, (j + 1) * B)
                 live = plan.cur[0] > 0
                 out_last = torch.where(live[:, None, None, None], plan.full, plan.hist)
                 zeros = first_masks.new_zeros((B, O, H * W), dtype=torch.float32) if y_mask is None else y_mask
-                outs, hist_new, state = self.refine(features, prev_mask, zeros, plan.full, out_last, tplt_valid, state)
+                outs, hist_new, state = self.refine(_frame_features(chunk, g, t - t0, B), prev_mask, zeros, plan.full,
+                                                    out_last, tplt_valid, state)
                 if t > 0:
-                    plan.hist.copy_(hist_new.view(B, O, H, W))
-                    if plan.fused:
-                        from . import ops
-                        plan.packed_hist.copy_(ops.pack_masks(plan.hist))
+                    plan.set_history(hist_new)
                 outs = outs.reshape(B, O, H * W)
             else:
                 outs = plan.full.view(B, O, H * W)
-            if t == 0:                                                   # frame 0 only warms the decoder state, :119-128
-                outs = y0
-            hist_all[t].copy_(outs)
+            hist_all[t].copy_(_reported(t, outs, y0))
             prev_mask = hist_all[t]
             if on_labels is not None:
                 if t == 0 or self.refine is not None:
                     lab_all[t].copy_(merge_labels(hist_all[t].view(B, O, H, W), tplt_valid))
                 else:
                     lab_all[t].copy_(plan.labels.view(B, H, W))
-                for b in range(B):
-                    if not extra[b]:
-                        on_labels(b, t, lab_all[t, b])
+                _emit_labels(on_labels, t, lab_all[t], extra)
             history.append(hist_all[t])
         self.last_iters = it_all
-        if cfg[5] == "hun" and not torch.cuda.is_current_stream_capturing():
-            # the clip's assignment statuses, one read: scipy's ValueError for a NaN / infeasible cost table
-            st = plan.status_all[:T].cpu()
-            bad = torch.nonzero(st)
-            if bad.numel():
-                t, b = (int(v) for v in bad[0])
-                from .ops import _LSAP_MESSAGES
-                raise ValueError(f"{_LSAP_MESSAGES.get(int(st[t, b]), 'linear_sum_assignment failed')} "
-                                 f"(video {b}, frame {t})")
+        plan.raise_on_status(T)
         return history
 
-    # model_encoder.py:115-134
+    # ---- BoxList path (prepare_proposals: model_encoder.py:115-134) --------------------------------------------------
     def prepare_proposals(self, raw: Sequence, im_h: int, im_w: int, device):
         props = []
         for p in raw:
@@ -686,6 +713,23 @@ class FrameLoop:
                                       want_packed=True)
         score_field = "scores" if "scores" in props[0].fields() else "objectness"
         return filter_results(list(props), self.nms_thresh, self.max_proposals, score_field)
+
+    def _init_templates(self, features, y0, shape):
+        """forward_timestep_init (evaluator.py:215-225) -> (tplt_dict, tplt_valid, n_tplt, row_scale)."""
+        B, O, H, W = shape
+        tpl, valid = zip(*(ohw_mask2boxlist(y0[b].view(O, H, W)) for b in range(B)))
+        tplt_valid = torch.stack(valid, 0)
+        # once per clip (the templates are fixed): live counts + the non-prefix row scale of the reference's
+        # OF_matrix (an object that is empty in frame 0 leaves a hole in the valid slots)
+        n_tplt, row_scale = self.dmm._valid_layout(tplt_valid)
+        tplt_dict = self.dmm.fill_template_dict(None, list(tpl), features, y0, tplt_valid)
+        if getattr(self.encoder, "static_outputs", False):
+            # a GraphedEncoder returns views of its graph's static buffers; every later replay overwrites
+            # them, so what the template dictionary keeps across frames must own its memory
+            for b in tplt_dict:
+                tplt_dict[b]["refine_input_feat"] = [tuple(f.clone() for f in tup)
+                                                     for tup in tplt_dict[b]["refine_input_feat"]]
+        return tplt_dict, tplt_valid, n_tplt, row_scale
 
     @torch.no_grad()
     def run(self, frames: torch.Tensor, first_masks: torch.Tensor, proposals: Sequence[Sequence],
@@ -702,13 +746,12 @@ class FrameLoop:
         encoder that nothing overlaps: a quarter of a 12-frame clip's time).  Results are unchanged; a later ``run`` on
         other frames simply ignores the prefetch."""
         B, T, C, H, W = frames.shape
-        O = first_masks.shape[1]
-        dev = frames.device
+        O, dev = first_masks.shape[1], frames.device
         n_frames = list(n_frames) if n_frames is not None else [T] * B
-        if self._slots_ok(frames, proposals, O):
-            return self._run_slots(frames, first_masks, proposals, n_frames, targets, on_labels, next_frames)
+        key = self._slots_key(frames, proposals, O)
+        if key is not None:
+            return self._run_slots(key, frames, first_masks, proposals, n_frames, targets, on_labels, next_frames)
         history, state, mask_hist = [], None, None
-        tplt_dict = tplt_valid = prev_mask = n_tplt = row_scale = None
         # Proposal look-ahead.  A frame's proposals (paste, tight boxes, NMS, top-k) depend on nothing the loop computes,
         # and their NMS ends in the step's only host sync (the kept counts).  On the main stream that sync drained
         # the whole step and the GPU idled while the host enqueued the next one; here the proposals of frame t + 1 are
@@ -729,84 +772,44 @@ class FrameLoop:
                             v.record_stream(main)
                 return out, side.record_event()
 
-        G = max(1, min(self._frames_per_chunk(T), T))
+        # The encoder has no temporal state (the templates and the decoder carry it), so `encode_ahead` frames of
+        # the clip go through it as ONE batch, time-major: G x B images per launch sequence instead of B -- the
+        # ResNet at 4 x 255 x 448 is launch bound (~90 kernels of 5-20 us), at 16-48 images it is not.
+        # `encode_overlap`: the chunk AFTER this one is encoded on its own stream while this chunk's steps -- a
+        # dependent chain of small kernels that leaves most of the chip idle -- run on the main stream.
+        chunks, chunk_of, _ = self._schedule(T, boxlist=True)
         enc_side = self._side_stream(dev, "encoder") if main is not None and self.encode_overlap else None
-
-        def encode(t0):
-            g = min(G, T - t0)
-
-            def go():
-                xs = frames[:, t0] if g == 1 else frames[:, t0:t0 + g].transpose(0, 1).reshape(g * B, C, H, W)
-                return self.encoder(xs)
-            if enc_side is None:
-                out = go()
-                if getattr(self.encoder, "static_outputs", False):
-                    # views of a graph's static buffers: the NEXT chunk is encoded (same graph, same buffers) as soon as
-                    # this one has been taken, i.e. before its steps are enqueued -- they must not alias the buffers
-                    out = _map_tensors(out, lambda v: v.clone())
-                return out, None
-            with torch.cuda.stream(enc_side):
-                out = go()
-                if getattr(self.encoder, "static_outputs", False):
-                    # views of a graph's static buffers: the next replay (issued while this chunk is still in use)
-                    # would overwrite them
-                    out = _map_tensors(out, lambda v: v.clone())
-                _map_tensors(out, lambda v: (v.record_stream(main), v)[1])
-                return out, enc_side.record_event()
-
+        # The steps read the encoder's outputs themselves, and the next chunk is encoded as soon as this one has been taken:
+        # a static encoder's outputs are always cloned.  The steps wait for the chunk: the event is taken after encoding.
+        enc = dict(main=main, enc_side=enc_side, clone_static=True, fence_on_main=False)
         if side is not None:
             side.wait_stream(main)                               # inputs the caller produced on the main stream
         if enc_side is not None:
             enc_side.wait_stream(main)
         ahead = prepare(0) if T > 0 else None
-        next_chunk = encode(0) if T > 0 else None
+        next_chunk = self._encode_chunk(frames, *chunks[0], **enc) if T > 0 else None
+        prev_mask = y0 = first_masks.float().view(B, O, H * W)
         for t in range(T):
-            extra = [n <= t for n in n_frames]
-            x = frames[:, t]
-            if t == 0:
-                y_mask = first_masks.float().view(B, O, H * W)
-            elif targets is not None:
-                y_mask = targets[:, t].float().view(B, O, H * W)
-            else:
+            extra, y_mask = _frame_inputs(t, y0, targets, n_frames)
+            if y_mask is None:
                 y_mask = first_masks.new_zeros((B, O, H * W), dtype=torch.float32)
             props, ready = ahead
             if ready is not None:
                 main.wait_event(ready)
-            # The encoder has no temporal state (the templates and the decoder carry it), so `encode_ahead` frames of
-            # the clip go through it as ONE batch, time-major: G x B images per launch sequence instead of B -- the
-            # ResNet at 4 x 255 x 448 is launch bound (~90 kernels of 5-20 us), at 16-48 images it is not.
-            # `encode_overlap`: the chunk AFTER this one is encoded on its own stream while this chunk's steps -- a
-            # dependent chain of small kernels that leaves most of the chip idle -- run on the main stream.
-            if t % G == 0:
+            kc = chunk_of[t]
+            t0, g = chunks[kc]
+            if t == t0:                                          # a chunk's first frame: take it, issue the one after it
                 chunk, enc_ready = next_chunk
                 if enc_ready is not None:
                     main.wait_event(enc_ready)
-                if t + G < T:
-                    next_chunk = encode(t + G)
-            j = t % G
-            features = chunk if min(G, T - (t - j)) == 1 else _slice_batch(chunk, j * B, (j + 1) * B)
-            if t == 0:                                                   # forward_timestep_init, :215-225
-                tpl, valid = [], []
-                for b in range(B):
-                    bl, v = ohw_mask2boxlist(y_mask[b].view(O, H, W))
-                    tpl.append(bl)
-                    valid.append(v)
-                tplt_valid = torch.stack(valid, 0)
-                # once per clip (the templates are fixed): live counts + the non-prefix row scale of the reference's
-                # OF_matrix (an object that is empty in frame 0 leaves a hole in the valid slots)
-                n_tplt, row_scale = self.dmm._valid_layout(tplt_valid)
-                tplt_dict = self.dmm.fill_template_dict(None, tpl, features, y_mask, tplt_valid)
-                if getattr(self.encoder, "static_outputs", False):
-                    # a GraphedEncoder returns views of its graph's static buffers; every later replay overwrites
-                    # them, so what the template dictionary keeps across frames must own its memory
-                    for b in tplt_dict:
-                        tplt_dict[b]["refine_input_feat"] = [tuple(f.clone() for f in tup)
-                                                             for tup in tplt_dict[b]["refine_input_feat"]]
-                prev_mask = y_mask
+                if kc + 1 < len(chunks):
+                    next_chunk = self._encode_chunk(frames, *chunks[kc + 1], **enc)
+            features = _frame_features(chunk, g, t - t0, B)
+            if t == 0:
+                tplt_dict, tplt_valid, n_tplt, row_scale = self._init_templates(features, y0, (B, O, H, W))
+            # alias_ok: nothing here edits init_pred / hist_new in place; a decoder may (evaluator.py:205): its own tensor
             infos = {"extra_frame": extra, "valid": tplt_valid, "shape": [[H, W]] * B, "n_tplt": n_tplt,
-                     "row_scale": row_scale,
-                     "alias_ok": self.refine is None}             # nothing here edits init_pred / hist_new in place; a
-                                                                  # decoder may (evaluator.py:205): it gets its own tensor
+                     "row_scale": row_scale, "alias_ok": self.refine is None}
             hist_in = prev_mask.view(B, O, H, W) if mask_hist is None else mask_hist       # :168-169
             init_pred, tplt_dict, _, hist_new = self.dmm.inference(infos, props, features["backbone_feature"], hist_in,
                                                                    tplt_dict)
@@ -814,16 +817,12 @@ class FrameLoop:
                 outs, hist_new, state = self.refine(features, prev_mask, y_mask, init_pred, hist_new, tplt_valid, state)
             else:
                 outs = init_pred.reshape(B, O, H * W)
-            if t == 0:                                                   # frame 0 only warms the decoder state, :119-128
-                outs = y_mask
-            else:
+            outs = _reported(t, outs, y0)
+            if t > 0:
                 mask_hist = hist_new
             prev_mask = outs.view(B, O, H * W)
             if on_labels is not None:
-                labels = merge_labels(outs.view(B, O, H, W), tplt_valid)
-                for b in range(B):
-                    if not extra[b]:
-                        on_labels(b, t, labels[b])
+                _emit_labels(on_labels, t, merge_labels(outs.view(B, O, H, W), tplt_valid), extra)
             history.append(outs)
             if t + 1 < T:
                 ahead = prepare(t + 1)                           # host sync inside: frame t's work is already queued

@@ -255,7 +255,8 @@ def test_frame_loop_fixed_slots_and_graph_equal_boxlist_path_without_host_syncs(
 
     ref_h, ref_l = run(make(False, False))
     for (slots, graph, kn) in [(True, False, {}), (True, True, {}), (True, True, dict(encode_ahead=1, encode_overlap=False)),
-                               (True, True, dict(encode_ahead=3)), (True, True, dict(fuse_epilogue=False)),
+                               (True, True, dict(encode_ahead=3)), (True, True, dict(encode_ahead=3, encode_first=2)),
+                               (True, True, dict(fuse_epilogue=False)),
                                (True, False, dict(fuse_epilogue=False, encode_ahead=2))]:
         lp = make(slots, graph, **kn)
         for rep in range(3):                                             # replays of the captured step; races

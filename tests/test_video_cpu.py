@@ -141,6 +141,118 @@ def test_frame_loop_chunk_sizes_by_clip_length_and_mode():
     assert lp._prefetched is None
 
 
+@pytest.mark.parametrize("encode_first", [0, 2])
+@pytest.mark.parametrize("encode_ahead", [0, 1, 3])
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_frame_loop_schedule_tiles_the_clip(pipelined, encode_ahead, encode_first):
+    """``FrameLoop._schedule``: chunks of at most G frames that tile [0, T) in order, ``chunk_of`` consistent with them,
+    the fixed-slot form starting with ``_first_chunk`` frames, the BoxList form uniform whatever ``encode_first`` says."""
+    lp = video.FrameLoop(encoder=lambda x: None, dmm=None)
+    lp.encode_ahead, lp.encode_first = encode_ahead, encode_first
+    for T in (1, 2, 5, 6, 12, 36):
+        for boxlist in (False, True):
+            chunks, chunk_of, G = lp._schedule(T, pipelined, boxlist=boxlist)
+            assert G == max(1, min(lp._frames_per_chunk(T, pipelined), T))
+            assert chunks[0][0] == 0 and sum(g for _, g in chunks) == T
+            assert all(a[0] + a[1] == b[0] for a, b in zip(chunks, chunks[1:]))        # in order, no gap, no overlap
+            assert all(1 <= g <= G for _, g in chunks)
+            assert len(chunk_of) == T and all(chunks[k][0] <= t < sum(chunks[k]) for t, k in enumerate(chunk_of))
+            if boxlist:
+                lp.encode_first = 0
+                assert lp._schedule(T, pipelined, boxlist=True).chunks == chunks     # encode_first is ignored ...
+                lp.encode_first = encode_first
+                assert [g for _, g in chunks[:-1]] == [G] * (len(chunks) - 1)           # ... the chunks are uniform
+            else:
+                assert chunks[0][1] == lp._first_chunk(T, pipelined)
+                assert [g for _, g in chunks[1:-1]] == [G] * len(chunks[1:-1])
+    if encode_ahead == 3 and encode_first == 2:                             # the case the GPU test runs at T = 6
+        assert lp._schedule(6, pipelined).chunks == [(0, 2), (2, 3), (5, 1)]
+        assert lp._schedule(6, pipelined, boxlist=True).chunks == [(0, 3), (3, 3)]
+
+
+def test_frame_loop_img_base_rows_keep_neighbouring_chunks_apart():
+    """``img_base_rows``: every frame of chunk k addresses half k % 2 of the feature batch [2 * G * B, ..], inside it; a
+    frame of chunk k and a frame of chunk k + 1 (live at the same time: k + 1 lands while k's steps run) share no row."""
+    lp = video.FrameLoop(encoder=lambda x: None, dmm=None)
+    for B in (1, 3):
+        for ea, ef, pipelined in [(0, 0, False), (0, 0, True), (1, 0, False), (3, 2, False), (3, 0, True), (5, 1, False)]:
+            lp.encode_ahead, lp.encode_first = ea, ef
+            for T in (1, 2, 5, 6, 12, 36):
+                sched = lp._schedule(T, pipelined)
+                rows = video.img_base_rows(sched, B)
+                assert len(rows) == T
+                span = [set(range(r, r + B)) for r in rows]
+                for t, k in enumerate(sched.chunk_of):
+                    half = (k % 2) * sched.G * B
+                    assert half <= rows[t] and rows[t] + B <= half + sched.G * B <= 2 * sched.G * B
+                    assert rows[t] == half + (t - sched.chunks[k][0]) * B
+                    for u, ku in enumerate(sched.chunk_of):
+                        if u != t and ku in (k, k + 1):
+                            assert not (span[t] & span[u]), (B, ea, ef, T, t, u)
+
+
+def test_frame_loop_step_tables_skip_ended_and_empty_videos():
+    """``step_tables``: m_valid is the video's live template count until the video ends and 0 from there on, and 0
+    everywhere for a video without templates; commit is 0 in frame 0 and 1 wherever m_valid > 0 after it."""
+    n_frames, n_tplt, T = [6, 3, 5], [2, 0, 3], 6
+    tab = video.step_tables(n_frames, n_tplt, T)
+    assert torch.tensor(tab).shape == (T, 2, 3)
+    for t in range(T):
+        for b in range(3):
+            m_valid, commit = tab[t][0][b], tab[t][1][b]
+            assert m_valid == (n_tplt[b] if t < n_frames[b] else 0)
+            assert commit == (1 if (t > 0 and m_valid > 0) else 0)
+    assert all(tab[t][0][1] == 0 and tab[t][1][1] == 0 for t in range(T))      # the video without templates
+    assert [tab[t][0][2] for t in range(T)] == [3, 3, 3, 3, 3, 0] and [tab[t][1][0] for t in range(T)] == [0, 1, 1, 1, 1, 1]
+
+
+def test_frame_loop_step_key_holds_every_immediate_of_the_captured_step():
+    """``FrameLoop._step_key``: equal settings give equal keys; each of nms_thresh, mask_thresh, padding, the solver's
+    max_iter, the algorithm and fuse_epilogue moves it; ``fused`` follows ONE rule, at its boundaries (8 / 9 template
+    slots, raw mask + 2 * padding 32 / 33); a plan is found again by its key."""
+    from dmm_net_amd.proposals import ClipProposals
+
+    def make():
+        ml = types.SimpleNamespace(cfgs={"score_weight": 0.3}, max_iter=40, proj_iter=5, relax_lr=0.1, is_test=1)
+        return video.FrameLoop(encoder=lambda x: None, dmm=types.SimpleNamespace(match_layer=ml, match_algo="relax"),
+                               nms_thresh=0.4, max_proposals=20)
+
+    def key(lp, O=5, M=28, G=3):
+        return lp._step_key(3, O, 96, 128, ClipProposals.empty(6, 3, 30, M, "cpu"), G)
+    base = key(make())
+    assert base == key(make()) and hash(base) == hash(key(make()))
+    assert (base.R, base.Mm, base.K, base.G, base.tail, base.fused, base.cfg[5]) == (30, 28, 20, 3, True, True, "relax")
+    changes = [lambda lp: setattr(lp, "nms_thresh", 0.05), lambda lp: setattr(lp, "mask_thresh", 0.7),
+               lambda lp: setattr(lp, "padding", 2), lambda lp: setattr(lp.dmm.match_layer, "max_iter", 3),
+               lambda lp: setattr(lp.dmm, "match_algo", "hun"), lambda lp: setattr(lp, "fuse_epilogue", False)]
+    for change in changes:
+        lp = make()
+        change(lp)
+        assert key(lp) != base
+    assert key(make(), G=4) != base and base._replace(G=4) == key(make(), G=4)
+    # nested BoxLists give the key of the same clip as a ClipProposals; lists without raw masks give none
+    bl = SimpleBoxList(torch.zeros(30, 4), (128, 96))
+    bl.add_field("mask", torch.zeros(30, 1, 28, 28))
+    short = SimpleBoxList(torch.zeros(7, 4), (128, 96))
+    short.add_field("mask", torch.zeros(7, 1, 28, 28))
+    assert make()._step_key(3, 5, 96, 128, [[bl, short], [short], [short]], 3) == base
+    assert make()._step_key(3, 5, 96, 128, [[bl, SimpleBoxList(torch.zeros(2, 4), (128, 96))]], 3) is None
+    assert make()._step_key(3, 5, 96, 128, [[], []], 3) is None
+    # the one rule for the fused epilogue
+    lp = make()
+    assert key(lp, O=8).fused and not key(lp, O=9).fused
+    assert key(lp, M=30).fused and not key(lp, M=31).fused                    # padding 1: 32 / 33
+    lp.padding = 2
+    assert key(lp, M=28).fused and not key(lp, M=29).fused                    # padding 2: 32 / 33
+    lp.fuse_epilogue = False
+    assert not key(lp, O=8, M=28).fused
+    # 'hun' runs on the fixed slots in the fused form only; the envelope is the key's own test
+    lp = make()
+    lp.dmm.match_algo = "hun"
+    assert key(lp).runs_on_slots() and not key(lp, O=9).runs_on_slots() and key(make(), O=9).runs_on_slots()
+    assert not key(make(), O=33).runs_on_slots() and not key(make(), M=63).runs_on_slots()
+
+
 def test_oracle_clip_chain_carries_the_history_and_skips_like_the_reference():
     """tests/clip_oracle.py (the CPU clip the GPU frame loop is compared with): frame 0 reports the annotation, a video
     without templates or past its length yields zeros and keeps its history, the template history of frame t feeds
