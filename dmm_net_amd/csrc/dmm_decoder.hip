@@ -11,6 +11,8 @@
 // For training on the fused form: the backward of the cell (12e), which recomputes the gates, and its fixed-order fold; and
 // what the refine step of training (dmm/modules/trainer.py:236-306) runs around the decoder: the backward of the pyramid (12f),
 // the backward of the upsample in 'write' mode (12g), the trainer's nearest / sigmoid / pad finish and its backward (12h).
+// The backward of the cell, of the upsample and the trainer's finish are templates over the activations' storage type as well:
+// their bf16 instantiations are (12l)-(12o), the bf16 training form.  The pyramid and its backward are fp32 only.
 #include "dmm_common.h"
 
 #include <math.h>
@@ -174,15 +176,17 @@ __global__ __launch_bounds__(256) void clstm_gates_kernel(
 //   d_w_mask  36 sums per channel over the workgroup's 256 positions (planes in evaluation order inside the lane, the
 //             64-lane tree of wave_sum_rows, the four waves in order through LDS) go to ws_w [position blocks][4 * Hd * 9];
 //             the fold adds the position blocks in ascending order.
-// Lanes past the last position hold ds = 0 and take part in the wave sums.
+// Lanes past the last position hold ds = 0 and take part in the wave sums.  T: the storage of the addends, of d_hidden and of
+// d_pre (12l), as in the forward; the gradient arithmetic, the tap sums and both reductions are fp32 in either form, so the
+// fold kernel is shared.
 __device__ __forceinline__ int eval_plane(int e) { return e == 0 ? 0 : (e == 1 ? 2 : 1); }
 
-template <bool WANT_M, bool WANT_W>
+template <typename T, bool WANT_M, bool WANT_W>
 __global__ __launch_bounds__(256) void clstm_gates_bwd_kernel(
-    const float *__restrict__ pre0, const float *__restrict__ pre1, const float *__restrict__ pre2, int64_t sb0, int64_t sb1,
+    const T *__restrict__ pre0, const T *__restrict__ pre1, const T *__restrict__ pre2, int64_t sb0, int64_t sb1,
     int64_t sb2, const float *__restrict__ masks, int64_t sb_m, const float *__restrict__ wm, const float *__restrict__ c_prev,
-    const float *__restrict__ d_hidden, const float *__restrict__ d_cell, int B, int Hd, int h, int w,
-    float *__restrict__ d_pre, float *__restrict__ d_cprev, float *__restrict__ ws_m, float *__restrict__ ws_w) {
+    const T *__restrict__ d_hidden, const float *__restrict__ d_cell, int B, int Hd, int h, int w,
+    T *__restrict__ d_pre, float *__restrict__ d_cprev, float *__restrict__ ws_m, float *__restrict__ ws_w) {
     __shared__ float s_w[WANT_W ? kGateCh * 4 * 36 : 1];
     __shared__ float s_wm[kGateCh * 36];               // the group's stencil weights: read as vector operands (36 wave-uniform
     const int hw = h * w;                              // scalars per channel, on top of twelve pointers, do not fit the SGPRs)
@@ -225,14 +229,14 @@ __global__ __launch_bounds__(256) void clstm_gates_bwd_kernel(
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int64_t off = (int64_t)(q * Hd + ch) * hw + p;
-                float v = pre0[(int64_t)b * sb0 + off];
-                if (pre1) v = v + pre1[(int64_t)b * sb1 + off];
-                if (pre2) v = v + pre2[(int64_t)b * sb2 + off];
+                float v = act_load(pre0 + (int64_t)b * sb0 + off);
+                if (pre1) v = v + act_load(pre1 + (int64_t)b * sb1 + off);
+                if (pre2) v = v + act_load(pre2 + (int64_t)b * sb2 + off);
                 g[q] = v;
             }
             const int64_t so = ((int64_t)b * Hd + ch) * hw + p;
             const float cp = c_prev ? c_prev[so] : 0.0f;
-            const float u = d_hidden ? d_hidden[so] / 3.0f : 0.0f;
+            const float u = d_hidden ? act_load(d_hidden + so) / 3.0f : 0.0f;
             const float v = d_cell ? d_cell[so] / 3.0f : 0.0f;
             float dcr[3];
 #pragma unroll
@@ -259,7 +263,7 @@ __global__ __launch_bounds__(256) void clstm_gates_bwd_kernel(
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q)
-                d_pre[((int64_t)b * 4 * Hd + (int64_t)(q * Hd + ch)) * hw + p] = (ds[0][q] + ds[1][q]) + ds[2][q];
+                act_store(d_pre + ((int64_t)b * 4 * Hd + (int64_t)(q * Hd + ch)) * hw + p, (ds[0][q] + ds[1][q]) + ds[2][q]);
             if (d_cprev) d_cprev[so] = (dcr[0] + dcr[1]) + dcr[2];
         }
         if (WANT_M) {
@@ -547,8 +551,9 @@ __device__ __forceinline__ float touch_weight(const Lerp &r, int i) {
     return wgt;
 }
 
-__global__ __launch_bounds__(256) void upsample_bwd_kernel(const float *__restrict__ d_dst, int64_t sb_dst, int C, int H, int W,
-                                                           int c0, float *__restrict__ d_src, int64_t sb_src, int h, int w,
+template <typename T>   // the storage of d_dst and d_src (12m): the gather accumulates in fp32 and rounds once, at the store
+__global__ __launch_bounds__(256) void upsample_bwd_kernel(const T *__restrict__ d_dst, int64_t sb_dst, int C, int H, int W,
+                                                           int c0, T *__restrict__ d_src, int64_t sb_src, int h, int w,
                                                            float sy, float sx, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -560,20 +565,20 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const float *__restri
     int Y0, Y1, X0, X1;
     touch_range(y, sy, H, Y0, Y1);
     touch_range(x, sx, W, X0, X1);
-    const float *g = d_dst + (int64_t)b * sb_dst + (int64_t)(c0 + c) * H * W;
+    const T *g = d_dst + (int64_t)b * sb_dst + (int64_t)(c0 + c) * H * W;
     float acc = 0.0f;
     for (int Y = Y0; Y <= Y1; ++Y) {
         const Lerp ly = lerp_of(Y, sy, h);
         if (ly.i0 != y && ly.i0 + ly.step != y) continue;
         const float wy = touch_weight(ly, y);
-        const float *row = g + (int64_t)Y * W;
+        const T *row = g + (int64_t)Y * W;
         for (int X = X0; X <= X1; ++X) {
             const Lerp lx = lerp_of(X, sx, w);
             if (lx.i0 != x && lx.i0 + lx.step != x) continue;
-            acc = acc + (wy * touch_weight(lx, x)) * row[X];
+            acc = acc + (wy * touch_weight(lx, x)) * act_load(row + X);
         }
     }
-    d_src[(int64_t)b * sb_src + ((int64_t)c * h + y) * w + x] = acc;
+    act_store(d_src + (int64_t)b * sb_src + ((int64_t)c * h + y) * w + x, acc);
 }
 
 // ---- (12h) the finish of the training step -------------------------------------------------------------------------------
@@ -584,7 +589,8 @@ __device__ __forceinline__ int nn_index(int dst, float scale, int in) {
     return i < in - 1 ? i : in - 1;
 }
 
-__global__ __launch_bounds__(256) void refine_train_finish_kernel(const float *__restrict__ logits, int64_t sb_l, int64_t so_l,
+template <typename T>   // the storage of the logits (12n); outs is fp32 in either form
+__global__ __launch_bounds__(256) void refine_train_finish_kernel(const T *__restrict__ logits, int64_t sb_l, int64_t so_l,
                                                                   int h, int w, int O, int n_obj, int H, int W, float sy, float sx,
                                                                   float *__restrict__ outs, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -596,8 +602,8 @@ __global__ __launch_bounds__(256) void refine_train_finish_kernel(const float *_
     const int t = (int)(r % O), b = (int)(r / O);
     float v = 0.0f;
     if (t < n_obj) {
-        const float *p = logits + (int64_t)b * sb_l + (int64_t)t * so_l;
-        v = sigmoid_f32(p[(int64_t)nn_index(Y, sy, h) * w + nn_index(X, sx, w)]);
+        const T *p = logits + (int64_t)b * sb_l + (int64_t)t * so_l;
+        v = sigmoid_f32(act_load(p + (int64_t)nn_index(Y, sy, h) * w + nn_index(X, sx, w)));
     }
     outs[i] = v;
 }
@@ -614,10 +620,11 @@ __device__ __forceinline__ void nn_block(int i, float scale, int in, int out, in
     while (hi >= lo && nn_index(hi, scale, in) != i) --hi;
 }
 
-__global__ __launch_bounds__(256) void refine_train_finish_bwd_kernel(const float *__restrict__ logits, int64_t sb_l, int64_t so_l,
+template <typename T>   // the storage of the logits and of d_logits (12o); d_outs is fp32, the block sum and the product too
+__global__ __launch_bounds__(256) void refine_train_finish_bwd_kernel(const T *__restrict__ logits, int64_t sb_l, int64_t so_l,
                                                                       int h, int w, const float *__restrict__ d_outs, int O,
                                                                       int n_obj, int H, int W, float sy, float sx,
-                                                                      float *__restrict__ d_logits, int64_t sb_d, int64_t so_d,
+                                                                      T *__restrict__ d_logits, int64_t sb_d, int64_t so_d,
                                                                       int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -633,8 +640,8 @@ __global__ __launch_bounds__(256) void refine_train_finish_bwd_kernel(const floa
     float acc = 0.0f;
     for (int Y = Y0; Y <= Y1; ++Y)
         for (int X = X0; X <= X1; ++X) acc = acc + g[(int64_t)Y * W + X];
-    const float p = sigmoid_f32(logits[(int64_t)b * sb_l + (int64_t)t * so_l + (int64_t)y * w + x]);
-    d_logits[(int64_t)b * sb_d + (int64_t)t * so_d + (int64_t)y * w + x] = (p * (1.0f - p)) * acc;
+    const float p = sigmoid_f32(act_load(logits + (int64_t)b * sb_l + (int64_t)t * so_l + (int64_t)y * w + x));
+    act_store(d_logits + (int64_t)b * sb_d + (int64_t)t * so_d + (int64_t)y * w + x, (p * (1.0f - p)) * acc);
 }
 
 // ---- the entries of the three templated kernels: one check and one launch for both storage types --------------------------
@@ -692,6 +699,87 @@ static int refine_finish_entry(const T *logits, int64_t sb_logits, int64_t so_lo
     return check_launch();
 }
 
+template <typename T>
+static int clstm_gates_bwd_entry(const T *pre0, const T *pre1, const T *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                 const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                 int hidden_size, int h, int w, const T *d_hidden, const float *d_cell, T *d_pre,
+                                 float *d_cell_prev, float *d_masks, float *d_w_mask, void *ws, size_t ws_bytes,
+                                 dmm_stream_t stream) {
+    if (B < 0 || hidden_size <= 0 || h <= 0 || w <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0) return DMM_OK;
+    if (!pre0 || !masks || !w_mask || !d_pre || (!d_hidden && !d_cell) || (d_cell_prev && !cell_prev)) return DMM_ERR_BAD_ARG;
+    const int64_t hw = (int64_t)h * w;
+    if (sb0 < 0 || sb1 < 0 || sb2 < 0 || sb_masks < 3 * hw) return DMM_ERR_BAD_ARG;
+    const bool reduce = d_masks || d_w_mask;
+    if (reduce && !ws) return DMM_ERR_BAD_ARG;
+    const int64_t blocks = ((int64_t)B * hw + 255) / 256, groups = (hidden_size + kGateCh - 1) / kGateCh;
+    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return DMM_ERR_UNSUPPORTED;
+    if (reduce && ws_bytes < dmm_clstm_gates_bwd_workspace_bytes(B, hidden_size, h, w)) return DMM_ERR_WORKSPACE;
+    float *ws_m = (float *)ws, *ws_w = reduce ? ws_m + groups * B * 27 * hw : nullptr;
+#define DMM_GATES_BWD(M_, W_)                                                                                              \
+    hipLaunchKernelGGL((clstm_gates_bwd_kernel<T, M_, W_>), dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,        \
+                       (hipStream_t)stream, pre0, pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, d_hidden, \
+                       d_cell, B, hidden_size, h, w, d_pre, d_cell_prev, ws_m, ws_w)
+    if (d_masks && d_w_mask) DMM_GATES_BWD(true, true);
+    else if (d_masks) DMM_GATES_BWD(true, false);
+    else if (d_w_mask) DMM_GATES_BWD(false, true);
+    else DMM_GATES_BWD(false, false);
+#undef DMM_GATES_BWD
+    int rc = check_launch();
+    if (rc != DMM_OK || !reduce) return rc;
+    const unsigned blocks_m = d_masks ? (unsigned)(((int64_t)B * 3 * hw + 255) / 256) : 0u;
+    const unsigned blocks_w = d_w_mask ? (unsigned)((36 * hidden_size + 255) / 256) : 0u;
+    hipLaunchKernelGGL(clstm_gates_bwd_fold_kernel, dim3(blocks_m + blocks_w), dim3(256), 0, (hipStream_t)stream, ws_m, ws_w,
+                       B, hidden_size, h, w, (int)groups, (int)blocks, blocks_m, d_masks, d_w_mask);
+    return check_launch();
+}
+
+template <typename T>
+static int upsample_bwd_entry(const T *d_dst, int64_t sb_dst, int B, int C, int H, int W, int C_dst, int c0, T *d_src,
+                              int64_t sb_src, int h, int w, dmm_stream_t stream) {
+    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C_dst <= 0) return DMM_ERR_BAD_ARG;
+    if (c0 < 0 || c0 + C > C_dst) return DMM_ERR_BAD_ARG;                            // the channel range lies inside d_dst
+    if (H < h || W < w) return DMM_ERR_UNSUPPORTED;                                  // the gather ranges assume out >= in
+    if (B == 0) return DMM_OK;
+    if (!d_dst || !d_src) return DMM_ERR_BAD_ARG;
+    if (sb_src < (int64_t)C * h * w || sb_dst < (int64_t)C_dst * H * W) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * C * h * w, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(upsample_bwd_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_dst, sb_dst, C, H, W,
+                       c0, d_src, sb_src, h, w, ac_scale(h, H), ac_scale(w, W), n);
+    return check_launch();
+}
+
+template <typename T>
+static int refine_train_finish_entry(const T *logits, int64_t sb_logits, int64_t so_logits, int h, int w, int B, int O, int n_obj,
+                                     int H, int W, float *outs, dmm_stream_t stream) {
+    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || O == 0) return DMM_OK;
+    if (!outs || (n_obj > 0 && !logits)) return DMM_ERR_BAD_ARG;
+    if (sb_logits < 0 || so_logits < 0) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * O * H * W, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(refine_train_finish_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
+                       sb_logits, so_logits, h, w, O, n_obj, H, W, nn_scale(h, H), nn_scale(w, W), outs, n);
+    return check_launch();
+}
+
+template <typename T>
+static int refine_train_finish_bwd_entry(const T *logits, int64_t sb_logits, int64_t so_logits, int h, int w, const float *d_outs,
+                                         int B, int O, int n_obj, int H, int W, T *d_logits, int64_t sb_d, int64_t so_d,
+                                         dmm_stream_t stream) {
+    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
+    if (B == 0 || n_obj == 0) return DMM_OK;
+    if (!logits || !d_outs || !d_logits) return DMM_ERR_BAD_ARG;
+    if (sb_logits < 0 || so_logits < 0 || sb_d < 0 || so_d < (int64_t)h * w) return DMM_ERR_BAD_ARG;
+    const int64_t n = (int64_t)B * n_obj * h * w, blocks = (n + 255) / 256;
+    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(refine_train_finish_bwd_kernel<T>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
+                       sb_logits, so_logits, h, w, d_outs, O, n_obj, H, W, nn_scale(h, H), nn_scale(w, W), d_logits,
+                       sb_d, so_d, n);
+    return check_launch();
+}
+
 }  // namespace dmm
 
 extern "C" int dmm_mask_pyramid_f32(const float *prev_mask, const float *y_mask, const float *init_pred, int64_t sb_prev,
@@ -742,33 +830,19 @@ extern "C" int dmm_clstm_gates_bwd_f32(const float *pre0, const float *pre1, con
                                        const float *cell_prev, int B, int hidden_size, int h, int w, const float *d_hidden,
                                        const float *d_cell, float *d_pre, float *d_cell_prev, float *d_masks, float *d_w_mask,
                                        void *ws, size_t ws_bytes, dmm_stream_t stream) {
-    if (B < 0 || hidden_size <= 0 || h <= 0 || w <= 0) return DMM_ERR_BAD_ARG;
-    if (B == 0) return DMM_OK;
-    if (!pre0 || !masks || !w_mask || !d_pre || (!d_hidden && !d_cell) || (d_cell_prev && !cell_prev)) return DMM_ERR_BAD_ARG;
-    const int64_t hw = (int64_t)h * w;
-    if (sb0 < 0 || sb1 < 0 || sb2 < 0 || sb_masks < 3 * hw) return DMM_ERR_BAD_ARG;
-    const bool reduce = d_masks || d_w_mask;
-    if (reduce && !ws) return DMM_ERR_BAD_ARG;
-    const int64_t blocks = ((int64_t)B * hw + 255) / 256, groups = (hidden_size + dmm::kGateCh - 1) / dmm::kGateCh;
-    if ((int64_t)B * hw > 0x7fffffffLL || groups > 65535) return DMM_ERR_UNSUPPORTED;
-    if (reduce && ws_bytes < dmm_clstm_gates_bwd_workspace_bytes(B, hidden_size, h, w)) return DMM_ERR_WORKSPACE;
-    float *ws_m = (float *)ws, *ws_w = reduce ? ws_m + groups * B * 27 * hw : nullptr;
-#define DMM_GATES_BWD(M_, W_)                                                                                              \
-    hipLaunchKernelGGL((dmm::clstm_gates_bwd_kernel<M_, W_>), dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0,      \
-                       (hipStream_t)stream, pre0, pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, d_hidden, \
-                       d_cell, B, hidden_size, h, w, d_pre, d_cell_prev, ws_m, ws_w)
-    if (d_masks && d_w_mask) DMM_GATES_BWD(true, true);
-    else if (d_masks) DMM_GATES_BWD(true, false);
-    else if (d_w_mask) DMM_GATES_BWD(false, true);
-    else DMM_GATES_BWD(false, false);
-#undef DMM_GATES_BWD
-    int rc = dmm::check_launch();
-    if (rc != DMM_OK || !reduce) return rc;
-    const unsigned blocks_m = d_masks ? (unsigned)(((int64_t)B * 3 * hw + 255) / 256) : 0u;
-    const unsigned blocks_w = d_w_mask ? (unsigned)((36 * hidden_size + 255) / 256) : 0u;
-    hipLaunchKernelGGL(dmm::clstm_gates_bwd_fold_kernel, dim3(blocks_m + blocks_w), dim3(256), 0, (hipStream_t)stream, ws_m, ws_w,
-                       B, hidden_size, h, w, (int)groups, (int)blocks, blocks_m, d_masks, d_w_mask);
-    return dmm::check_launch();
+    return dmm::clstm_gates_bwd_entry<float>(pre0, pre1, pre2, sb0, sb1, sb2, masks, sb_masks, w_mask, cell_prev, B, hidden_size, h,
+                                             w, d_hidden, d_cell, d_pre, d_cell_prev, d_masks, d_w_mask, ws, ws_bytes, stream);
+}
+
+extern "C" int dmm_clstm_gates_bwd_bf16(const void *pre0, const void *pre1, const void *pre2, int64_t sb0, int64_t sb1,
+                                        int64_t sb2, const float *masks, int64_t sb_masks, const float *w_mask,
+                                        const float *cell_prev, int B, int hidden_size, int h, int w, const void *d_hidden,
+                                        const float *d_cell, void *d_pre, float *d_cell_prev, float *d_masks, float *d_w_mask,
+                                        void *ws, size_t ws_bytes, dmm_stream_t stream) {
+    typedef dmm::bf16_t T;
+    return dmm::clstm_gates_bwd_entry<T>((const T *)pre0, (const T *)pre1, (const T *)pre2, sb0, sb1, sb2, masks, sb_masks, w_mask,
+                                         cell_prev, B, hidden_size, h, w, (const T *)d_hidden, d_cell, (T *)d_pre, d_cell_prev,
+                                         d_masks, d_w_mask, ws, ws_bytes, stream);
 }
 
 extern "C" int dmm_upsample_bilinear_into_f32(const float *src, int64_t sb_src, int B, int C, int h, int w, float *dst,
@@ -817,43 +891,37 @@ extern "C" int dmm_mask_pyramid_bwd_f32(const float *prev_mask, const float *ini
 
 extern "C" int dmm_upsample_bilinear_bwd_f32(const float *d_dst, int64_t sb_dst, int B, int C, int H, int W, int C_dst, int c0,
                                              float *d_src, int64_t sb_src, int h, int w, dmm_stream_t stream) {
-    if (B < 0 || C <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C_dst <= 0) return DMM_ERR_BAD_ARG;
-    if (c0 < 0 || c0 + C > C_dst) return DMM_ERR_BAD_ARG;                            // the channel range lies inside d_dst
-    if (H < h || W < w) return DMM_ERR_UNSUPPORTED;                                  // the gather ranges assume out >= in
-    if (B == 0) return DMM_OK;
-    if (!d_dst || !d_src) return DMM_ERR_BAD_ARG;
-    if (sb_src < (int64_t)C * h * w || sb_dst < (int64_t)C_dst * H * W) return DMM_ERR_BAD_ARG;
-    const int64_t n = (int64_t)B * C * h * w, blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dmm::upsample_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d_dst, sb_dst, C, H, W,
-                       c0, d_src, sb_src, h, w, dmm::ac_scale(h, H), dmm::ac_scale(w, W), n);
-    return dmm::check_launch();
+    return dmm::upsample_bwd_entry<float>(d_dst, sb_dst, B, C, H, W, C_dst, c0, d_src, sb_src, h, w, stream);
+}
+
+extern "C" int dmm_upsample_bilinear_bwd_bf16(const void *d_dst, int64_t sb_dst, int B, int C, int H, int W, int C_dst, int c0,
+                                              void *d_src, int64_t sb_src, int h, int w, dmm_stream_t stream) {
+    typedef dmm::bf16_t T;
+    return dmm::upsample_bwd_entry<T>((const T *)d_dst, sb_dst, B, C, H, W, C_dst, c0, (T *)d_src, sb_src, h, w, stream);
 }
 
 extern "C" int dmm_refine_train_finish_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w, int B, int O,
                                            int n_obj, int H, int W, float *outs, dmm_stream_t stream) {
-    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || O == 0) return DMM_OK;
-    if (!outs || (n_obj > 0 && !logits)) return DMM_ERR_BAD_ARG;
-    if (sb_logits < 0 || so_logits < 0) return DMM_ERR_BAD_ARG;
-    const int64_t n = (int64_t)B * O * H * W, blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dmm::refine_train_finish_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
-                       sb_logits, so_logits, h, w, O, n_obj, H, W, dmm::nn_scale(h, H), dmm::nn_scale(w, W), outs, n);
-    return dmm::check_launch();
+    return dmm::refine_train_finish_entry<float>(logits, sb_logits, so_logits, h, w, B, O, n_obj, H, W, outs, stream);
+}
+
+extern "C" int dmm_refine_train_finish_bf16(const void *logits, int64_t sb_logits, int64_t so_logits, int h, int w, int B, int O,
+                                            int n_obj, int H, int W, float *outs, dmm_stream_t stream) {
+    return dmm::refine_train_finish_entry<dmm::bf16_t>((const dmm::bf16_t *)logits, sb_logits, so_logits, h, w, B, O, n_obj, H, W,
+                                                       outs, stream);
 }
 
 extern "C" int dmm_refine_train_finish_bwd_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w,
                                                const float *d_outs, int B, int O, int n_obj, int H, int W, float *d_logits,
                                                int64_t sb_d, int64_t so_d, dmm_stream_t stream) {
-    if (B < 0 || O < 0 || n_obj < 0 || n_obj > O || h <= 0 || w <= 0 || H <= 0 || W <= 0) return DMM_ERR_BAD_ARG;
-    if (B == 0 || n_obj == 0) return DMM_OK;
-    if (!logits || !d_outs || !d_logits) return DMM_ERR_BAD_ARG;
-    if (sb_logits < 0 || so_logits < 0 || sb_d < 0 || so_d < (int64_t)h * w) return DMM_ERR_BAD_ARG;
-    const int64_t n = (int64_t)B * n_obj * h * w, blocks = (n + 255) / 256;
-    if (blocks > 0x7fffffffLL) return DMM_ERR_UNSUPPORTED;
-    hipLaunchKernelGGL(dmm::refine_train_finish_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, logits,
-                       sb_logits, so_logits, h, w, d_outs, O, n_obj, H, W, dmm::nn_scale(h, H), dmm::nn_scale(w, W), d_logits,
-                       sb_d, so_d, n);
-    return dmm::check_launch();
+    return dmm::refine_train_finish_bwd_entry<float>(logits, sb_logits, so_logits, h, w, d_outs, B, O, n_obj, H, W, d_logits, sb_d,
+                                                     so_d, stream);
+}
+
+extern "C" int dmm_refine_train_finish_bwd_bf16(const void *logits, int64_t sb_logits, int64_t so_logits, int h, int w,
+                                                const float *d_outs, int B, int O, int n_obj, int H, int W, void *d_logits,
+                                                int64_t sb_d, int64_t so_d, dmm_stream_t stream) {
+    typedef dmm::bf16_t T;
+    return dmm::refine_train_finish_bwd_entry<T>((const T *)logits, sb_logits, so_logits, h, w, d_outs, B, O, n_obj, H, W,
+                                                 (T *)d_logits, sb_d, so_d, stream);
 }

@@ -18,8 +18,8 @@ Three execution forms behind the one ``forward``:
   gradients are required (unless ``fused_train`` is set, below), in ``train()`` mode with ``dropout > 0``, for
   ``kernel_size == 1``, ``prev_mask_d != 1``, non-fp32 or CPU tensors.  With the default ``fused_train = False`` training
   through the decoder works this way and is not accelerated.
-* the FUSED TRAINING form (``decoder.fused_train = True``, opt-in; HIP tensors, fp32, 3x3, a gradient required, no active
-  dropout): the algebra of the fused form below under autograd.  The convolutions (on differentiable slices of
+* the FUSED TRAINING form (``decoder.fused_train = True``, opt-in; HIP tensors, fp32 -- or the bf16 operand set of
+  ``train_dtype``, below --, 3x3, a gradient required, no active dropout): the algebra of the fused form below under autograd.  The convolutions (on differentiable slices of
   ``Gates.weight``), the bilinear upsample, ``cat`` and the 'mul' product are torch ops; the cell is ``clstm_gates_fn``:
   ``dmm_clstm_gates_f32`` forward, ``dmm_clstm_gates_bwd_f32`` backward, which recomputes the gates from the cell's inputs
   instead of keeping the forward's intermediates.  One shared convolution share per level and direction instead of three
@@ -43,7 +43,16 @@ Three execution forms behind the one ``forward``:
   convolutions run in bf16 on weights cast once (``weight_slices``), and the kernels between them are the 16-bit entries
   (include/dmm_match.h (12i)-(12k)): fp32 arithmetic on widened values, one rounding at each 16-bit store.  The mask
   pyramid, the stencil weights, the cells, ``outs`` and the mask history stay fp32; the parameters stay fp32 masters.
-  Calls that require a gradient ignore the setting: the training forms are fp32.
+  Calls that require a gradient ignore the setting: the training forms have a switch of their own.
+
+``decoder.train_dtype = torch.bfloat16`` (opt-in; the default is fp32) runs the FUSED TRAINING form, and ``RefineTrainStep`` on
+it, on bf16 ACTIVATIONS behind an encoder that trains in bf16 (``TrainEncoder``): the skip maps and the spatial and temporal
+hiddens are bf16, the mask planes and the cells fp32 (any other set raises a ``DmmError`` that names it: no silent casts).  The
+library convolutions run in bf16 on bf16 casts of the differentiable fp32 weight slices, cast once per frame; the cell, the
+upsample and the trainer's finish run on the 16-bit entries forward and backward (include/dmm_match.h (12i), (12j),
+(12l)-(12o)); the mask pyramid, its backward and the loss stay fp32.  The parameters stay fp32 masters and receive fp32
+gradients: every convolution's weight gradient is widened before it is added to another's (``_ConvStacked``), the bias
+gradients and the mask stencil's are fp32 sums.  With the default ``train_dtype`` every route is what it was.
 """
 from __future__ import annotations
 
@@ -189,31 +198,40 @@ def clstm_gates(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev,
 
 def clstm_gates_bwd(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_prev, d_hidden, d_cell,
                     need=(True, True, True)):
-    """``dmm_clstm_gates_bwd_f32``: the inputs of ``clstm_gates`` and the upstream gradients ``d_hidden`` / ``d_cell``
-    ([B, Hd, h, w]; either may be None = zeros, not both) -> ``(d_pre, d_cell_prev, d_masks, d_w_mask)``.  ``d_pre``
-    [B, 4*Hd, h, w] is the gradient of the sum of the addends, so of each of them; ``need`` says which of ``d_cell_prev``,
-    ``d_masks`` [B, 3, h, w], ``d_w_mask`` [4*Hd, 9] are wanted (the others are None and cost nothing).  The gates are
-    recomputed from the inputs; bit-reproducible."""
+    """``dmm_clstm_gates_bwd_f32`` / ``_bf16`` by the addends' dtype: the inputs of ``clstm_gates`` and the upstream gradients
+    ``d_hidden`` / ``d_cell`` ([B, Hd, h, w]; either may be None = zeros, not both) -> ``(d_pre, d_cell_prev, d_masks,
+    d_w_mask)``.  ``d_pre`` [B, 4*Hd, h, w] is the gradient of the sum of the addends, so of each of them; ``need`` says which
+    of ``d_cell_prev``, ``d_masks`` [B, 3, h, w], ``d_w_mask`` [4*Hd, 9] are wanted (the others are None and cost nothing).
+    ``d_hidden`` and ``d_pre`` have the addends' dtype; masks, w_mask, cell_prev, ``d_cell`` and the other three gradients are
+    fp32 in either form.  The gates are recomputed from the inputs; bit-reproducible."""
     _need_device(masks)
-    ptrs, strides, keep = _addends(pre)
+    first = next(p for p in pre if p is not None)
+    entry = _act_entry("dmm_clstm_gates_bwd_", first.dtype, "the addends of the pre-activation")
+    ptrs, strides, keep = _addends(pre, dtype=first.dtype)
     B, C4, h, w = keep[0].shape
     Hd = C4 // 4
     assert C4 == 4 * Hd, keep[0].shape
     need_cell, need_masks, need_w = (bool(n) for n in need)
     assert not need_cell or cell_prev is not None, "d_cell_prev without cell_prev"
+    if d_hidden is not None and d_hidden.dtype != first.dtype:
+        raise _lib.DmmError(f"clstm_gates_bwd: d_hidden is {d_hidden.dtype}, the addends of the pre-activation {first.dtype}")
+    for name, t in (("masks", masks), ("w_mask", w_mask), ("cell_prev", cell_prev), ("d_cell", d_cell)):
+        if t is not None and t.dtype != torch.float32:
+            raise _lib.DmmError(f"clstm_gates_bwd: {name} is {t.dtype}; the mask planes, the stencil, the cell state and its "
+                                "gradient are float32")
     masks, sbm = _dense_batch(masks)
     w_mask = w_mask.contiguous()
     assert tuple(masks.shape) == (B, 3, h, w) and tuple(w_mask.shape) == (4 * Hd, 9)
     state = []
     for t in (cell_prev, d_hidden, d_cell):
         if t is not None:
-            assert tuple(t.shape) == (B, Hd, h, w) and t.dtype == torch.float32, (t.shape, (B, Hd, h, w))
+            assert tuple(t.shape) == (B, Hd, h, w), (t.shape, (B, Hd, h, w))
             t = t.contiguous()
         state.append(t)
     cell_prev, d_hidden, d_cell = state
     assert d_hidden is not None or d_cell is not None
     new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=masks.device)
-    d_pre = new(B, 4 * Hd, h, w)
+    d_pre = torch.empty((B, 4 * Hd, h, w), dtype=first.dtype, device=masks.device)
     d_cell_prev = new(B, Hd, h, w) if need_cell else None
     d_masks = new(B, 3, h, w) if need_masks else None
     d_w_mask = new(4 * Hd, 9) if need_w else None
@@ -221,7 +239,7 @@ def clstm_gates_bwd(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_p
     if need_masks or need_w:
         ws_bytes = int(_lib.load().dmm_clstm_gates_bwd_workspace_bytes(B, Hd, h, w))
         ws = torch.empty((max(ws_bytes, 4) // 4,), dtype=torch.float32, device=masks.device)
-    _lib.call("dmm_clstm_gates_bwd_f32", masks.device, *ptrs, *strides, _ptr(masks), sbm, _ptr(w_mask), _ptr(cell_prev),
+    _lib.call(entry, masks.device, *ptrs, *strides, _ptr(masks), sbm, _ptr(w_mask), _ptr(cell_prev),
               B, Hd, h, w, _ptr(d_hidden), _ptr(d_cell), _ptr(d_pre), _ptr(d_cell_prev), _ptr(d_masks), _ptr(d_w_mask), _ptr(ws),
               ws_bytes, _stream(masks))
     return d_pre, d_cell_prev, d_masks, d_w_mask
@@ -230,12 +248,13 @@ def clstm_gates_bwd(pre: Sequence[Optional[torch.Tensor]], masks, w_mask, cell_p
 class ClstmGatesFn(torch.autograd.Function):
     """The fused cell under autograd: ``apply(pre0, pre1, pre2, masks, w_mask, cell_prev) -> (hidden, cell)`` (``pre1``,
     ``pre2``, ``cell_prev`` may be None).  Forward: ``clstm_gates`` into fresh tensors; backward: ``clstm_gates_bwd``.
-    Saves its inputs only: the backward recomputes the gates."""
+    Saves its inputs only: the backward recomputes the gates.  On bf16 addends ``hidden`` and the addends' gradient are bf16;
+    the cell, the mask planes, the stencil and their gradients are fp32."""
 
     @staticmethod
     def forward(ctx, pre0, pre1, pre2, masks, w_mask, cell_prev):
         B, C4, h, w = pre0.shape
-        hidden, cell = pre0.new_empty((B, C4 // 4, h, w)), pre0.new_empty((B, C4 // 4, h, w))
+        hidden, cell = pre0.new_empty((B, C4 // 4, h, w)), pre0.new_empty((B, C4 // 4, h, w), dtype=torch.float32)
         clstm_gates([pre0, pre1, pre2], masks, w_mask.contiguous(), cell_prev, hidden, cell)
         ctx.save_for_backward(pre0, pre1, pre2, masks, w_mask, cell_prev)
         ctx.set_materialize_grads(False)
@@ -287,6 +306,15 @@ class _WeightSlices(torch.autograd.Function):
         return torch.cat(parts, 1), None
 
 
+class _LevelSlices(dict):
+    """One level's slices (``RSISMask._cut_slices``) with ``low``: the memo of the bf16 casts the bf16 training form's
+    convolutions run on (``RSISMask._conv``), so a slice is cast once per frame however many objects use it."""
+
+    def __init__(self, **slices):
+        super().__init__(**slices)
+        self.low = {}
+
+
 def _chain_weight(d):
     """``cat`` = [up | hs] of one level's slices (``RSISMask._cut_slices``; levels >= 1), made on first use and kept with them:
     the training form needs it only once an object has a spatial state, and then once for every object of the frame."""
@@ -300,13 +328,25 @@ class _ConvStacked(torch.autograd.Function):
     stacked along the batch (the objects of a frame), and one data-gradient call for all of them; the gradients of ``weight``
     and ``bias`` are taken group by group and added in group order.  Summed in a single library call over every group's
     pixels, conv_out's weight gradient came out 2 - 3 times further from fp64 than the trainer's per-object convolutions
-    leave it (profiles/r12_refine_train.md); this way it carries their error."""
+    leave it (profiles/r12_refine_train.md); this way it carries their error.
+
+    The bf16 training form (``x`` bf16, ``weight`` / ``bias`` the fp32 masters): the library runs in ``x``'s dtype on casts of
+    the two -- ``low``, an optional ``(weight, bias)`` pair cast by the caller once per frame, else cast here -- and every
+    group's weight gradient is widened to fp32 BEFORE it meets another's: the sum over the groups here, and autograd's sum over
+    the uses of a weight slice, are fp32 sums.  The bias gradient is an fp32 sum of the bf16 ``dy`` (rounded to bf16 by the
+    library it reached 1.68 of the stock form's error where tests/test_gpu_decoder_train_bf16.py allows 2;
+    profiles/r16_decoder_train_bf16.md).
+    ``chunks = 1`` is the plain convolution of that form."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, chunks):
-        ctx.save_for_backward(x, weight)
-        ctx.chunks, ctx.has_bias = int(chunks), bias is not None
-        return F.conv2d(x, weight, bias, padding=1)
+    def forward(ctx, x, weight, bias, chunks, low=None):
+        if weight.dtype != x.dtype:
+            w, b = low if low is not None else (weight.to(x.dtype), None if bias is None else bias.to(x.dtype))
+        else:
+            w, b = weight, bias
+        ctx.save_for_backward(x, w)
+        ctx.chunks, ctx.has_bias, ctx.master = int(chunks), bias is not None, weight.dtype
+        return F.conv2d(x, w, b, padding=1)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -319,14 +359,17 @@ class _ConvStacked(torch.autograd.Function):
         dy = dy.contiguous()
         dx = bwd(dy, x, [True, False, False])[0] if need_x else None
         dw = db = None
+        low = weight.dtype != ctx.master                                  # the bias gradient is then summed in fp32 here
         if need_w or need_b:
             for xc, dc in zip(x.chunk(ctx.chunks, 0), dy.chunk(ctx.chunks, 0)):
-                _, a, c = bwd(dc, xc, [False, need_w, need_b])
+                _, a, c = bwd(dc, xc, [False, need_w, need_b and not low])
                 if need_w:
+                    a = a.to(ctx.master)
                     dw = a if dw is None else dw + a
                 if need_b:
+                    c = dc.sum((0, 2, 3), dtype=ctx.master) if low else c
                     db = c if db is None else db + c
-        return dx, dw, db, None
+        return dx, dw, db, None, None
 
 
 def upsample_bilinear_into(src, dst, c0: int = 0, mode: str = "write"):
@@ -449,20 +492,22 @@ def mask_pyramid_torch(prev_mask, y_mask, init_pred, n_obj: int, H: int, W: int)
 
 
 def upsample_bilinear_bwd(d_dst, c0: int, C: int, h: int, w: int):
-    """``dmm_upsample_bilinear_bwd_f32``: the gradient of channels c0 .. c0 + C of d_dst [B, C', H, W] (what 'write' mode of
-    ``upsample_bilinear_into`` wrote) -> d_src [B, C, h, w].  H >= h and W >= w; anything else raises."""
+    """``dmm_upsample_bilinear_bwd_f32`` / ``_bf16`` by ``d_dst``'s dtype: the gradient of channels c0 .. c0 + C of d_dst
+    [B, C', H, W] (what 'write' mode of ``upsample_bilinear_into`` wrote) -> d_src [B, C, h, w] of the same dtype.  H >= h and
+    W >= w; anything else raises."""
     _need_device(d_dst)
-    assert d_dst.dtype == torch.float32
+    entry = _act_entry("dmm_upsample_bilinear_bwd_", d_dst.dtype, "d_dst")
     d_dst, sbd = _dense_batch(d_dst)
     B, Cd, H, W = d_dst.shape
-    d_src = torch.empty((B, C, h, w), dtype=torch.float32, device=d_dst.device)
-    _lib.call("dmm_upsample_bilinear_bwd_f32", d_dst.device, _ptr(d_dst), sbd, B, int(C), H, W, Cd, int(c0),
+    d_src = torch.empty((B, C, h, w), dtype=d_dst.dtype, device=d_dst.device)
+    _lib.call(entry, d_dst.device, _ptr(d_dst), sbd, B, int(C), H, W, Cd, int(c0),
               _ptr(d_src), C * h * w, int(h), int(w), _stream(d_dst))
     return d_src
 
 
 class UpsampleBilinearFn(torch.autograd.Function):
-    """``apply(src, size)``: ``upsample_bilinear_into`` ('write') into a fresh tensor; backward ``upsample_bilinear_bwd``."""
+    """``apply(src, size)``: ``upsample_bilinear_into`` ('write') into a fresh tensor of ``src``'s dtype (fp32 or bf16); backward
+    ``upsample_bilinear_bwd``."""
 
     @staticmethod
     def forward(ctx, src, size):
@@ -470,7 +515,7 @@ class UpsampleBilinearFn(torch.autograd.Function):
         H, W = int(size[0]), int(size[1])
         if H < h or W < w:
             raise _lib.DmmError(f"upsample_bilinear_fn: {h}x{w} -> {H}x{W} is not an upsample (its backward covers H >= h, W >= w)")
-        dst = torch.empty((B, C, H, W), dtype=torch.float32, device=src.device)
+        dst = torch.empty((B, C, H, W), dtype=src.dtype, device=src.device)
         upsample_bilinear_into(src, dst, 0, "write")
         ctx.src_size = (h, w)
         return dst
@@ -499,28 +544,34 @@ def _logit_planes(logits):
 
 
 def refine_train_finish(logits, O: int, H: int, W: int):
-    """``dmm_refine_train_finish_f32``: logits [B, n_obj, h, w] (any batch / object strides, dense planes) -> outs [B, O, H, W]
-    = sigmoid of the NEAREST interpolation (torch's default mode, trainer.py:275), zero rows beyond n_obj."""
+    """``dmm_refine_train_finish_f32`` / ``_bf16`` by the logits' dtype: logits [B, n_obj, h, w] (any batch / object strides,
+    dense planes) -> outs [B, O, H, W] fp32 = sigmoid of the NEAREST interpolation (torch's default mode, trainer.py:275), zero
+    rows beyond n_obj."""
     _need_device(logits)
-    assert logits.dtype == torch.float32 and logits.dim() == 4 and logits.shape[1] <= O
+    entry = _act_entry("dmm_refine_train_finish_", logits.dtype, "logits")
+    assert logits.dim() == 4 and logits.shape[1] <= O
     logits = _logit_planes(logits)
     B, n_obj, h, w = logits.shape
     outs = torch.empty((B, O, H, W), dtype=torch.float32, device=logits.device)
-    _lib.call("dmm_refine_train_finish_f32", logits.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w, B, int(O),
+    _lib.call(entry, logits.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w, B, int(O),
               n_obj, int(H), int(W), _ptr(outs), _stream(logits))
     return outs
 
 
 def refine_train_finish_bwd(logits, d_outs):
-    """``dmm_refine_train_finish_bwd_f32``: the forward's logits and d_outs [B, O, H, W] -> d_logits [B, n_obj, h, w]."""
+    """``dmm_refine_train_finish_bwd_f32`` / ``_bf16`` by the logits' dtype: the forward's logits and d_outs [B, O, H, W] fp32
+    -> d_logits [B, n_obj, h, w] of the logits' dtype."""
     _need_device(logits)
+    entry = _act_entry("dmm_refine_train_finish_bwd_", logits.dtype, "logits")
+    if d_outs.dtype != torch.float32:
+        raise _lib.DmmError(f"refine_train_finish_bwd: d_outs is {d_outs.dtype}; the probabilities and their gradient are float32")
     logits = _logit_planes(logits)
     B, n_obj, h, w = logits.shape
-    assert d_outs.dtype == torch.float32 and d_outs.dim() == 4 and d_outs.shape[0] == B and d_outs.shape[1] >= n_obj
+    assert d_outs.dim() == 4 and d_outs.shape[0] == B and d_outs.shape[1] >= n_obj
     d_outs = d_outs.contiguous()
     O, H, W = d_outs.shape[1:]
-    d_logits = torch.empty((B, n_obj, h, w), dtype=torch.float32, device=logits.device)
-    _lib.call("dmm_refine_train_finish_bwd_f32", logits.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w,
+    d_logits = torch.empty((B, n_obj, h, w), dtype=logits.dtype, device=logits.device)
+    _lib.call(entry, logits.device, _ptr(logits), logits.stride(0), logits.stride(1), h, w,
               _ptr(d_outs), B, O, n_obj, H, W, _ptr(d_logits), n_obj * h * w, h * w, _stream(logits))
     return d_logits
 
@@ -546,8 +597,9 @@ def refine_train_finish_fn(logits, O: int, H: int, W: int):
 
 
 def refine_train_finish_torch(logits, O: int, H: int, W: int):
-    """The twin of ``refine_train_finish_fn``."""
-    p = torch.sigmoid(F.interpolate(logits, (H, W)))
+    """The twin of ``refine_train_finish_fn`` (bf16 logits are widened before the sigmoid: the probabilities are fp32)."""
+    x = F.interpolate(logits, (H, W))
+    p = torch.sigmoid(x.float() if x.dtype == torch.bfloat16 else x)
     outs = p.new_zeros((p.shape[0], O, H, W))
     outs[:, :p.shape[1]] = p
     return outs
@@ -602,6 +654,7 @@ class RSISMask(nn.Module):
         self.fused = True                    # False: always the stock form (A/B timing, tests)
         self.fused_train = False             # True: calls that require a gradient take the fused training form
         self._compute_dtype = torch.float32  # the activations' dtype of the fused (no-grad) form: ``compute_dtype``
+        self._train_dtype = torch.float32    # the activations' dtype of the fused training form: ``train_dtype``
         self._slices = None                  # (key, per-level weight slices, conv_out's pair) of the fused form
         self.conv_calls = 0                  # convolutions issued by the fused form (diagnostic, like dmm_launch_count)
 
@@ -617,11 +670,25 @@ class RSISMask(nn.Module):
             raise ValueError(f"RSISMask.compute_dtype is torch.float32 or torch.bfloat16, not {dtype!r}")
         self._compute_dtype = dtype
 
+    @property
+    def train_dtype(self):
+        """The dtype of the fused TRAINING form's activations (``fused_train = True``, a gradient required): ``torch.float32``
+        (default) or, opt-in, ``torch.bfloat16`` (module docstring).  The parameters stay fp32 masters with fp32 gradients;
+        calls that require no gradient ignore it (``compute_dtype`` is theirs)."""
+        return self._train_dtype
+
+    @train_dtype.setter
+    def train_dtype(self, dtype):
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"RSISMask.train_dtype is torch.float32 or torch.bfloat16, not {dtype!r}")
+        self._train_dtype = dtype
+
     # ---- dispatch ------------------------------------------------------------------------------------------------
     def _route(self, tensors: Sequence[torch.Tensor]) -> str:
-        """'fused' (no gradient), 'train' (a gradient is required and ``fused_train`` is on) or 'stock'.  Without a gradient
-        and with ``compute_dtype = torch.bfloat16`` the fused form takes bf16 tensors beside fp32 ones (which tensor has to be
-        which: ``_check_bf16_operands``); in every other case all of them are fp32."""
+        """'fused' (no gradient), 'train' (a gradient is required and ``fused_train`` is on) or 'stock'.  With
+        ``compute_dtype = torch.bfloat16`` (no gradient) or ``train_dtype = torch.bfloat16`` (a gradient) the form takes bf16
+        tensors beside fp32 ones (which tensor has to be which: ``_check_bf16_operands``); in every other case all of them
+        are fp32."""
         if not self.fused or self.skip_mode not in _SKIP_MODES or int(self.kernel_size) != 3 or self.prev_mask_d != 1:
             return "stock"
         if self.training and self.dropout > 0:
@@ -632,16 +699,21 @@ class RSISMask(nn.Module):
             return "stock"
         if not all(t.is_cuda and t.dtype == torch.float32 for t in params):
             return "stock"
-        taken = (torch.float32,) if grad or self._compute_dtype == torch.float32 else (torch.float32, torch.bfloat16)
+        act = self._train_dtype if grad else self._compute_dtype
+        taken = (torch.float32,) if act == torch.float32 else (torch.float32, torch.bfloat16)
         if not all(t.is_cuda and t.dtype in taken for t in tensors):
             return "stock"
         return "train" if grad else "fused"
 
+    def _act_dtype(self, route: str):
+        """The activations' dtype of a fused route: ``train_dtype`` for 'train', ``compute_dtype`` for 'fused'."""
+        return self._train_dtype if route == "train" else self._compute_dtype
+
     @staticmethod
-    def _check_bf16_operands(low, full):
-        """The operand set of the bf16 fused form: ``low`` (skip maps, hiddens) bf16, ``full`` (mask planes, cells) fp32."""
+    def _check_bf16_operands(low, full, setting="compute_dtype"):
+        """The operand set of a bf16 fused form: ``low`` (skip maps, hiddens) bf16, ``full`` (mask planes, cells) fp32."""
         if not all(t.dtype == torch.bfloat16 for t in low) or not all(t.dtype == torch.float32 for t in full):
-            raise _lib.DmmError("RSISMask with compute_dtype = torch.bfloat16 takes bfloat16 skip maps, spatial hiddens and "
+            raise _lib.DmmError(f"RSISMask with {setting} = torch.bfloat16 takes bfloat16 skip maps, spatial hiddens and "
                                 "temporal hiddens and float32 mask planes and cells; got "
                                 f"{sorted({str(t.dtype) for t in low})} and {sorted({str(t.dtype) for t in full})}")
 
@@ -657,14 +729,14 @@ class RSISMask(nn.Module):
         if prev_hidden_temporal is not None:
             ts += list(prev_hidden_temporal)
         route = self._route(ts)
+        if route != "stock" and self._act_dtype(route) == torch.bfloat16:
+            low = list(skip_feats) + ([] if prev_hidden_temporal is None else list(prev_hidden_temporal))
+            full = list(prev_mask_list)
+            if prev_state_spatial is not None:
+                low += [st[0] for st in prev_state_spatial]
+                full += [st[1] for st in prev_state_spatial]
+            self._check_bf16_operands(low, full, "train_dtype" if route == "train" else "compute_dtype")
         if route == "fused":
-            if self._compute_dtype == torch.bfloat16:
-                low = list(skip_feats) + ([] if prev_hidden_temporal is None else list(prev_hidden_temporal))
-                full = list(prev_mask_list)
-                if prev_state_spatial is not None:
-                    low += [st[0] for st in prev_state_spatial]
-                    full += [st[1] for st in prev_state_spatial]
-                self._check_bf16_operands(low, full)
             return self._forward_fused(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
         if route == "train":
             return self._forward_fused_train(skip_feats, prev_mask_list, prev_state_spatial, prev_hidden_temporal)
@@ -721,7 +793,7 @@ class RSISMask(nn.Module):
                 Wt, bias = Wt.detach(), bias.detach()
             cup = cin if i == 0 or self.skip_mode != "concat" else self.skip_dims_out[i - 1]
             w_x, w_x2, w_m, w_hs, w_ht = _WeightSlices.apply(Wt, (0, cup, cin, cin + 1, cin + 1 + Hd, cin + 1 + 2 * Hd))
-            d = {"m": w_m.reshape(4 * Hd, 9), "hs": w_hs, "ht": w_ht, "bias": bias, "up": None, "skip": w_x, "cat": None}
+            d = _LevelSlices(m=w_m.reshape(4 * Hd, 9), hs=w_hs, ht=w_ht, bias=bias, up=None, skip=w_x, cat=None)
             if i > 0:
                 d["up"] = w_x
                 d["skip"] = w_x2 if self.skip_mode == "concat" else w_x if self.skip_mode == "sum" else None
@@ -759,20 +831,32 @@ class RSISMask(nn.Module):
         weight's gradient once per frame."""
         return self._cut_slices(train=True)
 
-    def _conv(self, x, w, b=None):
+    def _conv(self, x, w, b=None, low=None):
+        """One 3x3 / padding 1 library convolution.  ``x`` bf16 on fp32 ``w`` / ``b`` -- the bf16 training form on its fp32
+        master slices -- runs in bf16 on casts of the two and hands the slices fp32 gradients (``_ConvStacked``); ``low``: a
+        level's memo of such casts (``_cut_slices``), so a slice is cast once per frame however many objects use it."""
         self.conv_calls += 1
-        return F.conv2d(x, w, b, padding=1)
+        if w.dtype == x.dtype:
+            return F.conv2d(x, w, b, padding=1)
+        pair = None
+        if low is not None:
+            pair = low.get((id(w), id(b)))
+            if pair is None:
+                with torch.no_grad():
+                    pair = low[(id(w), id(b))] = (w.to(x.dtype), None if b is None else b.to(x.dtype))
+        return _ConvStacked.apply(x, w, b, 1, pair)
 
     def skip_terms(self, skip_feats, slices=None):
         """The object-independent share of every level's pre-activation: conv(skip map, W_skip) + bias (None where the
         level has no such term: 'mul' / 'none' above level 0).  Once per frame.  ``slices``: default ``weight_slices()``."""
         sl = self.weight_slices() if slices is None else slices
-        return [None if d["skip"] is None else self._conv(f, d["skip"], d["bias"]) for d, f in zip(sl, skip_feats)]
+        return [None if d["skip"] is None else self._conv(f, d["skip"], d["bias"], getattr(d, "low", None))
+                for d, f in zip(sl, skip_feats)]
 
     def temporal_terms(self, hidden_temporal, slices=None):
         """conv(h_t, W_ht) per level; ``hidden_temporal[i]`` may stack every object of the frame along the batch."""
         sl = self.weight_slices() if slices is None else slices
-        return [self._conv(h, d["ht"]) for d, h in zip(sl, hidden_temporal)]
+        return [self._conv(h, d["ht"], None, getattr(d, "low", None)) for d, h in zip(sl, hidden_temporal)]
 
     def _level(self, i, d, skip_term, temporal_term, skip, masks, state_spatial, hidden, cell, up_src, chain_in=None,
                holds_state=False, hidden_copy=None):
@@ -829,7 +913,9 @@ class RSISMask(nn.Module):
                              skip_terms=None, temporal_terms=None, bilinear=None, head=True):
         """The fused algebra under autograd: per level the addends (skip term with the bias, temporal term, chain term on
         cat[up, h_s] / up / h_s) are library convolutions on differentiable slices of ``Gates.weight``, the upsample, ``cat``
-        and the 'mul' product are torch ops, and the cell is ``clstm_gates_fn`` (HIP forward and backward).
+        and the 'mul' product are torch ops, and the cell is ``clstm_gates_fn`` (HIP forward and backward).  The activations'
+        dtype is the skip maps': on the bf16 operand set of ``train_dtype`` every op here is the same op in bf16 (``_conv``
+        on the fp32 master slices), the cells and the mask planes fp32.
 
         The optional arguments let a driver hand over what does not depend on the object (``RefineTrainStep``); the defaults
         compute everything here.  ``slices``: ``train_slices()`` taken once per frame; ``skip_terms``: per level
@@ -850,18 +936,18 @@ class RSISMask(nn.Module):
             f = skip_feats[i]
             st = None if prev_state_spatial is None else prev_state_spatial[i]
             chain_bias = None if skip_terms[i] is not None else d["bias"]
-            chain = None
+            chain, low = None, getattr(d, "low", None)
             if i == 0:
                 if st is not None:
-                    chain = self._conv(st[0], d["hs"])
+                    chain = self._conv(st[0], d["hs"], None, low)
             else:
                 x = bilinear(up, tuple(f.shape[-2:]))
                 if self.skip_mode == "mul":
                     x = f * x
                 if st is None:
-                    chain = self._conv(x, d["up"], chain_bias)
+                    chain = self._conv(x, d["up"], chain_bias, low)
                 else:
-                    chain = self._conv(torch.cat([x, st[0]], 1), _chain_weight(d), chain_bias)
+                    chain = self._conv(torch.cat([x, st[0]], 1), _chain_weight(d), chain_bias, low)
             hidden, c = clstm_gates_fn([skip_terms[i], temporal_terms[i], chain], prev_mask_list[i], d["m"],
                                        None if st is None else st[1])
             hidden_list.append([hidden, c])
@@ -1072,6 +1158,13 @@ class RefineTrainStep:
       ``clstm_gates_fn`` and ``upsample_bilinear_fn``, then one upsample, one ``conv_out`` and one ``refine_train_finish_fn``
       for all objects.  ``kernels`` names which of the three pieces run on their HIP functions; setting one to False routes
       that piece alone through its torch twin (the same function in torch ops).
+
+    With ``decoder.train_dtype = torch.bfloat16`` (and ``fused_train``, HIP tensors, a gradient required) ``_fused`` runs on
+    bf16 ACTIVATIONS, behind an encoder that trains in bf16: the skip maps and the hiddens in ``thid`` are bf16 (anything else
+    raises the named ``DmmError``: no silent casts), every convolution runs in bf16 and the kernels between them are the 16-bit
+    entries (include/dmm_match.h (12i), (12j), (12l)-(12o)).  ``prev_mask`` / ``ref_mask`` / ``init_pred``, the pyramid, the
+    cells, ``outs_pad`` and the loss stay fp32; the parameters stay fp32 masters and receive fp32 gradients, every
+    convolution's weight gradient widened before it is added to another's.  The same convolution and launch counts.
     """
 
     def __init__(self, decoder: RSISMask, only_temporal: bool = False, iou_weight: float = 1.0):
@@ -1089,11 +1182,14 @@ class RefineTrainStep:
         if n_obj <= 0:
             raise ValueError("RefineTrainStep: no valid object (the trainer's num_template_not_empty == 0 branch is the caller's)")
         dec = self.decoder
-        ts = feats + [prev_mask, ref_mask, init_pred]
-        if state.thid is not None:
-            ts += [h for hs in state.thid for h in hs]
-        fused = dec.fused_train and dec._route(ts) in ("train", "fused")
+        planes = [prev_mask, ref_mask, init_pred]
+        hiddens = [] if state.thid is None else [h for hs in state.thid for h in hs]
+        route = dec._route(feats + planes + hiddens)
+        fused = dec.fused_train and route in ("train", "fused")
         self.last_route = "fused" if fused else "stock"
+        if fused and dec._act_dtype(route) == torch.bfloat16 and (route == "train" or feats[0].dtype != torch.float32):
+            # (without a gradient the step takes all-fp32 tensors under compute_dtype = bf16 as it always has)
+            dec._check_bf16_operands(feats + hiddens, planes, "train_dtype" if route == "train" else "compute_dtype")
         run = self._fused if fused else self._stock
         probs, thid = run(feats, prev_mask, ref_mask, init_pred, state.thid, n_obj, B, O, H, W)      # [B, O, HW]
         from .losses import mask_step_losses
@@ -1140,6 +1236,6 @@ class RefineTrainStep:
         top = torch.cat(tops, 0)                                                    # [n_obj * B, Hd / 8, h, w]
         top = bilinear(top, (top.shape[-2] * 2, top.shape[-1] * 2))
         dec.conv_calls += 1
-        logits = _ConvStacked.apply(top, dec.conv_out.weight, dec.conv_out.bias, n_obj)   # [n_obj * B, 1, 2h, 2w]
+        logits = _ConvStacked.apply(top, dec.conv_out.weight, dec.conv_out.bias, n_obj, None)   # [n_obj * B, 1, 2h, 2w]
         logits = logits.view(n_obj, B, *logits.shape[-2:]).transpose(0, 1)          # [B, n_obj, 2h, 2w] (strided view)
         return finish(logits, O, H, W).view(B, O, H * W), thid

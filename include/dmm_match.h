@@ -861,7 +861,8 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  * the cell (12b); (12f)-(12h) are what the refine step of TRAINING (dmm/modules/trainer.py:236-306) runs around the decoder:
  * the backward of the pyramid (12a), the backward of the upsample (12c) in 'write' mode, and the trainer's own finish
  * (nearest interpolation, sigmoid, pad) with its backward.  None of (12f)-(12h) uses an atomic or a workspace.  (12i)-(12k) are
- * (12b)-(12d) on bf16 activations, for the evaluator behind a bf16 encoder (RSISMask.compute_dtype = torch.bfloat16).
+ * (12b)-(12d) on bf16 activations, for the evaluator behind a bf16 encoder (RSISMask.compute_dtype = torch.bfloat16); (12l)-(12o)
+ * are (12e), (12g) and (12h) on bf16 activations, for the trainer behind one (RSISMask.train_dtype = torch.bfloat16).
  *
  * (12a) dmm_mask_pyramid_f32 -- evaluator.py:188-195: MaxPool2d((2,2), ceil_mode=True) applied 5, 4, 3 and 2 times to the planes
  *   prev_mask[b, t], y_mask[b, t], init_pred[b, t] (each H x W at base + b * sb + t * so), b < B, t < n_obj, in ONE launch and
@@ -943,8 +944,8 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  *   the same order (the library is built with -ffp-contract=off; the kernels are one template over the storage type), and every
  *   16-bit output is rounded ONCE, to nearest even, at its store (a NaN becomes 0x7FC0, torch's rule).  So entry_bf16(x) equals
  *   bf16(entry_f32(widened x)) bit for bit, and its fp32 outputs equal entry_f32's bit for bit.  A lane owns one position and
- *   issues 2-byte loads and stores: any width, any 2-byte-aligned plane or row, nothing stored outside the tensor.  No backward
- *   forms, no atomics, no workspace.  Each entry validates as its fp32 sibling does: the same answers in the same order, before
+ *   issues 2-byte loads and stores: any width, any 2-byte-aligned plane or row, nothing stored outside the tensor.  No
+ *   atomics, no workspace (the backward forms are (12l)-(12o)).  Each entry validates as its fp32 sibling does: the same answers in the same order, before
  *   any HIP call.
  * (12i) dmm_clstm_gates_bf16 -- (12b) with pre0..2, hidden and hidden_copy bf16 (same null meanings and batch strides).  masks,
  *   w_mask, cell_prev and cell stay fp32: the cell state is the recurrence along the object chain and keeps full precision; the
@@ -952,6 +953,27 @@ DMM_API int dmm_graph_nodes_to_kernels(void *graph, int flags, int *n_memset, in
  * (12j) dmm_upsample_bilinear_into_bf16 -- (12c) with src and dst bf16, modes 0 / 1 / 2; in modes 1 and 2 dst is read as bf16,
  *   combined in fp32 and rounded once.
  * (12k) dmm_refine_finish_bf16 -- (12d) with bf16 logits (the output of a bf16 conv_out); outs and mask_hist fp32, valid int32.
+ *
+ * (12l)-(12o) The TRAINING entries (12e), (12g), (12h) on bf16 activations (RSISMask.train_dtype = torch.bfloat16, behind a bf16
+ *   TrainEncoder).  The rule of (12i)-(12k) holds for each: 16-bit values widened on load, the fp32 entry's expressions in its
+ *   order (one template over the storage type), every 16-bit output rounded once at its store, 2-byte loads and stores by the lane
+ *   that owns the element -- any 2-byte-aligned base.  So entry_bf16(x) == bf16(entry_f32(widened x)) for its 16-bit outputs and
+ *   == entry_f32(widened x) for its fp32 outputs, bit for bit.  The operands that are fp32 in the forward are fp32 here; the
+ *   pyramid and its backward (12a), (12f) have no 16-bit form (mask planes are fp32 in every form).  Each entry validates as its
+ *   fp32 sibling does, the same answers in the same order before any launch; strides in elements; no float atomics.
+ * (12l) dmm_clstm_gates_bwd_bf16 -- (12e), the backward of (12i).  bf16: pre0..2, d_hidden (the gradient of the bf16 hidden) and
+ *   d_pre.  fp32: masks, w_mask, cell_prev, d_cell, d_cell_prev, d_masks, d_w_mask and the workspace -- the gate gradients reach
+ *   both reductions unrounded.  Same null meanings (pre1 / pre2 / cell_prev absent; d_hidden or d_cell = zeros, not both; a null
+ *   output = not wanted), the same batch strides, the same dmm_clstm_gates_bwd_workspace_bytes, the same fold launch and fixed
+ *   orders as (12e).
+ * (12m) dmm_upsample_bilinear_bwd_bf16 -- (12g) with d_dst and d_src bf16: the gather accumulates in fp32, Y then X ascending,
+ *   and rounds once.  H >= h >= 1 and W >= w >= 1, anything else DMM_ERR_UNSUPPORTED; batch strides sb_dst / sb_src as (12g).
+ * (12n) dmm_refine_train_finish_bf16 -- the forward of (12h) on bf16 logits (the output of a bf16 conv_out; strided as (12d)'s:
+ *   sb_logits / so_logits, dense planes); outs [B, O, H, W] fp32 dense, zero rows for n_obj <= t < O.  Equals the fp32 entry on
+ *   the widened logits bit for bit.
+ * (12o) dmm_refine_train_finish_bwd_bf16 -- the backward of (12h): logits bf16 (strided as above), d_outs fp32 [B, O, H, W] dense,
+ *   d_logits bf16 (plane (b, t) at base + b * sb_d + t * so_d, so_d >= h * w): the block sum and the product with p (1 - p) are
+ *   fp32, rounded once.
  *
  * Answers of (12f)-(12h) before any launch, in this order: DMM_ERR_BAD_ARG for a negative B / O / n_obj, n_obj > O, a size
  * <= 0, a channel range outside d_dst; (12g) DMM_ERR_UNSUPPORTED for H < h or W < w; DMM_OK when there is nothing to do
@@ -995,6 +1017,18 @@ DMM_API int dmm_refine_train_finish_f32(const float *logits, int64_t sb_logits, 
 DMM_API int dmm_refine_train_finish_bwd_f32(const float *logits, int64_t sb_logits, int64_t so_logits, int h, int w,
                                             const float *d_outs, int B, int O, int n_obj, int H, int W, float *d_logits,
                                             int64_t sb_d, int64_t so_d, dmm_stream_t stream);
+DMM_API int dmm_clstm_gates_bwd_bf16(const void *pre0, const void *pre1, const void *pre2, int64_t sb0, int64_t sb1, int64_t sb2,
+                                     const float *masks, int64_t sb_masks, const float *w_mask, const float *cell_prev, int B,
+                                     int hidden_size, int h, int w, const void *d_hidden, const float *d_cell, void *d_pre,
+                                     float *d_cell_prev, float *d_masks, float *d_w_mask, void *ws, size_t ws_bytes,
+                                     dmm_stream_t stream);
+DMM_API int dmm_upsample_bilinear_bwd_bf16(const void *d_dst, int64_t sb_dst, int B, int C, int H, int W, int C_dst, int c0,
+                                           void *d_src, int64_t sb_src, int h, int w, dmm_stream_t stream);
+DMM_API int dmm_refine_train_finish_bf16(const void *logits, int64_t sb_logits, int64_t so_logits, int h, int w, int B, int O,
+                                         int n_obj, int H, int W, float *outs, dmm_stream_t stream);
+DMM_API int dmm_refine_train_finish_bwd_bf16(const void *logits, int64_t sb_logits, int64_t so_logits, int h, int w,
+                                             const float *d_outs, int B, int O, int n_obj, int H, int W, void *d_logits,
+                                             int64_t sb_d, int64_t so_d, dmm_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * (13) The soft-IoU mask loss of the trainer's frame step, forward and backward, with the logged hard IoU riding along.

@@ -1,13 +1,17 @@
 """Times one training step of the refine decoder on the GPU, stock form beside ``fused_train``, and prints ONE JSON line.
 
-    python tools/decoder_train_timing.py [--out FILE] [--repeats 3] [--iters 5]
+    python tools/decoder_train_timing.py [--out FILE] [--repeats 3] [--iters 5] [--dtype fp32|bf16]
 
 Config 4's sizes: 4 videos of 255 x 448, hidden 128, 'concat', 5 objects chained as the trainer chains them (object t's
 spatial state is object t - 1's hidden), temporal hiddens present.  One step = forward of the five decoder calls + backward
 of the sum of their upsampled sigmoids, gradients to every parameter and skip map.  HIP events after warm-up, min / median /
 max over ``repeats`` windows of ``iters`` steps, in ms per step; ``torch.cuda.max_memory_allocated`` of one step per form;
 and the cell's backward kernel alone at the coarsest and the finest level (us per call, with and without the two
-reductions)."""
+reductions).
+
+``--dtype bf16`` adds, in the same run, ``fused_train_bf16``: the same step with ``decoder.train_dtype = torch.bfloat16`` on bf16
+skip maps and temporal hiddens, then ``fused_train`` once more (``fused_train_again``: the fp32 form's spread under the same
+conditions), the device time of the kernels of one step of each form, and the cell's bf16 backward kernel beside the fp32 one."""
 import argparse
 import json
 import os
@@ -39,11 +43,27 @@ def windows(fn, repeats, iters, warmup=3):
     return {"min": min(out), "median": statistics.median(out), "max": max(out)}
 
 
+def device_time_ms(fn):
+    """The summed device time of the kernels of one call of ``fn`` (``torch.profiler``), in ms."""
+    from torch.profiler import ProfilerActivity, profile
+    fn()
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    total = 0.0
+    for e in prof.events():
+        if getattr(e, "device_type", None) is not None and "cuda" in str(e.device_type).lower():
+            total += float(getattr(e, "device_time_total", 0.0) or getattr(e, "cuda_time_total", 0.0))
+    return total / 1e3
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "decoder_train_timing needs an MI355X"
     dev = "cuda:0"
@@ -59,17 +79,20 @@ def main():
                 for _ in range(n_obj)]
     leaves = feats + list(dec.parameters())
 
-    def step():
-        spatial, loss = None, 0
-        for t in range(n_obj):
-            out_mask, spatial = dec(feats, masks[t], spatial, temporal[t])
-            loss = loss + torch.sigmoid(F.interpolate(out_mask, (H, W))).sum()
-        return torch.autograd.grad(loss, leaves)
+    def make(feats, temporal, leaves):
+        def step():
+            spatial, loss = None, 0
+            for t in range(n_obj):
+                out_mask, spatial = dec(feats, masks[t], spatial, temporal[t])
+                loss = loss + torch.sigmoid(F.interpolate(out_mask, (H, W)).float()).sum()
+            return torch.autograd.grad(loss, leaves)
+        return step
+    step = make(feats, temporal, leaves)
 
     res = {"what": "refine decoder training step (forward + backward)", "B": B, "objects": n_obj, "H": H, "W": W,
            "hidden": hidden, "skip_mode": "concat", "unit": "ms per step", "repeats": a.repeats, "iters": a.iters}
 
-    def measure(fused_train):
+    def measure(fused_train, step=step):
         dec.fused_train = fused_train
         t = windows(step, a.repeats, a.iters)
         torch.cuda.synchronize()
@@ -104,6 +127,29 @@ def main():
                                 ("d_pre_d_cell_prev_only", (True, False, False))):
                 res[f"kernel_clstm_gates_bwd_level{lvl}_{label}_us"] = us(windows(
                     lambda: D.clstm_gates_bwd(pre, masks[0][lvl], wm, cp, dh, dc, need=need), a.repeats, 50))
+                if a.dtype == "bf16":
+                    pre16, dh16 = [p.to(torch.bfloat16) for p in pre], dh.to(torch.bfloat16)
+                    res[f"kernel_clstm_gates_bwd_bf16_level{lvl}_{label}_us"] = us(windows(
+                        lambda: D.clstm_gates_bwd(pre16, masks[0][lvl], wm, cp, dh16, dc, need=need), a.repeats, 50))
+    if a.dtype == "bf16":
+        bf16 = torch.bfloat16
+        feats16 = [f.detach().to(bf16).requires_grad_(True) for f in feats]
+        temporal16 = [[t.to(bf16) for t in ts] for ts in temporal]
+        step16 = make(feats16, temporal16, feats16 + list(dec.parameters()))
+        dec.train_dtype = bf16
+        c0 = dec.conv_calls
+        res["fused_train_bf16"] = measure(True, step16)
+        res["fused_train_bf16_convolutions_per_step"] = (dec.conv_calls - c0) // (3 + a.repeats * a.iters + 1)
+        res["fused_train_bf16_kernel_time_ms"] = device_time_ms(step16)
+        dec.train_dtype = torch.float32
+        res["fused_train_again"] = measure(True)
+        res["fused_train_kernel_time_ms"] = device_time_ms(step)
+        dec.fused_train = False
+        lo = min(res["fused_train"]["min"], res["fused_train_again"]["min"])
+        hi = max(res["fused_train"]["max"], res["fused_train_again"]["max"])
+        res["fused_train_spread"] = hi - lo
+        res["fused_train_bf16_faster_than_fused_train_by_more_than_its_spread"] = bool(lo - res["fused_train_bf16"]["max"] > hi - lo)
+        res["fused_train_bf16_slower_than_fused_train_by_more_than_its_spread"] = bool(res["fused_train_bf16"]["min"] - hi > hi - lo)
     line = json.dumps(res)
     print(line)
     if a.out:

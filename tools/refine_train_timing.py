@@ -1,6 +1,6 @@
 """Times one refine training step on the GPU in three forms and prints ONE JSON line.
 
-    python tools/refine_train_timing.py [--out FILE] [--repeats 3] [--iters 5] [--no-profile]
+    python tools/refine_train_timing.py [--out FILE] [--repeats 3] [--iters 5] [--no-profile] [--dtype fp32|bf16]
 
 Config 4's sizes: 4 videos of 255 x 448, hidden 128, 'concat', 5 objects, TWO frames chained as the trainer chains them
 (frame 1's ``prev_mask`` is frame 0's ``outs``, attached; the temporal hiddens carry their graph), so the cross-frame
@@ -13,7 +13,12 @@ to every parameter, every skip map and both frames' ``init_pred``.
 
 HIP events after warm-up, min / median / max over ``repeats`` windows of ``iters`` steps, ms per step; (b) is measured twice,
 before and after (c), and its spread is taken over both.  ``torch.cuda.max_memory_allocated`` of one step per form, and the
-kernels of one step of (b) and (c) by device time from ``torch.profiler``."""
+kernels of one step of (b) and (c) by device time from ``torch.profiler``.
+
+``--dtype bf16`` adds, in the same run, (d) ``step_bf16``: the step with ``decoder.train_dtype = torch.bfloat16`` on bf16 skip maps
+(what a trainer behind a bf16 encoder hands over), then (c) once more (``step_again``: the fp32 step's spread under the same
+conditions), the kernels of one bf16 step, and every 16-bit training kernel beside its fp32 sibling at the finest level's sizes
+(us per call)."""
 import argparse
 import json
 import os
@@ -72,12 +77,38 @@ def kernel_table(fn, top=24):
             "kernels": [{"name": k[:96], "calls": n, "ms": t / 1e3} for k, (n, t) in table]}
 
 
+def kernel_pairs(dec, B, n_obj, O, H, W, repeats, iters=50):
+    """Every 16-bit training kernel beside its fp32 sibling, us per call: the cell's backward and the upsample's at the finest
+    level, the trainer's finish and its backward on conv_out's output for all objects."""
+    dev = "cuda:0"
+    Hd, (h, w) = dec.skip_dims_out[3], D.pyramid_sizes(H, W)[3]
+    r = lambda *s: torch.randn(s, device=dev)
+    pre, cp, dh, dc = [r(B, 4 * Hd, h, w) for _ in range(3)], r(B, Hd, h, w), r(B, Hd, h, w), r(B, Hd, h, w)
+    masks, wm = torch.rand(B, 3, h, w, device=dev), r(4 * Hd, 9) * 0.3
+    d_up = r(B, dec.skip_dims_out[2], h, w)
+    h2, w2 = D.pyramid_sizes(H, W)[2]
+    logits, d_outs = r(n_obj * B, 1, 2 * h, 2 * w).view(n_obj, B, 2 * h, 2 * w).transpose(0, 1), r(B, O, H, W)
+    out = {}
+    with torch.no_grad():
+        for name, to in (("fp32", lambda t: t), ("bf16", lambda t: t.to(torch.bfloat16))):
+            p16, dh16, up16, lg16 = [to(p) for p in pre], to(dh), to(d_up), to(logits.contiguous()).view(B, n_obj, 2 * h, 2 * w)
+            for label, fn in (("clstm_gates_bwd_all_outputs", lambda: D.clstm_gates_bwd(p16, masks, wm, cp, dh16, dc)),
+                              ("clstm_gates_bwd_d_pre_d_cell_prev_only",
+                               lambda: D.clstm_gates_bwd(p16, masks, wm, cp, dh16, dc, need=(True, False, False))),
+                              ("upsample_bilinear_bwd", lambda: D.upsample_bilinear_bwd(up16, 0, up16.shape[1], h2, w2)),
+                              ("refine_train_finish", lambda: D.refine_train_finish(lg16, O, H, W)),
+                              ("refine_train_finish_bwd", lambda: D.refine_train_finish_bwd(lg16, d_outs))):
+                out[f"{label}_{name}"] = {k: 1e3 * v for k, v in windows(fn, repeats, iters).items()}
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "refine_train_timing needs an MI355X"
     dev = "cuda:0"
@@ -96,7 +127,7 @@ def main():
     sw = valid.float()
     leaves = [t for fr in frames for t in fr["feats"] + [fr["init_pred"]]] + list(dec.parameters())
 
-    def make(step):
+    def make(step, frames=frames, leaves=leaves):
         def run():
             ref_mask = frames[0]["y_mask"]
             prev_mask, state, total = ref_mask, None, 0
@@ -111,9 +142,9 @@ def main():
            "W": W, "hidden": hidden, "skip_mode": "concat", "frames": T, "unit": "ms per step", "repeats": a.repeats,
            "iters": a.iters}
 
-    def measure(step, fused_train):
+    def measure(step, fused_train, **kw):
         dec.fused_train = fused_train
-        fn = make(step)
+        fn = make(step, **kw)
         t = windows(fn, a.repeats, a.iters)
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
@@ -145,6 +176,27 @@ def main():
                 res[f"profile_{name}"] = kernel_table(make(st))
             except Exception as e:                                    # the timing above stands without the table
                 res[f"profile_{name}_error"] = repr(e)
+    if a.dtype == "bf16":
+        bf16 = torch.bfloat16
+        frames16 = [dict(fr, feats=[f.detach().to(bf16).requires_grad_(True) for f in fr["feats"]]) for fr in frames]
+        low = dict(frames=frames16, leaves=[t for fr in frames16 for t in fr["feats"] + [fr["init_pred"]]] + list(dec.parameters()))
+        dec.train_dtype = bf16
+        c0 = dec.conv_calls
+        res["step_bf16"] = measure(step, True, **low)
+        res["step_bf16_convolutions_per_step"] = (dec.conv_calls - c0) // (2 + a.repeats * a.iters + 1)
+        if not a.no_profile:
+            try:
+                res["profile_step_bf16"] = kernel_table(make(step, **low))
+            except Exception as e:
+                res["profile_step_bf16_error"] = repr(e)
+        dec.train_dtype = torch.float32
+        res["step_again"] = measure(step, True)
+        assert res["step_bf16"]["route"] == "fused" and res["step_again"]["route"] == "fused"
+        s_min, s_max = min(res["step"]["min"], res["step_again"]["min"]), max(res["step"]["max"], res["step_again"]["max"])
+        res["step_fp32_spread"] = s_max - s_min
+        res["step_bf16_faster_than_step_by_more_than_its_spread"] = bool(s_min - res["step_bf16"]["max"] > s_max - s_min)
+        res["step_bf16_slower_than_step_by_more_than_its_spread"] = bool(res["step_bf16"]["min"] - s_max > s_max - s_min)
+        res["kernels_us"] = kernel_pairs(dec, B, n_obj, O, H, W, a.repeats)
     dec.fused_train = False
     line = json.dumps(res)
     print(line)
