@@ -14,8 +14,10 @@ of per-workgroup slabs and a gather, no float atomics.  The library calls run un
 ``cudnn.deterministic`` with its naive reference kernel on gfx950 -- and onto ``dmm_conv3x3_bf16``; ``"library"`` (the
 default) leaves every route as it is.  ``"own_all"`` is ``"own"`` plus the narrow 3x3 convolutions (stride 1, widths that
 are multiples of 32 but not of 64: the 32-channel level-2 heads), which ``"own"`` runs as unfold + GEMM: forward and data
-gradient on ``dmm_conv3x3_narrow_bf16``, the weight gradient on ``dmm_wgrad3x3_narrow_bf16``.  The setting has no effect while
-the mode is off."""
+gradient on ``dmm_conv3x3_narrow_bf16``, the weight gradient on ``dmm_wgrad3x3_narrow_bf16``.  ``"own_stem"`` is ``"own_all"``
+plus the 7x7 / stride 2 stem (3 -> 64), the last convolution on unfold + GEMM: forward on ``dmm_conv7x7s2_stem_bf16``, weight
+gradient (fp32 from the kernel) on ``dmm_wgrad7x7s2_stem_bf16`` -- a deterministic ResNet step then holds no library
+convolution and no unfold.  The setting has no effect while the mode is off."""
 from __future__ import annotations
 
 import contextlib
@@ -42,12 +44,13 @@ def get_deterministic_setting() -> Optional[bool]:
 
 def set_deterministic_conv(which: str) -> None:
     """Who computes the 3x3 convolutions of a deterministic step: ``"library"`` (MIOpen under cudnn.deterministic, the default),
-    ``"own"`` (``dmm_conv3x3_bf16`` for every 3x3 / padding 1 convolution with widths that are multiples of 64) or
+    ``"own"`` (``dmm_conv3x3_bf16`` for every 3x3 / padding 1 convolution with widths that are multiples of 64),
     ``"own_all"`` (``"own"``, and ``dmm_conv3x3_narrow_bf16`` / ``dmm_wgrad3x3_narrow_bf16`` for the stride-1 ones whose widths
-    are multiples of 32 only)."""
+    are multiples of 32 only) or ``"own_stem"`` (``"own_all"``, and ``dmm_conv7x7s2_stem_bf16`` / ``dmm_wgrad7x7s2_stem_bf16``
+    for the 7x7 / stride 2 / padding 3 stem, 3 -> 64)."""
     global _CONV
-    if not isinstance(which, str) or which not in ("library", "own", "own_all"):
-        raise ValueError('set_deterministic_conv takes "library", "own" or "own_all"')
+    if not isinstance(which, str) or which not in ("library", "own", "own_all", "own_stem"):
+        raise ValueError('set_deterministic_conv takes "library", "own", "own_all" or "own_stem"')
     _CONV = which
 
 

@@ -1339,3 +1339,59 @@ def wgrad3x3_narrow_bf16(dy: torch.Tensor, x: torch.Tensor, *, out=None, workspa
     _lib.call("dmm_wgrad3x3_narrow_bf16", x.device, _ptr(dy), _ptr(x), B, H, W, ci, co, _ptr(out), _ptr(workspace),
               workspace.numel(), _stream(x))
     return out
+
+
+# ---- the 7x7 / stride 2 stem of the deterministic mode (include/dmm_match.h (10f)) ----------------------------------------
+def _stem_image(x: torch.Tensor, what: str) -> torch.Tensor:
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or x.shape[1] != 3:
+        raise _lib.DmmError(f"{what} takes a bf16 x [B, 3, H, W]")
+    return x.contiguous(memory_format=torch.channels_last)
+
+
+def conv7x7s2_stem_bf16(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, out=None) -> torch.Tensor:
+    """The 7x7 / stride 2 / padding 3 stem convolution (3 -> 64) by ``dmm_conv7x7s2_stem_bf16`` (MFMA implicit GEMM over 7 kernel
+    rows x 32 lanes, 21 of them real; fp32 accumulation, bias added in fp32, one rounding; no split of the reduction and no
+    workspace; deterministic: bit-identical call after call, and an image's result does not depend on its batch).
+    x: [B, 3, H, W] bf16 channels-last; w: [64, 3, 7, 7] bf16 channels-last; bias: bf16 [64] or None -> y [B, 64, Ho, Wo] bf16
+    channels-last, Ho = (H - 1) // 2 + 1.  ``out`` may be caller-owned; by default it is fresh."""
+    _need_gpu(x, w, bias)
+    cl = torch.channels_last
+    x = _stem_image(x, "conv7x7s2_stem_bf16")
+    if w.dtype != torch.bfloat16 or tuple(w.shape) != (64, 3, 7, 7):
+        raise _lib.DmmError("conv7x7s2_stem_bf16 takes a bf16 w [64, 3, 7, 7]")
+    w = w.contiguous(memory_format=cl)
+    if bias is not None:
+        if bias.dtype != torch.bfloat16 or tuple(bias.shape) != (64,):
+            raise _lib.DmmError("conv7x7s2_stem_bf16 takes a bf16 bias [64]")
+        bias = bias.contiguous()
+    B, _, H, W = x.shape
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if out is None:
+        out = torch.empty((B, 64, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=cl)
+    elif tuple(out.shape) != (B, 64, Ho, Wo) or out.dtype != torch.bfloat16 or not out.is_contiguous(memory_format=cl):
+        raise _lib.DmmError("conv7x7s2_stem_bf16: out must be bf16 channels-last [B, 64, Ho, Wo]")
+    _lib.call("dmm_conv7x7s2_stem_bf16", x.device, _ptr(x), _ptr(w), _ptr(bias), B, H, W, _ptr(out), _stream(x))
+    return out
+
+
+def wgrad7x7s2_stem_bf16(dy: torch.Tensor, x: torch.Tensor, *, out=None, workspace=None) -> torch.Tensor:
+    """The weight gradient of ``conv7x7s2_stem_bf16(x, w)`` by ``dmm_wgrad7x7s2_stem_bf16``: dy [B, 64, Ho, Wo] and x [B, 3, H, W]
+    bf16 channels-last -> fp32 [64, 3, 7, 7] (the parameter's own layout), overwritten; implicit patch matrix, pixel slabs
+    folded in a fixed order, no atomics.  ``out`` / ``workspace`` (uint8, >= ``dmm_wgrad7x7s2_stem_workspace_bytes``) may be
+    caller-owned; by default both are fresh."""
+    _need_gpu(dy, x)
+    x = _stem_image(x, "wgrad7x7s2_stem_bf16")
+    B, _, H, W = x.shape
+    if dy.dim() != 4 or dy.dtype != torch.bfloat16 or tuple(dy.shape) != (B, 64, (H - 1) // 2 + 1, (W - 1) // 2 + 1):
+        raise _lib.DmmError("wgrad7x7s2_stem_bf16 takes a bf16 dy [B, 64, Ho, Wo] that belongs to x")
+    dy = dy.contiguous(memory_format=torch.channels_last)
+    if out is None:
+        out = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (64, 3, 7, 7) or out.dtype != torch.float32 or not out.is_contiguous():
+        raise _lib.DmmError("wgrad7x7s2_stem_bf16: out must be fp32 contiguous [64, 3, 7, 7]")
+    need = _need_cached(("w7s", B, H, W), _lib.load().dmm_wgrad7x7s2_stem_workspace_bytes, B, H, W)
+    if workspace is None:
+        workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=x.device)
+    _lib.call("dmm_wgrad7x7s2_stem_bf16", x.device, _ptr(dy), _ptr(x), B, H, W, _ptr(out), _ptr(workspace), workspace.numel(),
+              _stream(x))
+    return out

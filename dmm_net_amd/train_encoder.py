@@ -21,7 +21,8 @@ between):
 * **1x1 convolutions are matrix products** of the [B*H*W, Cin] activation matrix (2/3 of a bottleneck): forward and data
   gradient on hipBLASLt; 3x3 forward / data gradient on MIOpen (in the deterministic mode with
   ``set_deterministic_conv("own")``: on ``dmm_conv3x3_bf16``, ``csrc/dmm_conv.hip``; with ``"own_all"`` the 32-channel heads
-  too, on ``dmm_conv3x3_narrow_bf16`` / ``dmm_wgrad3x3_narrow_bf16``); EVERY weight gradient from ``dmm_wgrad*_bf16``
+  too, on ``dmm_conv3x3_narrow_bf16`` / ``dmm_wgrad3x3_narrow_bf16``; with ``"own_stem"`` the 7x7 stem as well, on
+  ``dmm_conv7x7s2_stem_bf16`` / ``dmm_wgrad7x7s2_stem_bf16``, ``csrc/dmm_stem.hip``); EVERY weight gradient from ``dmm_wgrad*_bf16``
   (``csrc/dmm_wgrad.hip``: MFMA, split over the rows, fp32 straight into the master's gradient, no atomics) -- hipBLASLt's pick
   for these products has no split-K (66 us each), MIOpen's bf16 solvers bring a zeroing and a cast launch each.
 * **BatchNorm (+ residual) (+ ReLU) as two launches each way** (``dmm_bn_*`` in ``csrc/dmm_encoder_train.hip``) where the
@@ -121,6 +122,7 @@ def _zeroed(n: int, device) -> torch.Tensor:
 
 # ---- deterministic mode (dmm_net_amd.determinism): resolved once per TrainEncoder call and pinned while it builds / runs ----
 _DET: Optional[bool] = None              # set by TrainEncoder while its forward (eager or plan build) runs
+_OWN_SETTINGS = ("own", "own_all", "own_stem")     # ``set_deterministic_conv`` values that take the 3x3 convolutions off MIOpen
 
 
 def _det_now() -> bool:
@@ -146,15 +148,21 @@ class _det_scope:
 
 
 def _own_conv_now() -> bool:
-    """The deterministic mode's 3x3 convolutions on ``dmm_conv3x3_bf16`` (``set_deterministic_conv("own")`` / ``"own_all"``)
-    instead of MIOpen."""
-    return _det_now() and get_deterministic_conv() in ("own", "own_all")
+    """The deterministic mode's 3x3 convolutions on ``dmm_conv3x3_bf16`` (``set_deterministic_conv("own")`` / ``"own_all"`` /
+    ``"own_stem"``) instead of MIOpen."""
+    return _det_now() and get_deterministic_conv() in _OWN_SETTINGS
 
 
 def _narrow_conv_now() -> bool:
     """The deterministic mode's NARROW 3x3 convolutions (``_narrow_ok``) on ``dmm_conv3x3_narrow_bf16`` /
-    ``dmm_wgrad3x3_narrow_bf16`` (``set_deterministic_conv("own_all")``) instead of unfold + GEMM."""
-    return _det_now() and get_deterministic_conv() == "own_all"
+    ``dmm_wgrad3x3_narrow_bf16`` (``set_deterministic_conv("own_all")`` / ``"own_stem"``) instead of unfold + GEMM."""
+    return _det_now() and get_deterministic_conv() in ("own_all", "own_stem")
+
+
+def _stem_conv_now() -> bool:
+    """The deterministic mode's 7x7 stem (``_stem_ok``) on ``dmm_conv7x7s2_stem_bf16`` / ``dmm_wgrad7x7s2_stem_bf16``
+    (``set_deterministic_conv("own_stem")``) instead of unfold + GEMM."""
+    return _det_now() and get_deterministic_conv() == "own_stem"
 
 
 def _det_ws(nbytes: int, device) -> torch.Tensor:
@@ -298,11 +306,15 @@ _DET_AS_GEMM = ("forward", "dgrad")     # (module switch for the A/B in tools/cf
 
 def _wgrad_launch(rec):
     """One weight gradient, ``rec`` = (kind, dy, x, dims, dw): "1x1" (rows, co, ci), "3x3" (B, H, W, ci, co, stride, Ho, Wo),
-    "3x3n" (B, H, W, ci, co; the narrow kernel, sized and launched by its wrapper in ``ops``) -> dw, overwritten."""
+    "3x3n" (B, H, W, ci, co; the narrow kernel, sized and launched by its wrapper in ``ops``), "7x7s" (B, H, W; the stem kernel,
+    likewise) -> dw, overwritten."""
     from . import _lib, ops
     kind, dy, x, dims, dw = rec
     if kind == "3x3n":
         ops.wgrad3x3_narrow_bf16(dy, x, out=dw)
+        return
+    if kind == "7x7s":
+        ops.wgrad7x7s2_stem_bf16(dy, x, out=dw)
         return
     need = _lib.load().dmm_wgrad_workspace_bytes
     dev = x.device
@@ -341,14 +353,23 @@ def _narrow_ok(m: nn.Conv2d) -> bool:
             and m.in_channels % 32 == 0 and m.out_channels % 32 == 0 and not _wgrad_ok(m))
 
 
+def _stem_ok(m: nn.Conv2d) -> bool:
+    """The ResNet stem: 7x7 / stride 2 / padding 3, 3 -> 64, no groups, no dilation."""
+    return (m.kernel_size == (7, 7) and m.stride == (2, 2) and m.padding == (3, 3) and m.groups == 1 and m.dilation == (1, 1)
+            and m.in_channels == 3 and m.out_channels == 64)
+
+
 def _conv_route(m: nn.Module, linear_1x1: bool = True, own_wgrad: bool = True) -> Optional[str]:
     """The route of convolution module ``m`` on a bf16 activation on the device: "1x1" (``_Conv1x1Fn``), "3x3" (``_Conv3x3Fn``),
-    "narrow" (``_ConvNarrowFn``: only under the narrow setting, ``_narrow_conv_now``), or None (the stock ops).  ``_conv`` takes
-    it, and ``TrainEncoder._tick`` prepares the weight copies of exactly the modules it names."""
+    "narrow" (``_ConvNarrowFn``: only under the narrow setting, ``_narrow_conv_now``), "stem" (``_ConvStemFn``: only under the
+    stem setting, ``_stem_conv_now``, and for an input that requires no gradient), or None (the stock ops).  ``_conv`` takes
+    it, and ``TrainEncoder._tick`` prepares the weight copies of exactly the 1x1 / 3x3 / narrow modules it names."""
     if not (own_wgrad and isinstance(m, nn.Conv2d)):
         return None
     if not _wgrad_ok(m):
-        return "narrow" if _narrow_ok(m) and _narrow_conv_now() else None
+        if _narrow_ok(m) and _narrow_conv_now():
+            return "narrow"
+        return "stem" if _stem_ok(m) and _stem_conv_now() else None
     if linear_1x1 and m.kernel_size == (1, 1) and m.padding == (0, 0) and m.bias is None:
         return "1x1"
     return "3x3" if m.kernel_size == (3, 3) and m.padding == (1, 1) else None
@@ -532,6 +553,35 @@ class _ConvNarrowFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
+class _ConvStemFn(torch.autograd.Function):
+    """The 7x7 / stride 2 / padding 3 stem (``_stem_ok``) of a channels-last bf16 image with an fp32 MASTER weight in the
+    deterministic mode under ``set_deterministic_conv("own_stem")`` (resolved by ``_conv`` in the forward; the backward needs no
+    setting): forward and bias add by ``dmm_conv7x7s2_stem_bf16``, the weight gradient -- fp32 from the kernel, in the
+    master's layout -- by ``dmm_wgrad7x7s2_stem_bf16`` (deferred and captured like the others), the bias gradient by the
+    deterministic statistics kernel.  No data gradient: ``_conv`` sends an input that requires one to ``_DetConvFn``."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from . import ops
+        w, _, b = _bf16_weights(weight, bias, None, False)
+        y = ops.conv7x7s2_stem_bf16(x, w, b)
+        ctx.save_for_backward(x)
+        ctx.has_bias, ctx.det = bias is not None, _det_now()
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("_ConvStemFn has no data gradient: the image must not require one")
+        dy = dy.contiguous(memory_format=_CL)
+        dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x.device)        # the master's own layout
+        _wgrad(("7x7s", dy, x, (x.shape[0], x.shape[2], x.shape[3]), dw))
+        db = _channel_sums(dy, ctx.det) if ctx.has_bias else None
+        return None, dw, db
+
+
 def _channel_sums(dy, det: bool = False):
     """sum over (batch, rows, columns) of a channels-last bf16 gradient in fp32 (a bias gradient): the statistics kernel's first
     row -- one launch where ``dy.float().sum((0, 2, 3))`` is a cast of the whole tensor and a reduction.  ``det``: the
@@ -555,7 +605,8 @@ def _conv(x, m: nn.Conv2d, dtype, linear_1x1: bool = True, own_wgrad: bool = Tru
     MIOpen, and both take their weight gradient from ``dmm_wgrad*_bf16``; anything else (the 7x7 stem, widths that are not a
     multiple of 64, fp32 mode, the CPU) goes through the stock ops with a differentiable cast of the weight -- except, in the
     deterministic mode under ``set_deterministic_conv("own_all")``, a narrow 3x3 convolution (``_narrow_ok``), which runs on
-    ``_ConvNarrowFn``."""
+    ``_ConvNarrowFn``, and, under ``"own_stem"``, the 7x7 stem (``_stem_ok``) of an input that requires no gradient, which runs
+    on ``_ConvStemFn``."""
     route = _conv_route(m, linear_1x1, own_wgrad) if x.is_cuda and dtype == torch.bfloat16 and x.dtype == dtype else None
     if route == "1x1":
         return _Conv1x1Fn.apply(x.contiguous(memory_format=_CL), m.weight, m.stride[0], shadow)
@@ -563,6 +614,8 @@ def _conv(x, m: nn.Conv2d, dtype, linear_1x1: bool = True, own_wgrad: bool = Tru
         return _Conv3x3Fn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias, m.stride[0], shadow)
     if route == "narrow":
         return _ConvNarrowFn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias, shadow)
+    if route == "stem" and not x.requires_grad:
+        return _ConvStemFn.apply(x.contiguous(memory_format=_CL), m.weight, m.bias)
     b = None if m.bias is None else m.bias.to(dtype)
     if linear_1x1 and m.kernel_size == (1, 1) and m.padding == (0, 0) and m.groups == 1 and m.dilation == (1, 1):
         if m.stride != (1, 1):
@@ -597,7 +650,7 @@ class _DetConvFn(torch.autograd.Function):
     weight, the bias gradient a torch reduction -- the convolutions under cudnn.deterministic, like the rest of the mode's
     library calls.
 
-    With ``set_deterministic_conv("own")`` the forward of a plain convolution (no groups, no dilation) and its stride-1 data
+    With ``set_deterministic_conv("own")`` (and the settings above it) the forward of a plain convolution (no groups, no dilation) and its stride-1 data
     gradient (the forward convolution of dy) are an unfold + ONE GEMM too, the product the weight gradient already takes: the
     7x7 stem and the 32-channel heads leave MIOpen's naive kernel (profiles/r08_deterministic_conv.md)."""
 
@@ -605,7 +658,7 @@ class _DetConvFn(torch.autograd.Function):
     def forward(ctx, x, w, b, stride, padding, dilation, groups):
         ctx.save_for_backward(x, w)
         ctx.conf = (tuple(stride), tuple(padding), tuple(dilation), groups, b is not None)
-        ctx.own = get_deterministic_conv() in ("own", "own_all")
+        ctx.own = get_deterministic_conv() in _OWN_SETTINGS
         if ctx.own and "forward" in _DET_AS_GEMM and groups == 1 and tuple(dilation) == (1, 1):
             return _conv_as_gemm(x, w, b, tuple(stride), tuple(padding))
         with library_flags(True):
@@ -784,7 +837,8 @@ class TrainEncoder(nn.Module):
         from . import _lib
         memo = self._wprep
         own = _own_conv_now()                           # every data gradient runs on the flipped weight, whatever the shape
-        key = tuple(id(m) for m in convs) + (own, _narrow_conv_now())     # (tables of one setting are not reused under another)
+        # (tables of one setting are not reused under another)
+        key = tuple(id(m) for m in convs) + (own, _narrow_conv_now(), _stem_conv_now())
         ptrs = tuple(m.weight.data_ptr() for m in convs)
         got = memo.get(key)
         if got is None or got[0] != ptrs:
@@ -959,7 +1013,7 @@ class TrainEncoder(nn.Module):
         # (the mode is part of the key: a graph captured in one mode never replays in the other)
         conv = get_deterministic_conv() if det else "library"
         key = (tuple(img.shape), img.dtype, img.device.index, self.skips_need_grad, bn_groups, conv,
-               conv in ("own", "own_all"), det)
+               conv in _OWN_SETTINGS, det)
         plans = self._plans.setdefault(key, [])
         # a plan's static buffers belong to ONE forward until its backward has run: a second forward of the same shape before
         # that (the trainer's clip: one encoder call per frame, one backward; trainer.py:95-131) takes / captures another plan

@@ -841,6 +841,35 @@ DMM_API size_t dmm_wgrad3x3_narrow_workspace_bytes(int B, int H, int W, int ci, 
 DMM_API int dmm_wgrad3x3_narrow_bf16(const void *dy, const void *x, int B, int H, int W, int ci, int co, float *dw,
                                      void *workspace, size_t workspace_bytes, dmm_stream_t stream);
 
+/* (10f) The 7x7 / stride 2 / padding 3 STEM convolution (3 -> 64, dmm/modules/vision.py's ResNet conv1) of the training encoder
+ * for the DETERMINISTIC mode, as train.py:46 runs it under cudnn.deterministic: three input channels are 6-byte pixels, which
+ * the 16-byte operand pieces of (10b) / (10d) / (10e) cannot take.  ci = 3 and co = 64 are fixed.
+ * dmm_conv7x7s2_stem_bf16:
+ *   y[b, ho, wo, co] = bf16( bias[co] + sum_(kh,kw,ci) x[b, 2ho+kh-3, 2wo+kw-3, ci] * w[co, kh, kw, ci] )        (zero outside)
+ *   x [B, H, W, 3] and y [B, Ho, Wo, 64] dense channels-last bf16, Ho = (H-1)/2 + 1, Wo likewise; w the bf16 channels-last weight
+ *   [64, 7, 7, 3] (weight.to(bf16, channels_last)); bias bf16 [64] or NULL.  fp32 accumulation, the bias added in fp32, ONE
+ *   rounding.  MFMA 32x32x16 bf16 over K = 7 kernel rows x 32 lanes (21 real; the other 11 are exact zeros on BOTH operands: no
+ *   value from outside the 7x7 window or from outside the tensor is fetched, let alone multiplied).  No atomics, no split of the
+ *   reduction, no workspace: the summation order of an output element is a function of nothing but a term's position in the
+ *   147-term reduction, an image's bits do not depend on its batch, results are bit-identical call after call, eagerly and in
+ *   graph replay.  x needs only its natural 2-byte alignment (an image row is 6 W bytes); w and y 16-byte; the bias 2-byte.
+ *   Answers, before any launch: DMM_ERR_BAD_ARG for B < 0, H / W <= 0, B * H * W > 2^56; DMM_OK for B == 0; DMM_ERR_BAD_ARG for
+ *   a null x / w / y, a misaligned pointer.
+ * dmm_wgrad7x7s2_stem_bf16:  dw[co, ci, kh, kw] = sum_(b,ho,wo) dy[(b,ho,wo), co] * x[b, 2ho+kh-3, 2wo+kw-3, ci]   (zero outside),
+ *   dy [B*Ho*Wo, 64] dense bf16 (16-byte aligned), x as above; dw fp32 (4-byte aligned) in the parameter's own [64, 3, 7, 7]
+ *   layout, OVERWRITTEN (no zeroing, no atomics: pixel slabs -> fp32 partial tables in the caller's workspace -> summed in slab
+ *   order by a second launch, as (10b) / (10e)).  The slab count is a function of (B, H, W) only.  workspace:
+ *   dmm_wgrad7x7s2_stem_workspace_bytes(B, H, W) bytes, 4-byte aligned (0 for arguments the entry rejects and for B == 0).
+ *   Answers, before any launch: DMM_ERR_BAD_ARG for B < 0, H / W <= 0, B * H * W > 2^56, a null or misaligned dw; for B == 0 dw
+ *   is zeroed and the answer is DMM_OK; DMM_ERR_BAD_ARG for a null or misaligned dy / x; DMM_ERR_WORKSPACE for a null or short
+ *   workspace; DMM_ERR_BAD_ARG for a misaligned one.
+ * No data gradient: the image never requires one. */
+DMM_API int dmm_conv7x7s2_stem_bf16(const void *x, const void *w, const void *bias, int B, int H, int W, void *y,
+                                    dmm_stream_t stream);
+DMM_API size_t dmm_wgrad7x7s2_stem_workspace_bytes(int B, int H, int W);
+DMM_API int dmm_wgrad7x7s2_stem_bf16(const void *dy, const void *x, int B, int H, int W, float *dw, void *workspace,
+                                     size_t workspace_bytes, dmm_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------------
  * (11) HIP-graph hygiene for captured steps that contain other libraries' launches (MIOpen, hipBLASLt, torch): between the
  * end of a stream capture and hipGraphInstantiate, replace every memset node (flags & 1; element size 1 / 2 / 4) and every

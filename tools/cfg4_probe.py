@@ -4,8 +4,8 @@ its time on MI355X: memory format, dtype policy, who runs the 1x1 convolutions, 
 
     python tools/cfg4_probe.py <variant> [--find] [--steps K]       one variant, one JSON line
         [--deterministic]   the step in dmm_net_amd's deterministic mode (set_deterministic(True))
-        [--det-conv {library,own,own_all}]   who runs the mode's 3x3 convolutions (set_deterministic_conv; own_all: the
-                            32-channel heads on the narrow kernels too); a train variant with
+        [--det-conv {library,own,own_all,own_stem}]   who runs the mode's convolutions (set_deterministic_conv; own_all: the
+                            32-channel heads on the narrow kernels too; own_stem: the 7x7 stem as well); a train variant with
                             "nogemmfwd" / "nogemmdx" in its name keeps the forwards / data gradients of the stem and the
                             32-channel heads on MIOpen under "own"
         [--repeats R]       R timed runs of K steps: ms_per_step_wall is their median, with min / max beside it
@@ -32,8 +32,8 @@ def one(variant, find, steps, frames):
     torch.backends.cudnn.benchmark = bool(find)
     det = "--deterministic" in sys.argv
     det_conv = sys.argv[sys.argv.index("--det-conv") + 1] if "--det-conv" in sys.argv else "library"
-    if det_conv not in ("library", "own", "own_all"):
-        sys.exit("--det-conv takes library, own or own_all")
+    if det_conv not in ("library", "own", "own_all", "own_stem"):
+        sys.exit("--det-conv takes library, own, own_all or own_stem")
     import dmm_net_amd
     dmm_net_amd.set_deterministic_conv(det_conv)
     if det:
@@ -154,7 +154,8 @@ def one(variant, find, steps, frames):
                       "ms_per_step_wall": round(wall, 3), "wall_min_ms": round(min(walls), 3),
                       "wall_max_ms": round(max(walls), 3), "fwd_ms": round(fwd, 3), "bwd_ms": round(bwd, 3),
                       "settle_s": round(settle_s, 1), "loss": float(loss),
-                      "mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 2)}), flush=True)
+                      "mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 2),
+                      "mem_MiB": round(torch.cuda.max_memory_allocated() / 2**20, 1)}), flush=True)
 
 
 def matrix(out):
